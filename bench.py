@@ -2,7 +2,12 @@
 """Throughput benchmark of the Segment-Anything hot path (BASELINE.json metric:
 images/sec encode+mask @1024x1024).
 
-  python bench.py --gpus N --steps K --warmup W [--model vit_b] [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--model vit_b] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times ONE block of K steps, optionally writes the masks of the last timed step
+(--dump-outputs) and prints the JSON line.  Everything else it can measure or check (profiled repeats and the roofline,
+encoder_only, hbm_kernels, abi_path, decode_only, the configs / ViT-H legs, cpu_baseline and the parity checks against
+the oracle, inproc_replicas at N > 1) runs only with --full.
 
 One process per GPU (N > 1: launched by torch.distributed.run, RCCL only for the barrier and the
 max-over-ranks of the elapsed time: images are independent, there is no data-path collective).
@@ -11,11 +16,21 @@ resident in HBM: pre-process -> ViT encoder -> prompt encoder + mask decoder (on
 image, single-mask mode) -> bilinear upsample + threshold, masks left in HBM.  At N = 1 the default
 workload is BASELINE.json configs[1] (ViT-B, batch 1, one point prompt).
 
-Timing: the block of K steps is timed `--repeats` times (default 21), each repeat bracketed by a barrier and
-torch.cuda.synchronize() on both sides and reduced to the MAX over ranks; `value` comes from the MEDIAN repeat
-(`ms_per_step` likewise; every repeat's time is in `repeat_ms`).
+Timing: after W warm-up steps the device keeps stepping for --settle-seconds (default 1 s; the first ~0.2 s of load runs
+slower than the steady state), then the block of K steps is timed `--repeats` times (default 1; 21 with --full), each
+repeat bracketed by a barrier and torch.cuda.synchronize() on both sides and reduced to the MAX over ranks; `value` comes
+from the MEDIAN repeat (`ms_per_step` likewise; every repeat's time is in `repeat_ms`).
 
-Besides the contract fields the JSON line carries
+--dump-outputs DIR: after the timed steps, the masks the last timed step wrote (what a caller of dlimg_amd_encode_and_mask
+receives; N > 1: every rank's, gathered in item order) go to DIR/masks.npy as float32 [images, 1024, 1024] (0 / 255).
+Above MAX_DUMP_BYTES a fixed seeded sample of whole masks is written.  Inputs and weights are seeded, so two builds run
+with the same arguments can be compared output for output.
+
+Every run's line carries `rccl`: at N > 1 the ranks counted by an all-reduce of ones and the gather of the finished masks
+to every rank (RCCL all_gather over xGMI, after the timed region: no collective is on the data path); a multi-GPU line
+is only printed when both check out.
+
+With --full the JSON line carries besides the contract fields
   roofline      dominant kernel (the f16 MFMA GEMMs of the encoder): algorithmic FLOPs / the kernels' own execution
                 time (HIP events attached to each dispatch) in a profiled repeat that runs on ONE lane, i.e. every
                 kernel alone on the chip; chip_frac = all FLOPs of a step / ms_per_step / peak, the only figure that
@@ -28,8 +43,6 @@ Besides the contract fields the JSON line carries
   mask_iou      IoU of the HIP mask against the oracle's mask for that image (+ logits_check: max-abs error of the
                 decoder's logits / IoU predictions / the embedding against the oracle, fraction of near-zero logits)
   stages        per-stage breakdown of the profiled repeat (profile_mode says how it was taken)
-  rccl          N > 1: ranks counted by an all-reduce of ones, and the optional gather of the finished masks to
-                every rank (RCCL all_gather over xGMI, after the timed region: no collective is on the data path)
   inproc_replicas  N > 1: the same node driven the way a host of the reference would drive it -- ONE process, ONE
                 Environment over all N GPUs (DLIMGEDIT_DEVICES), 8 images per GPU per call through slots 13 / 14 of the
                 drop-in table, masks gathered into one buffer on GPU 0 by the library (peer copies over xGMI)
@@ -64,6 +77,19 @@ sys.path.insert(0, str(ROOT))
 MFMA_F16_PEAK_TFLOPS = 2500.0      # MI355X dense f16/bf16 (MI355X_MICROARCH.md, spec)
 HBM_PEAK_GBS = 8000.0
 HBM_COPY_GBS = 6290.0               # what a float4 copy kernel reaches from HBM (MI355X_MICROARCH.md)
+MAX_DUMP_BYTES = 64 * 10**6         # --dump-outputs: at most this much float32 mask data
+
+
+def dump_outputs(out_dir: str, masks) -> None:
+    """masks: uint8 [n, 1024, 1024] (numpy) -> out_dir/masks.npy as float32; a fixed seeded sample of whole masks when the
+    full set would exceed MAX_DUMP_BYTES."""
+    masks = np.asarray(masks)
+    per_mask = masks[0].size * 4
+    keep = max(1, MAX_DUMP_BYTES // per_mask)
+    if masks.shape[0] > keep:
+        masks = masks[np.sort(np.random.default_rng(0).choice(masks.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "masks.npy"), masks.astype(np.float32))
 
 
 def synthetic_image(seed: int, width: int = 1024, height: int = 1024) -> np.ndarray:
@@ -278,9 +304,17 @@ def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=21, help="timed repeats of the block of --steps steps (median reported)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed repeats of the block of --steps steps (median reported; default 1, with --full 21)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline (roofline, ABI and decode rates, configs / "
+                         "ViT-H legs, cpu_baseline and parity against the oracle, inproc_replicas)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the masks of the last timed step to DIR/masks.npy (float32)")
     ap.add_argument("--no-abi-path", action="store_true")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--settle-seconds", type=float, default=1.0,
+                    help="after the warm-up steps, keep stepping this long before the timed block (clocks reach steady state)")
     ap.add_argument("--model", default="vit_b")
     ap.add_argument("--batch", type=int, default=1, help="images per GPU per step")
     ap.add_argument("--seed", type=int, default=0)
@@ -296,6 +330,9 @@ def main() -> None:
                          "CPU (gloo); the line is marked, its numbers mean nothing (tests/test_bench_cpu.py)")
     ap.add_argument("--inproc-images-per-gpu", type=int, default=8, help="images per GPU per call of the inproc_replicas leg")
     args = ap.parse_args()
+    full = args.full
+    if args.repeats is None:
+        args.repeats = 21 if full else 1
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus, sys.argv[1:]))      # before anything here has touched the GPU
@@ -387,6 +424,16 @@ def main() -> None:
 
     for _ in range(args.warmup):
         step()
+    engine_sync()
+    # The first ~0.2 s of sustained load runs slower than the steady state (the first repeat of every committed profile: about
+    # +15 ms over a 200-step block, +4 ms over a 20-step one), which a few warm-up steps do not cover.  One timed block is
+    # the default, so the device keeps stepping for --settle-seconds first and the block reads the steady state.
+    if not stub:
+        settle_end = time.perf_counter() + args.settle_seconds
+        while time.perf_counter() < settle_end:
+            for _ in range(25):
+                step()
+            engine_sync()
     sync_all()
     repeat_s, own_s = [], []
     for _ in range(max(1, args.repeats)):
@@ -405,6 +452,14 @@ def main() -> None:
     # every rank's own clock of the median repeat (N > 1): the MAX above is what `value` uses, this shows who set it
     median_repeat = int(np.argsort(repeat_s)[len(repeat_s) // 2])
     per_rank_s = sharding.all_ranks(own_s[median_repeat], device=coll_dev) if world > 1 else [own_s[median_repeat]]
+    if args.dump_outputs and world == 1:        # N > 1: the gathered masks, below
+        if stub:
+            last = local_masks.numpy()
+        else:
+            last = np.empty((B, 1024, 1024), np.uint8)
+            for i, p in enumerate(mask_ptrs):
+                ext.copy_to_host(env, last[i], p)
+        dump_outputs(args.dump_outputs, last)
 
     decoder_flops = DECODER_FLOPS                # per prompt
     result = None
@@ -466,6 +521,8 @@ def main() -> None:
                                   "own_share_intact_on_every_rank": all_ok}), file=sys.stderr)
             dist.destroy_process_group()
             raise SystemExit(3)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, gathered.cpu().numpy())
         if rank == 0:
             result["rccl"] = {"rccl_ranks": ranks, "backend": "gloo (no device: orchestration REHEARSAL on CPU, not a result)" if stub else
                               "gloo (one-GPU REHEARSAL, not a result)" if args.rehearse_gloo else "nccl (RCCL)",
@@ -479,7 +536,7 @@ def main() -> None:
         result["rccl"] = {"rccl_ranks": 1, "gather": None}
 
     # ---- N > 1: the node driven from ONE process through the drop-in table (rank 0; the other ranks wait on the HOST)
-    if world > 1 and not stub:
+    if world > 1 and not stub and full:
         if rank == 0:
             devices = [0] * world if args.rehearse_gloo else list(range(world))
             try:
@@ -492,7 +549,7 @@ def main() -> None:
     # ---- profiled repeats of the same steps: HIP events attached to every GEMM dispatch, on the stream it is launched on.
     # First in the regime `value` is measured in (all lanes, requests coalesced as in the timed region), then with every
     # request on lane 0 (each kernel alone on the chip).
-    if rank == 0 and not stub:
+    if rank == 0 and not stub and full:
         def profiled(mode):
             ext.set_profiling(env, mode)
             ext.take_stage_stats(env)
@@ -655,7 +712,7 @@ def main() -> None:
                              if enc_ms > 0 else 0.0}
 
     # ---- per-stage rates SURVEY.md section 8d asks for next to the metric: encoder alone (device resident, all lanes)
-    if rank == 0 and world == 1 and not stub:
+    if rank == 0 and world == 1 and not stub and full:
         for _ in range(2):
             ext.encode_only(env, views)
         ext.synchronize(env)
@@ -669,7 +726,7 @@ def main() -> None:
     # ---- the two pixel kernels against the HBM rate (north_star: "HBM GB/s for the pre/post kernels"): one image per
     # launch sits on the launch floor (`stages` above), so they are also clocked with 16 images / masks per launch.
     # Launches rotate over 768 MB of distinct inputs and outputs (3 x the 256 MB Infinity Cache): what moves is HBM traffic.
-    if rank == 0 and world == 1 and not stub:
+    if rank == 0 and world == 1 and not stub and full:
         pre_b, post_b = 4 * 1024 * 1024 + 4096 * 768 * 2, 256 * 256 * 4 + 1024 * 1024      # algorithmic bytes per image / mask
         hk = {"unit": "GB/s", "peak": HBM_PEAK_GBS, "achievable": HBM_COPY_GBS,
               "achievable_note": "float4 copy kernel, HBM to HBM (MI355X_MICROARCH.md)",
@@ -689,7 +746,7 @@ def main() -> None:
         result["hbm_kernels"] = hk
 
     # ---- the drop-in ABI itself: host buffers in and out (PCIe inclusive), rank 0, N = 1 only
-    if rank == 0 and world == 1 and not stub and not args.no_abi_path:
+    if rank == 0 and world == 1 and not stub and full and not args.no_abi_path:
         import threading
         view = api.ImageView(imgs[0], api.Channels.rgba)
 
@@ -782,7 +839,7 @@ def main() -> None:
 
     # ---- BASELINE.json configs 3-5 at one GPU's share and the ViT-H model, in the driver's own run: the
     # headline above is configs[1]; these legs are short (--leg-seconds each) and run after it, rank 0, N = 1 only
-    if rank == 0 and world == 1 and not stub and not args.no_config_legs:
+    if rank == 0 and world == 1 and not stub and full and not args.no_config_legs:
         legs = {args.model: config_legs(api, ext, env, cfg, args.leg_seconds)}
         if args.model == "vit_b" and args.model_dir is None:
             # configs[3] / configs[4] name the ViT-H encoder: a second Environment on seeded synthetic ViT-H weights (this
@@ -815,7 +872,7 @@ def main() -> None:
                                      "configs[1].  chip_frac = FLOPs done per second / 2500 TFLOP/s", **legs}
 
     # ---- CPU baseline (oracle port) + mask IoU, rank 0, N = 1 only
-    if rank == 0 and world == 1 and not stub and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not stub and full and not args.no_cpu_baseline:
         from oracle import sam_oracle as O
         if params is None:
             params = W.load_weights(Path(model_dir) / "segmentation" / W.weight_file_name(cfg))[1] \

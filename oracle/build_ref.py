@@ -19,11 +19,18 @@ REF_INCLUDE = Path("/root/reference/src/include")
 OUT = Path(__file__).resolve().parent / "_ref"
 
 
+def _reference_present() -> bool:
+    try:
+        return (REF_INCLUDE / "dlimgedit" / "dlimgedit.hpp").exists()
+    except OSError:             # a tree the building user may not read (Path.exists raises on EACCES): the same as absent
+        return False
+
+
 def build_abi_consumer() -> Path | None:
-    """Returns the binary path, or None when the reference tree is not present (GPU box)."""
+    """Returns the binary path, or None when the reference tree is not present (GPU box) or not readable."""
     exe = OUT / "abi_consumer"
     src = ROOT / "tests" / "abi_consumer.cpp"
-    if not (REF_INCLUDE / "dlimgedit" / "dlimgedit.hpp").exists():
+    if not _reference_present():
         return exe if exe.exists() else None
     OUT.mkdir(parents=True, exist_ok=True)
     if exe.exists() and exe.stat().st_mtime > src.stat().st_mtime:

@@ -8,6 +8,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -66,3 +68,41 @@ def test_gemm_shape_table_matches_the_survey_figures():
     assert 150 < intensity["gemm_proj"] < 155 and intensity["gemm_patch"] < 312.5
     assert all(intensity[k] > 312.5 for k in ("gemm_fc2", "gemm_norm", "gemm_norm_gelu"))
     assert abs(four["gemm_proj"]["bytes"] / 1e6 - 127.5) < 1.0
+
+
+def test_plain_run_times_one_block_of_the_given_steps():
+    """A plain run times exactly --steps steps once (ms_per_step is that block's time per step) and measures nothing else."""
+    r = _run(["--stub-device", "--steps", "4", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert d["steps"] == 4 and d["repeats"] == 1 and len(d["repeat_ms"]) == 1
+    assert abs(d["ms_per_step"] * 4 - d["repeat_ms"][0]) < 1e-2
+    for key in ("roofline", "stages", "abi_path", "decode_only", "configs", "cpu_baseline", "mask_iou", "inproc_replicas"):
+        assert key not in d
+
+
+def test_dump_outputs_writes_the_last_step_masks(tmp_path):
+    """--dump-outputs DIR: the masks of the last timed step as float32, every rank's in item order at N > 1."""
+    one, two = tmp_path / "one", tmp_path / "two"
+    r = _run(["--stub-device", "--steps", "3", "--warmup", "1", "--dump-outputs", str(one)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    m = np.load(one / "masks.npy")
+    assert m.dtype == np.float32 and m.shape == (1, 1024, 1024)
+    assert (m[0, :8] == 1).all() and m[0, 8, 0] == 4            # the stand-in's pattern of rank 0, call 4 = warm-up + 3 steps
+    r = _run(["--gpus", "2", "--stub-device", "--steps", "2", "--warmup", "1", "--dump-outputs", str(two)])
+    assert r.returncode == 0, r.stderr[-2000:]
+    m = np.load(two / "masks.npy")
+    assert m.shape == (2, 1024, 1024) and (m[0, :8] == 1).all() and (m[1, :8] == 17).all()
+
+
+def test_dump_outputs_samples_whole_masks_under_the_size_cap(tmp_path):
+    sys.path.insert(0, str(ROOT))
+    import bench
+    masks = np.arange(20, dtype=np.uint8)[:, None, None] * np.ones((1, 1024, 1024), np.uint8)
+    bench.dump_outputs(str(tmp_path / "a"), masks)
+    bench.dump_outputs(str(tmp_path / "b"), masks)
+    a, b = np.load(tmp_path / "a" / "masks.npy"), np.load(tmp_path / "b" / "masks.npy")
+    assert (tmp_path / "a" / "masks.npy").stat().st_size <= bench.MAX_DUMP_BYTES + 4096
+    assert a.dtype == np.float32 and 1 <= a.shape[0] < 20 and np.array_equal(a, b)
+    picked = a[:, 0, 0]
+    assert np.all(np.diff(picked) > 0) and all((a[i] == picked[i]).all() for i in range(a.shape[0]))

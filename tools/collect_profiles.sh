@@ -8,7 +8,7 @@ MODEL="${1:-vit_b}"
 export GPU_MAX_HW_QUEUES=8 DLIMGEDIT_PLAIN_STREAMS=1
 O=$R/gpurun_out/prof_$MODEL
 rm -rf "$O"; mkdir -p "$O"
-B="python3 $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-abi-path --no-config-legs --repeats 5 --model $MODEL"
+B="python3 $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-abi-path --no-config-legs --repeats 5 --model $MODEL"
 DEPTH=$(python3 -c "import sys; sys.path.insert(0, '$R'); from dlimgedit_amd.sam_config import get_config; print(get_config('$MODEL').depth)")
 timeout -k 10 200 rocprofv3 --kernel-trace -d $O/kt -o kt -- $B > $O/bench_kt.log 2>&1 && echo kt ok &&
 DLIMGEDIT_SINGLE_LANE=1 timeout -k 10 200 rocprofv3 --kernel-trace -d $O/kt1 -o kt1 -- $B > $O/bench_kt1.log 2>&1 && echo kt1 ok &&

@@ -110,7 +110,7 @@ print(f"sum over these kernels: {total_mj:.0f} mJ per image, kernels running one
 # ---- the steady state of the lanes: the official command as one long block
 import json  # noqa: E402
 steps = 3000 if D <= 768 else 600
-cmd = [sys.executable, str(Path(__file__).resolve().parent.parent / "bench.py"), "--model", model, "--steps", str(steps), "--warmup", "5",
+cmd = [sys.executable, str(Path(__file__).resolve().parent.parent / "bench.py"), "--full", "--model", model, "--steps", str(steps), "--warmup", "5",
        "--repeats", "3", "--no-cpu-baseline", "--no-abi-path", "--no-config-legs"]
 # sampled from start to end: model load and warm-up draw far less than the timed blocks, so the steady state is read from the
 # samples within 10 % of the highest power seen (their median, with the clock samples taken at the same moments)
