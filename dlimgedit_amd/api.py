@@ -471,6 +471,7 @@ class ext:
                 "dlimg_amd_test_layernorm": ([vp, vp, vp, cf, ci, ci, ci, vp, vp], ci),
                 "dlimg_amd_test_attention": ([ci, vp, vp, vp, vp, ci, ci, ci, vp], ci),
                 "dlimg_amd_test_resize": ([vp, ci, ci, ci, ci, ci, ci, vp], ci),
+                "dlimg_amd_test_decode": ([vp, ci, vp, ci, vp, vp, vp, vp, vp], ci),
                 "dlimg_amd_bench_attention": ([ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_prepost": ([ci, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_gemm": ([ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
@@ -496,7 +497,7 @@ class ext:
                "dlimg_amd_test_postprocess", "dlimg_amd_test_postprocess_batch", "dlimg_amd_test_force_gemm_tile",
                "dlimg_amd_test_force_gemm_consumer_tile", "dlimg_amd_test_gemm", "dlimg_amd_test_gemm_ln",
                "dlimg_amd_test_lane_worker", "dlimg_amd_test_gemm_stream", "dlimg_amd_test_layernorm",
-               "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_bench_attention",
+               "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps")
 
@@ -804,6 +805,22 @@ class ext:
         _check_hook(cls._h().dlimg_amd_test_attention(int(is_global), qkv.ctypes.data, cls._ptr(qkv_bias), rel_h.ctypes.data,
                                                  rel_w.ctypes.data, batch, heads, hd, out.ctypes.data))
         return out
+
+    @classmethod
+    def test_decode(cls, env: Environment, embeddings: np.ndarray, emb_index, coords, labels):
+        """The product's decoder (one SamModel::decode call for all prompts) on given embeddings [n][4096][256]: prompt i
+        decodes embeddings[emb_index[i]] with the packed prompt coords[i] ([2][2], resized-image pixels) and labels[i]
+        ([2]).  Returns (logits [count][4][256][256], iou [count][4])."""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, 4096, 256)
+        idx = np.ascontiguousarray(emb_index, dtype=np.int32).reshape(-1)
+        count = idx.size
+        c = np.ascontiguousarray(coords, dtype=np.float32).reshape(count, 4)
+        l = np.ascontiguousarray(labels, dtype=np.float32).reshape(count, 2)
+        logits = np.empty((count, 4, 256, 256), dtype=np.float32)
+        iou = np.empty((count, 4), dtype=np.float32)
+        _check_hook(cls._h().dlimg_amd_test_decode(env.handle(), emb.shape[0], emb.ctypes.data, count, idx.ctypes.data,
+                                                   c.ctypes.data, l.ctypes.data, logits.ctypes.data, iou.ctypes.data))
+        return logits, iou
 
     @classmethod
     def test_resize(cls, pixels: np.ndarray, channels: Channels, out_w: int, out_h: int) -> np.ndarray:

@@ -383,6 +383,29 @@ DLIMG_API int dlimg_amd_test_attention(int global, uint16_t const* qkv, float co
     });
 }
 
+DLIMG_API int dlimg_amd_test_decode(dlimg_Environment env, int n_emb, float const* emb, int count, int const* emb_index,
+                                    float const* coords, float const* labels, float* out_logits, float* out_iou) {
+    return guarded([&] {
+        if (n_emb < 1 || count < 1) throw Exception("test_decode: n_emb and count must be at least 1");
+        if (!emb || !emb_index || !coords || !labels || !out_logits || !out_iou) throw Exception("test_decode: null pointer");
+        for (int i = 0; i < count; ++i)
+            if (emb_index[i] < 0 || emb_index[i] >= n_emb) throw Exception("test_decode: embedding index out of range");
+        // the product's decoder on a lane of replica 0, exactly as dlimg_amd_get_logits runs it: one decode() call for all
+        // `count` prompts (chunks of 16 and all)
+        SamModel& m = impl(env).next_lane(0);
+        std::lock_guard<std::mutex> lock(m.mutex());
+        HIP_CHECK(hipSetDevice(m.device()));
+        const size_t per = (size_t)kTokens * kEmbedDim;
+        Upload<float> dev(emb, (size_t)n_emb * per);
+        std::vector<float const*> ptrs(count);
+        for (int i = 0; i < count; ++i) ptrs[i] = dev.get() + (size_t)emb_index[i] * per;
+        m.decode(ptrs.data(), coords, labels, count);
+        m.synchronize();
+        download(out_logits, m.logits(), (size_t)count * 4 * kLowRes * kLowRes);
+        download(out_iou, m.iou(), (size_t)count * 4);
+    });
+}
+
 DLIMG_API int dlimg_amd_test_resize(uint8_t const* pixels, int width, int height, int stride, int channels, int out_w,
                                     int out_h, uint8_t* out_pixels) {
     return guarded([&] {

@@ -78,6 +78,13 @@ DLIMG_API int dlimg_amd_test_layernorm(float const* x, float const* w, float con
  * global != 0: rel tables are [127][hd]; else windowed 14x14 with [27][hd] tables and qkv_bias [3*D]. */
 DLIMG_API int dlimg_amd_test_attention(int global, uint16_t const* qkv, float const* qkv_bias, float const* rel_h,
                                        float const* rel_w, int batch, int heads, int hd, uint16_t* out);
+/* The product's mask decoder (SamModel::decode, one call for all `count` prompts, on a lane of env's first replica) on
+ * given embeddings: emb [n_emb][4096][256] fp32 (token-major, as dlimg_amd_get_embedding returns them), prompt i decodes
+ * embedding emb_index[i] with the packed prompt coords [i][2][2] (resized-image pixels) and labels [i][2] (1 / -1: a
+ * point, 2 / 3: a box).  out_logits [count][4][256][256], out_iou [count][4].  count < 1, an index out of range and null
+ * pointers are errors. */
+DLIMG_API int dlimg_amd_test_decode(dlimg_Environment env, int n_emb, float const* emb, int count, int const* emb_index,
+                                    float const* coords, float const* labels, float* out_logits, float* out_iou);
 /* K17: the stb_image_resize-equivalent longest-side resampler (default filter, sRGB, clamp):
  * pixels [height][stride] -> out_pixels [out_h][out_w * bytes_per_pixel] packed. */
 DLIMG_API int dlimg_amd_test_resize(uint8_t const* pixels, int width, int height, int stride, int channels, int out_w,
