@@ -363,6 +363,9 @@ class Segmentation:
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None) -> list:
+        """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
+        -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
+        point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0)."""
         n = len(segs)
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
@@ -656,8 +659,9 @@ class ext:
 
     @classmethod
     def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0) -> list:
-        """Device-output form of Segmentation.compute_mask_batch: masks land tightly packed at `dev_out` (a device pointer
-        on HIP device `root_device`), wherever their embeddings live; returns the byte offset of every mask."""
+        """Device-output form of Segmentation.compute_mask_batch (points, regions or both, as there): masks land tightly
+        packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their embeddings live; returns the byte
+        offset of every mask."""
         n = len(segs)
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         p = r = None

@@ -1,11 +1,12 @@
 // Token-side kernels of the SAM prompt encoder / mask decoder (everything that is NOT a big GEMM).
 // In the reference all of this runs inside the decoder ONNX graph behind Session::operator()
 // (/root/reference/src/segmentation.cpp:154-158); the published definition is SAM's PromptEncoder,
-// TwoWayTransformer and MaskDecoder.  The token side is 7 tokens per prompt: latency-bound fp32
+// TwoWayTransformer and MaskDecoder.  The token side is 7 or 8 tokens per prompt: latency-bound fp32
 // VALU work, kept in fp32 end to end.
 #include "device_common.hpp"
 #include "kernels.hpp"
 
+#include <cstring>
 #include <mutex>
 #include <type_traits>
 
@@ -14,37 +15,44 @@ namespace {
 
 #include "gemm_f16_tile.inc"
 
-constexpr int TOK = 7;        // iou token + 4 mask tokens + 2 prompt tokens
+// Tokens per prompt: iou token + 4 mask tokens + the prompt's points -- 7 (a point and its pad token, or the two corners of
+// a box) or 8 (a point and a box).  It is the template parameter TOK of everything below that depends on it: the launchers
+// pick the instantiation, the 7-token code is what it was when TOK was a constant of this file, and a launch never mixes
+// counts.
+constexpr int OUT_TOK = 5;    // iou token + 4 mask tokens: the rows the heads read
 constexpr int DIM = 256;
 constexpr int INNER = 128;    // cross-attention width (downsample 2)
 constexpr int HEADS = 8;
 constexpr int NTOK_IMG = 4096;
 
 // ---------------------------------------------------------------------------------------------
-// Prompt encoder: SamOnnxModel._embed_points applied to the two packed points
-// (segmentation.cpp:135-152 packs them; labels 1/-1 for a point, 2/3 for a box).
-// Column c of the 7 token rows of prompt p: iou token, 4 mask tokens, the 2 prompt points.
-DLIMG_DEVICE void prompt_token_column(const k::DecoderPrompts& pr, int p, int c, const float* __restrict__ gauss,
+// Prompt encoder: SamOnnxModel._embed_points applied to the TOK - 5 packed points
+// (segmentation.cpp:135-152 packs two; labels 1/-1 for a point, 2/3 for a box; SAM's PromptEncoder.forward puts the point
+// in front of the box corners and sends no pad token with a box: labels 1, 2, 3).
+// Column c of the TOK token rows of prompt p: iou token, 4 mask tokens, the prompt points.
+template <int TOK, typename Prompts>
+DLIMG_DEVICE void prompt_token_column(const Prompts& pr, int p, int c, const float* __restrict__ gauss,
                                       const float* __restrict__ point_embed, const float* __restrict__ not_a_point,
                                       const float* __restrict__ iou_token, const float* __restrict__ mask_tokens,
-                                      float (&out)[7]) {
+                                      float (&out)[TOK]) {
+    constexpr int NPTS = TOK - OUT_TOK;
     out[0] = iou_token[c];
 #pragma unroll
     for (int m = 0; m < 4; ++m) out[1 + m] = mask_tokens[m * DIM + c];
     const int kf = c & 127;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float x = (pr.coords[(p * 2 + i) * 2 + 0] + 0.5f) / 1024.0f;
-        const float y = (pr.coords[(p * 2 + i) * 2 + 1] + 0.5f) / 1024.0f;
+    for (int i = 0; i < NPTS; ++i) {
+        const float x = (pr.coords[(p * NPTS + i) * 2 + 0] + 0.5f) / 1024.0f;
+        const float y = (pr.coords[(p * NPTS + i) * 2 + 1] + 0.5f) / 1024.0f;
         float v = __fadd_rn(__fmul_rn(2.0f * x - 1.0f, gauss[kf]), __fmul_rn(2.0f * y - 1.0f, gauss[128 + kf]));
         v = 6.283185307179586f * v;
         float e = c < 128 ? sinf(v) : cosf(v);
-        const float lab = pr.labels[p * 2 + i];
+        const float lab = pr.labels[p * NPTS + i];
         if (lab == -1.0f) e = not_a_point[c];
 #pragma unroll
         for (int k4 = 0; k4 < 4; ++k4)
             if (lab == (float)k4) e += point_embed[k4 * DIM + c];
-        out[5 + i] = e;
+        out[OUT_TOK + i] = e;
     }
 }
 
@@ -62,10 +70,12 @@ DLIMG_DEVICE void prompt_token_column(const k::DecoderPrompts& pr, int p, int c,
 // at one prompt against 9.4 us for this one, 27 against 35 us at five prompts -- scalar weight loads and LDS reads
 // share one counter and serialise.  Not kept.)
 constexpr int RCHUNK = 8;               // rows a wave accumulates at a time in the token linears
-constexpr int TL_MAX_ROWS = 112;              // 16 prompts x 7 tokens per launch
+constexpr int TL_MAX_ROWS = k::kDecoderMaxRows;   // 16 prompts x 7 tokens, or 14 prompts x 8 tokens, per launch
 constexpr int TL_MAX_OPS = 5;
 constexpr int TL_PROMPT_SLICE = 2;           // prompts per workgroup of the fused attention-output kernels
-constexpr int TL_ROW_SLICE = 14;            // rows per workgroup of token_linears_kernel (two prompts)
+constexpr int TL_MAX_ROW_SLICE = 16;         // lane L of a wave finishes row L of a slice
+// rows per workgroup of token_linears_kernel (two prompts)
+template <int TOK> constexpr int TL_ROW_SLICE = TL_PROMPT_SLICE * TOK;
 
 struct LinJob { k::TokenLinear op[TL_MAX_OPS]; int count; int rows; };
 
@@ -147,7 +157,7 @@ DLIMG_DEVICE void stage_token_rows(const k::TokenRows& m, int row0, int rows, fl
 // residual entry with its LayerNorm scale / shift.  [Before r03 lane 0 fetched bias and residual after the sums: one more
 // round trip to L2 per call, which a workgroup that runs several columns per wave pays several times over.]
 struct TokenColumn { float4_t w; float bias, rx, radd, rlw, rlb; };
-static_assert(TL_ROW_SLICE <= 16, "lane L of a wave finishes row L of the slice");
+static_assert(TL_ROW_SLICE<7> <= TL_MAX_ROW_SLICE && TL_ROW_SLICE<8> <= TL_MAX_ROW_SLICE, "lane L of a wave finishes row L of the slice");
 DLIMG_DEVICE TokenColumn token_column_prefetch(const k::TokenLinear& op, int first_col, int row0, int row1) {
     const int lane = lane_id();
     const int n = first_col + (threadIdx.x >> 6);
@@ -163,7 +173,7 @@ DLIMG_DEVICE TokenColumn token_column_prefetch(const k::TokenLinear& op, int fir
     }
     return c;
 }
-// NR = rows of the slice, 7 or 14 (whole prompts).
+// NR = rows of the slice: one or two whole prompts of TOK rows.
 // The accumulate loop keeps the round-2 shape -- a run-time row bound, one guarded step per row, chunks of 8 -- and the whole
 // library is built with -fno-slp-vectorize (dlimgedit_amd/build.py).  With the row count a compile-time constant and the
 // seven rows' loads in straight-line code, the SLP vectoriser paired the rows (2,1), (4,3), (6,5) into chains of
@@ -177,10 +187,10 @@ DLIMG_DEVICE TokenColumn token_column_prefetch(const k::TokenLinear& op, int fir
 // code; whether it is a gap in the compiler's hazard table for packed fp32 on gfx950 or an erratum is not known.  The
 // tuning build keeps the failing form (-DDLIMG_STRAIGHT_ROWS, build it WITHOUT -fno-slp-vectorize to see it fail);
 // tests/test_gpu_concurrency.py keeps the stress in the suite.
-template <int NR>
+template <int TOK, int NR>
 DLIMG_DEVICE void token_linear_columns(const k::TokenLinear& op, int first_col, const float* lds_in, const float2_t* stat_in,
                                        const float2_t* stat_res, const TokenColumn& col, int row0) {
-    static_assert(NR % TOK == 0 && NR <= 16, "slices are whole prompts");
+    static_assert(NR % TOK == 0 && NR <= TL_MAX_ROW_SLICE, "slices are whole prompts");
     const int lane = lane_id();
     const int n = first_col + (threadIdx.x >> 6);
     if (n >= op.N) return;
@@ -253,25 +263,26 @@ DLIMG_DEVICE void token_linear_columns(const k::TokenLinear& op, int first_col, 
 }
 // the body once for each slice size
 #define DLIMG_FOR_SLICE_ROWS(count, ...)                                   \
-    if ((count) == TL_ROW_SLICE) { constexpr int NR = TL_ROW_SLICE; __VA_ARGS__ } \
+    if ((count) == TL_ROW_SLICE<TOK>) { constexpr int NR = TL_ROW_SLICE<TOK>; __VA_ARGS__ } \
     else { constexpr int NR = TOK; __VA_ARGS__ }
 
 #if defined(DLIMG_TUNING) && defined(DLIMG_LOW_OCCUPANCY)
 __attribute__((amdgpu_waves_per_eu(1, 4)))
 #endif
+template <int TOK>
 __global__ __launch_bounds__(256) void token_linears_kernel(LinJob job) {
     __shared__ float2_t stat_in[TL_MAX_ROWS], stat_res[TL_MAX_ROWS];
     int o = 0, first = blockIdx.x * 4;
     while (o + 1 < job.count && first >= job.op[o].N) { first -= job.op[o].N; ++o; }      // N is a multiple of 4
     const k::TokenLinear& op = job.op[o];
     // rows are dealt to blockIdx.y in slices of TL_ROW_SLICE: more prompts are more workgroups, not longer ones
-    const int row0 = blockIdx.y * TL_ROW_SLICE, row1 = min(job.rows, row0 + TL_ROW_SLICE);
+    const int row0 = blockIdx.y * TL_ROW_SLICE<TOK>, row1 = min(job.rows, row0 + TL_ROW_SLICE<TOK>);
     const TokenColumn w_first = token_column_prefetch(op, first, row0, row1);
     const bool ln_in = op.in.ln_w && op.K == DIM, ln_res = op.resid.x && op.resid.ln_w;
     if (ln_in) token_row_stats(op.in, row1, stat_in, row0);
     if (ln_res) token_row_stats(op.resid, row1, stat_res, row0);
     if (ln_in || ln_res) __syncthreads();
-    DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<NR>(op, first, nullptr, stat_in, stat_res, w_first, row0);)
+    DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<TOK, NR>(op, first, nullptr, stat_in, stat_res, w_first, row0);)
 }
 
 // Deep layers (the token MLP's second linear, K = 2048): one column per wave like token_linears_kernel, but the input
@@ -279,13 +290,15 @@ __global__ __launch_bounds__(256) void token_linears_kernel(LinJob job) {
 // load sits inside the accumulation loop (that loop, 8 dependent trips to L2, made this launch 20.5 us for one prompt).
 // Same order of additions as token_linear_columns: results are bit-identical.
 constexpr int TLD_MAX_K = 2048;
+template <int TOK>
 __global__ __launch_bounds__(256) void token_linear_deep_kernel(k::TokenLinear op, int rows) {
+    constexpr int row_slice = TL_ROW_SLICE<TOK>;
     extern __shared__ __attribute__((aligned(16))) float lds[];        // [row slice][K]
     __shared__ float2_t stat_res[TL_MAX_ROWS];
     const int lane = lane_id();
     const int n = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int K4 = op.K >> 2, trips = K4 >> 6;
-    const int row0 = blockIdx.y * TL_ROW_SLICE, row1 = min(rows, row0 + TL_ROW_SLICE);
+    const int row0 = blockIdx.y * row_slice, row1 = min(rows, row0 + row_slice);
     float4_t w[TLD_MAX_K / 256];
 #pragma unroll
     for (int t = 0; t < TLD_MAX_K / 256; ++t)
@@ -334,13 +347,14 @@ __global__ __launch_bounds__(256) void token_linear_deep_kernel(k::TokenLinear o
 //   merge  : the consumers (token_merge_linear_kernel, output_heads_kernel) fold the 8 group partials in a fixed order
 //            and apply the output projection themselves
 // The query projection (LayerNorm + positional part on the fly, 256 -> 128) can ride in this launch: a workgroup needs
-// the 16 columns of its head for 7 tokens only and computes them with the code (and bits) of token_linears_kernel.
+// the 16 columns of its head for the prompt's tokens only and computes them with the code (and bits) of token_linears_kernel.
 constexpr int T2I_GROUPS = 8;                                  // key groups per head
 constexpr int T2I_THREADS = 256;
 constexpr int T2I_KEYS = NTOK_IMG / T2I_GROUPS / T2I_THREADS;  // keys per thread
 constexpr int T2I_WAVES = T2I_THREADS / 64;
 constexpr int T2I_PARTS = T2I_GROUPS;                          // partial triples per (prompt, head, query)
 
+template <int TOK>
 __global__ __launch_bounds__(T2I_THREADS) void token_to_image_partial_kernel(const float* __restrict__ q, k::TokenLinear qp,
                                                                              const half_t* __restrict__ K, int ldk,
                                                                              const half_t* __restrict__ V, int ldv,
@@ -373,7 +387,7 @@ __global__ __launch_bounds__(T2I_THREADS) void token_to_image_partial_kernel(con
         stage_token_rows<TOK>(qp.in, row0, TOK, xrows, qstat);
         qp.Y = qrows - (size_t)row0 * INNER;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) token_linear_columns<TOK>(qp, h * 16 + 4 * i, xrows, nullptr, nullptr, wf[i], row0);
+        for (int i = 0; i < 4; ++i) token_linear_columns<TOK, TOK>(qp, h * 16 + 4 * i, xrows, nullptr, nullptr, wf[i], row0);
         __syncthreads();
         if (tid < TOK * 16) sq[tid] = qrows[(tid / 16) * INNER + h * 16 + (tid & 15)] * 0.25f;               // 16^-0.5
     } else if (tid < TOK * 16) {
@@ -433,9 +447,9 @@ __global__ __launch_bounds__(T2I_THREADS) void token_to_image_partial_kernel(con
 }
 
 
-// Self-attention among the 7 tokens of every prompt (8 heads x 32), recomputed by every workgroup into LDS, followed by
+// Self-attention among the TOK tokens of every prompt (8 heads x 32), recomputed by every workgroup into LDS, followed by
 // the output projection (one column per wave) with bias and residual: one launch instead of two.
-// Thread c owns channel c of q, k and v of a prompt (21 registers); a head is 32 adjacent lanes, so a score is one product
+// Thread c owns channel c of q, k and v of a prompt (3 TOK registers); a head is 32 adjacent lanes, so a score is one product
 // per lane summed over the half wave (DPP inside the rows of 16, one lane exchange across them).  [The first version had
 // every lane walk all 32 channels of its head out of LDS: 3136 LDS reads per thread and prompt, 12-14 us per launch.]
 DLIMG_DEVICE float sum_over_32_lanes(float v) {
@@ -445,6 +459,7 @@ DLIMG_DEVICE float sum_over_32_lanes(float v) {
     v += dpp_move<0x140>(v);
     return v + __shfl_xor(v, 16, 64);
 }
+template <int TOK>
 DLIMG_DEVICE void token_self_attn_out_body(const float* __restrict__ q, const float* __restrict__ kx, const float* __restrict__ v,
                                            const k::TokenLinear& op, int P, const int block_x, const int block_y, float* lds) {
     // prompts are dealt to block_y in pairs (rows row0 .. row1 of the token matrix; LDS rows are local)
@@ -484,12 +499,13 @@ DLIMG_DEVICE void token_self_attn_out_body(const float* __restrict__ q, const fl
     }
     if (op.resid.x && op.resid.ln_w) token_row_stats(op.resid, row1, stat_res, row0);
     __syncthreads();
-    DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<NR>(op, block_x * 4, att, nullptr, stat_res, w_first, row0);)
+    DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<TOK, NR>(op, block_x * 4, att, nullptr, stat_res, w_first, row0);)
 }
+template <int TOK>
 __global__ __launch_bounds__(256) void token_self_attn_out_kernel(const float* __restrict__ q, const float* __restrict__ kx,
                                                                   const float* __restrict__ v, k::TokenLinear op, int P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    token_self_attn_out_body(q, kx, v, op, P, blockIdx.x, blockIdx.y, lds);
+    token_self_attn_out_body<TOK>(q, kx, v, op, P, blockIdx.x, blockIdx.y, lds);
 }
 
 // The same launch with the layer's image-side projection riding along: [K | Q | V] = keys . W^T (decoder_image side, an MFMA
@@ -500,9 +516,10 @@ __global__ __launch_bounds__(256) void token_self_attn_out_kernel(const float* _
 // same bits -- in front of them the self-attention's workgroups.  Both parts use 256 threads.
 constexpr int SAG_BM = 64, SAG_BN = 64;
 constexpr size_t SAG_GEMM_LDS = (size_t)2 * (SAG_BM + SAG_BN) * 64 * 2 + aux_bytes(SAG_BM, SAG_BN);
-constexpr size_t SAG_TOKEN_LDS = (size_t)TL_PROMPT_SLICE * TOK * (DIM * 4 + 8);
-constexpr size_t SAG_LDS = SAG_GEMM_LDS > SAG_TOKEN_LDS ? SAG_GEMM_LDS : SAG_TOKEN_LDS;
-static_assert(SAG_LDS <= 48 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
+template <int TOK> constexpr size_t SA_TOKEN_LDS = (size_t)TL_PROMPT_SLICE * TOK * (DIM * 4 + 8);
+template <int TOK> constexpr size_t SAG_LDS = SAG_GEMM_LDS > SA_TOKEN_LDS<TOK> ? SAG_GEMM_LDS : SA_TOKEN_LDS<TOK>;
+static_assert(SAG_LDS<7> <= 48 * 1024 && SAG_LDS<8> <= 48 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
+template <int TOK>
 __global__ __launch_bounds__(256, 4) void self_attn_out_and_gemm_kernel(k::GemmArgs g, int gemm_tiles, const float* __restrict__ q,
                                                                         const float* __restrict__ kx, const float* __restrict__ v,
                                                                         k::TokenLinear op, int P, int token_blocks_x) {
@@ -511,7 +528,7 @@ __global__ __launch_bounds__(256, 4) void self_attn_out_and_gemm_kernel(k::GemmA
     // dispatched in index order -- behind them the long chain of the token part would start when the GEMM is all but done
     const int token_blocks = (int)gridDim.x - gemm_tiles;        // a multiple of 8: the tiles keep their XCDs
     if ((int)blockIdx.x < token_blocks) {
-        token_self_attn_out_body(q, kx, v, op, P, blockIdx.x % token_blocks_x, blockIdx.x / token_blocks_x, reinterpret_cast<float*>(smem));
+        token_self_attn_out_body<TOK>(q, kx, v, op, P, blockIdx.x % token_blocks_x, blockIdx.x / token_blocks_x, reinterpret_cast<float*>(smem));
         return;
     }
     gemm_f16_tile<SAG_BM, SAG_BN, 2, 2, 64, 2, 4, k::ACT_NONE, EPI_PLAIN>(g, xcd_remap((int)blockIdx.x - token_blocks, gemm_tiles), smem);
@@ -521,12 +538,12 @@ __global__ __launch_bounds__(256, 4) void self_attn_out_and_gemm_kernel(k::GemmA
 //   merge_partials         folds the 8 key-group partials of (prompt, head, token) in a fixed order -> att [rows][128] in LDS
 //   output projection      thread c = output column c: y[r][c] = att[r] . Wo[c] + b[c] + resid[r][c] with Wo TRANSPOSED
 //                          ([128][256], prepared at load) so that a wave reads 256 contiguous bytes per k
-// Every workgroup of the consumer repeats both for the rows it needs (7 x 256 x 128 FMAs at most per prompt, the 128 KB of
+// Every workgroup of the consumer repeats both for the rows it needs (TOK x 256 x 128 FMAs at most per prompt, the 128 KB of
 // Wo come out of L2), so the result is the same bits wherever it is computed and nothing has to be exchanged.
 // NR rows starting at token t0 of prompt p0 (wrapping into the next prompts); blockDim.x >= 128.  Thread = (head, element)
 // for the rows r = (tid / 128) + i * (blockDim.x / 128); the 24 values of up to 4 rows are requested before the first is
 // used (one round trip to L2 for 4 rows, not four).
-template <int NR>
+template <int TOK, int NR>
 DLIMG_DEVICE void merge_partials(const float* __restrict__ part, int p0, int t0, float* att /*LDS [NR][128]*/) {
     const int e = threadIdx.x & 15, h = (threadIdx.x >> 4) & (HEADS - 1);
     const int rstep = blockDim.x >> 7, rfirst = threadIdx.x >> 7;
@@ -563,7 +580,7 @@ DLIMG_DEVICE void merge_partials(const float* __restrict__ part, int p0, int t0,
     }
 }
 // one row (the heads kernel): threads 0..127
-DLIMG_DEVICE void merge_partials_one(const float* __restrict__ part, int p, int t, float* att /*LDS [128]*/) {
+DLIMG_DEVICE void merge_partials_one(const float* __restrict__ part, int p, int t, int TOK, float* att /*LDS [128]*/) {
     const int e = threadIdx.x & 15, h = (threadIdx.x >> 4) & (HEADS - 1);
     const float* src = part + ((((size_t)p * HEADS + h) * TOK + t) * T2I_PARTS) * 18;
     float M[T2I_PARTS], L[T2I_PARTS], O[T2I_PARTS];
@@ -603,15 +620,16 @@ DLIMG_DEVICE void lds_row_stats(const float* y, int rows, float eps, float2_t* s
 // from five) (every workgroup pays the fold, the 128 KB of Wo and the projection before its columns: at five prompts 640
 // workgroups of 16 columns took 53 us, two and a half rounds on 256 CUs).  The arithmetic of a column does not depend on COLS.  [Kept small on purpose: code that runs once is fetched cold, and a 43 KB body --
 // 32 columns, two prompts, everything unrolled -- took 24 us where this one takes half.]
-constexpr size_t TML_LDS = (size_t)(INNER * DIM + TL_ROW_SLICE * INNER + TL_ROW_SLICE * DIM) * 4 + 2 * TL_ROW_SLICE * 8;
-template <int NR, int COLS>
+template <int TOK>
+constexpr size_t TML_LDS = (size_t)(INNER * DIM + TL_ROW_SLICE<TOK> * INNER + TL_ROW_SLICE<TOK> * DIM) * 4 + 2 * TL_ROW_SLICE<TOK> * 8;
+template <int TOK, int NR, int COLS>
 DLIMG_DEVICE void token_merge_linear_body(const float* __restrict__ part, const k::TokenLinear& out,
                                           const float* __restrict__ out_wt, const k::TokenLinear& next, int p0, float* lds) {
     float* wt = lds;                                     // [128][256]: the whole transposed output projection (128 KB)
     float* att = wt + INNER * DIM;                       // [rows][128]
-    float* y = att + TL_ROW_SLICE * INNER;               // [rows][256]
-    float2_t* stat_res = reinterpret_cast<float2_t*>(y + TL_ROW_SLICE * DIM);
-    float2_t* stat_in = stat_res + TL_ROW_SLICE;
+    float* y = att + TL_ROW_SLICE<TOK> * INNER;          // [rows][256]
+    float2_t* stat_res = reinterpret_cast<float2_t*>(y + TL_ROW_SLICE<TOK> * DIM);
+    float2_t* stat_in = stat_res + TL_ROW_SLICE<TOK>;
     const int row0 = p0 * TOK, row1 = row0 + NR;
     const int first = blockIdx.x * COLS;
     const int c = threadIdx.x, lane = lane_id(), wave = c >> 6;
@@ -629,7 +647,7 @@ DLIMG_DEVICE void token_merge_linear_body(const float* __restrict__ part, const 
     float nadd[NR];
 #pragma unroll
     for (int r = 0; r < NR; ++r) nadd[r] = next.in.add ? next.in.add[(size_t)(row0 + r) * DIM + c] : 0.f;
-    merge_partials<NR>(part, p0, 0, att);
+    merge_partials<TOK, NR>(part, p0, 0, att);
     if (res_ln) token_row_stats(out.resid, row1, stat_res - row0, row0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -674,15 +692,15 @@ DLIMG_DEVICE void token_merge_linear_body(const float* __restrict__ part, const 
 #pragma unroll 1
     for (int i = 0; i < COLS / 4; ++i) {
         const TokenColumn following = token_column_prefetch(next, first + 4 * min(i + 1, COLS / 4 - 1), row0, row1);
-        token_linear_columns<NR>(next, first + 4 * i, y, nullptr, nullptr, col, row0);
+        token_linear_columns<TOK, NR>(next, first + 4 * i, y, nullptr, nullptr, col, row0);
         col = following;
     }
 }
-template <int COLS>
+template <int TOK, int COLS>
 __global__ __launch_bounds__(256) void token_merge_linear_kernel(const float* __restrict__ part, k::TokenLinear out,
                                                                  const float* __restrict__ out_wt, k::TokenLinear next, int P) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    token_merge_linear_body<TOK, COLS>(part, out, out_wt, next, blockIdx.y, lds);
+    token_merge_linear_body<TOK, TOK, COLS>(part, out, out_wt, next, blockIdx.y, lds);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -719,6 +737,7 @@ DLIMG_DEVICE void head_layer(const float* x /*LDS*/, const float* __restrict__ w
 
 // The workgroup first finishes the final token-to-image attention for ITS token (merge of the partials, output projection,
 // residual: see merge_partials) and applies norm_final_attn to it.
+template <int TOK /*rows per prompt*/>
 __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float* __restrict__ part, k::TokenLinear out,
                                                                     const float* __restrict__ out_wt, k::TokenRows norm,
                                                                     k::HeadWeights hw, float* __restrict__ hyper,
@@ -740,7 +759,7 @@ __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float*
         if (out.resid.ln_w) { rw = out.resid.ln_w[c]; rb = out.resid.ln_b[c]; }
     }
     const float ob = (out.b && kq == 0) ? out.b[c] : 0.f;
-    if (threadIdx.x < INNER) merge_partials_one(part, p, tok, att);
+    if (threadIdx.x < INNER) merge_partials_one(part, p, tok, TOK, att);
     if (out.resid.x && out.resid.ln_w && (threadIdx.x >> 6) == 15) {       // statistics of the residual row: the last wave
         const int lane = lane_id();
         const float4_t v = reinterpret_cast<const float4_t*>(out.resid.x + (size_t)row * DIM)[lane];
@@ -785,20 +804,31 @@ __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float*
 // rows, which they rebuild in LDS instead of waiting for them, and the rest initialise the keys.  The three have nothing
 // to do with each other except that all are the first step of their chain -- and every launch of the decoder costs its
 // 5-9 us of dependent latency.  The prompts travel as kernel arguments: no host-to-device copy in front of a decode.
+// They travel at the size of the launch's own token count (k::DecoderPrompts holds the largest): a two-point launch carries
+// the 512 bytes it always did.
+template <int TOK>
+struct StartPrompts {
+    static constexpr int NPTS = TOK - OUT_TOK;
+    float coords[k::kDecoderMaxPrompts * NPTS * 2];
+    float labels[k::kDecoderMaxPrompts * NPTS];
+    const float* emb[k::kDecoderMaxPrompts];
+};
+template <int TOK>
 struct DecoderStart {
-    k::DecoderPrompts prompts;
+    StartPrompts<TOK> prompts;
     const float* gauss; const float* point_embed; const float* not_a_point; const float* iou_token; const float* mask_tokens;
     float* tokens;
     LinJob first;
     int lin_blocks, lin_cols;
     const float* no_mask; float* keys; half_t* keys_h; size_t n4_per_prompt; int P;
 };
-__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart a) {
-    __shared__ __attribute__((aligned(16))) float rows[TL_ROW_SLICE * DIM];
+template <int TOK>
+__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart<TOK> a) {
+    __shared__ __attribute__((aligned(16))) float rows[TL_ROW_SLICE<TOK> * DIM];
     const int c = threadIdx.x;
     if ((int)blockIdx.x < a.P) {
         float v[TOK];
-        prompt_token_column(a.prompts, blockIdx.x, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
+        prompt_token_column<TOK>(a.prompts, blockIdx.x, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
 #pragma unroll
         for (int t = 0; t < TOK; ++t) a.tokens[((size_t)blockIdx.x * TOK + t) * DIM + c] = v[t];
         return;
@@ -808,16 +838,16 @@ __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart a) {
         int o = 0, first = (bid % a.lin_cols) * 4;
         while (o + 1 < a.first.count && first >= a.first.op[o].N) { first -= a.first.op[o].N; ++o; }
         const k::TokenLinear& op = a.first.op[o];
-        const int row0 = (bid / a.lin_cols) * TL_ROW_SLICE, row1 = min(a.first.rows, row0 + TL_ROW_SLICE);
+        const int row0 = (bid / a.lin_cols) * TL_ROW_SLICE<TOK>, row1 = min(a.first.rows, row0 + TL_ROW_SLICE<TOK>);
         const TokenColumn w_first = token_column_prefetch(op, first, row0, row1);
         for (int p = row0 / TOK; p * TOK < row1; ++p) {
             float v[TOK];
-            prompt_token_column(a.prompts, p, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
+            prompt_token_column<TOK>(a.prompts, p, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
 #pragma unroll
             for (int t = 0; t < TOK; ++t) rows[(p * TOK + t - row0) * DIM + c] = v[t];
         }
         __syncthreads();
-        DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<NR>(op, first, rows, nullptr, nullptr, w_first, row0);)
+        DLIMG_FOR_SLICE_ROWS(row1 - row0, token_linear_columns<TOK, NR>(op, first, rows, nullptr, nullptr, w_first, row0);)
         return;
     }
     const float* __restrict__ no_mask = a.no_mask;
@@ -838,39 +868,51 @@ __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart a) {
 
 }  // namespace
 
+// the body once for each supported token count (k::decoder_tokens_supported)
+#define DLIMG_FOR_TOKENS(T, who, ...)                                        \
+    if ((T) == 7) { constexpr int TOK = 7; __VA_ARGS__ }                     \
+    else if ((T) == 8) { constexpr int TOK = 8; __VA_ARGS__ }                \
+    else { throw_error(who ": 7 or 8 tokens per prompt"); }
+
 namespace k {
 
 void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, hipStream_t s) {
+                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
     if (P <= 0) return;
-    if (P > kDecoderMaxPrompts || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
+    if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 or 8 tokens per prompt");
+    if (P > decoder_max_prompts(T) || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
     const size_t n4 = (size_t)NTOK_IMG * DIM / 4;
     const size_t total = n4 * P;
     const int key_blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    DecoderStart a{};
-    a.prompts = prompts;
-    a.gauss = gauss; a.point_embed = point_embed; a.not_a_point = not_a_point; a.iou_token = iou_token; a.mask_tokens = mask_tokens;
-    a.tokens = tokens;
-    a.first.count = n_first;
-    a.first.rows = P * TOK;
     int cols = 0;
     for (int i = 0; i < n_first; ++i) {
         if (first[i].K != DIM || first[i].N <= 0 || first[i].N % 4 || first[i].in.ln_w || first[i].in.add || first[i].resid.x)
             throw_error("decoder_start: the first linears take the plain 256-wide token rows");
-        a.first.op[i] = first[i];
         cols += first[i].N / 4;
     }
-    a.lin_cols = cols > 0 ? cols : 1;
-    a.lin_blocks = cols * ((P * TOK + TL_ROW_SLICE - 1) / TL_ROW_SLICE);
-    a.no_mask = no_mask; a.keys = keys; a.keys_h = keys_h; a.n4_per_prompt = n4; a.P = P;
-    hipLaunchKernelGGL(decoder_start_kernel, dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
+    DLIMG_FOR_TOKENS(T, "decoder_start",
+        DecoderStart<TOK> a{};
+        constexpr int NPTS = StartPrompts<TOK>::NPTS;
+        std::memcpy(a.prompts.coords, prompts.coords, (size_t)P * NPTS * 2 * sizeof(float));
+        std::memcpy(a.prompts.labels, prompts.labels, (size_t)P * NPTS * sizeof(float));
+        for (int i = 0; i < P; ++i) a.prompts.emb[i] = prompts.emb[i];
+        a.gauss = gauss; a.point_embed = point_embed; a.not_a_point = not_a_point; a.iou_token = iou_token; a.mask_tokens = mask_tokens;
+        a.tokens = tokens;
+        a.first.count = n_first;
+        a.first.rows = P * T;
+        for (int i = 0; i < n_first; ++i) a.first.op[i] = first[i];
+        a.lin_cols = cols > 0 ? cols : 1;
+        a.lin_blocks = cols * ((P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE);
+        a.no_mask = no_mask; a.keys = keys; a.keys_h = keys_h; a.n4_per_prompt = n4; a.P = P;
+        hipLaunchKernelGGL(decoder_start_kernel<TOK>, dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);)
 }
 
-size_t token_to_image_scratch_floats(int P) { return (size_t)P * HEADS * TOK * T2I_PARTS * 18; }
+size_t token_to_image_scratch_floats(int P, int T) { return (size_t)P * HEADS * T * T2I_PARTS * 18; }
 
-void token_linears(const TokenLinear* ops, int count, int rows, hipStream_t s) {
+void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t s) {
     if (count <= 0 || rows <= 0) return;
+    if (!decoder_tokens_supported(T) || rows % T) throw_error("token_linears: whole prompts of 7 or 8 token rows");
     if (count > TL_MAX_OPS || rows > TL_MAX_ROWS) throw_error("token_linears: too many layers or rows for one launch");
     LinJob job;
     job.count = count;
@@ -884,31 +926,35 @@ void token_linears(const TokenLinear* ops, int count, int rows, hipStream_t s) {
         job.op[i] = ops[i];
         blocks += ops[i].N / 4;
     }
-    const int slices = (rows + TL_ROW_SLICE - 1) / TL_ROW_SLICE;
+    const int row_slice = TL_PROMPT_SLICE * T;
+    const int slices = (rows + row_slice - 1) / row_slice;
     if (count == 1 && ops[0].K > DIM && ops[0].K % 256 == 0 && ops[0].K <= TLD_MAX_K && !ops[0].in.ln_w && !ops[0].in.add) {
-        static k::LdsOptIn opt_in;
-        opt_in.ensure((const void*)token_linear_deep_kernel, (size_t)TL_ROW_SLICE * TLD_MAX_K * 4,
-                      "token_linears: the device refuses the kernel's LDS size");
-        const size_t lds = (size_t)std::min(rows, TL_ROW_SLICE) * ops[0].K * 4;
-        hipLaunchKernelGGL(token_linear_deep_kernel, dim3(ops[0].N / 4, slices), dim3(256), lds, s, ops[0], rows);
+        const size_t lds = (size_t)std::min(rows, row_slice) * ops[0].K * 4;
+        DLIMG_FOR_TOKENS(T, "token_linears",
+            static k::LdsOptIn opt_in;          // one per token count
+            opt_in.ensure((const void*)token_linear_deep_kernel<TOK>, (size_t)TL_ROW_SLICE<TOK> * TLD_MAX_K * 4,
+                          "token_linears: the device refuses the kernel's LDS size");
+            hipLaunchKernelGGL(token_linear_deep_kernel<TOK>, dim3(ops[0].N / 4, slices), dim3(256), lds, s, ops[0], rows);)
         return;
     }
-    hipLaunchKernelGGL(token_linears_kernel, dim3(blocks, slices), dim3(256), 0, s, job);
+    DLIMG_FOR_TOKENS(T, "token_linears", hipLaunchKernelGGL(token_linears_kernel<TOK>, dim3(blocks, slices), dim3(256), 0, s, job);)
 }
 
-void token_self_attention_out(const float* q, const float* kx, const float* v, const TokenLinear& out, int P, hipStream_t s) {
+void token_self_attention_out(const float* q, const float* kx, const float* v, const TokenLinear& out, int P, int T, hipStream_t s) {
     if (P <= 0) return;
-    if (P * TOK > TL_MAX_ROWS || out.K != DIM || out.N % 4) throw_error("token_self_attention_out: unsupported shape");
-    const size_t lds = (size_t)TL_PROMPT_SLICE * TOK * (DIM * 4 + 8);
-    static_assert((size_t)TL_PROMPT_SLICE * TOK * (DIM * 4 + 8) <= 64 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
-    hipLaunchKernelGGL(token_self_attn_out_kernel, dim3(out.N / 4, (P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE), dim3(256), lds, s, q, kx,
-                       v, out, P);
+    if (!decoder_tokens_supported(T) || P * T > TL_MAX_ROWS || out.K != DIM || out.N % 4)
+        throw_error("token_self_attention_out: unsupported shape");
+    static_assert(SA_TOKEN_LDS<7> <= 64 * 1024 && SA_TOKEN_LDS<8> <= 64 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
+    DLIMG_FOR_TOKENS(T, "token_self_attention_out",
+        hipLaunchKernelGGL(token_self_attn_out_kernel<TOK>, dim3(out.N / 4, (P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE), dim3(256),
+                           SA_TOKEN_LDS<TOK>, s, q, kx, v, out, P);)
 }
 
-bool token_self_attention_out_with_gemm(const float* q, const float* kx, const float* v, const TokenLinear& out, int P,
+bool token_self_attention_out_with_gemm(const float* q, const float* kx, const float* v, const TokenLinear& out, int P, int T,
                                         const GemmArgs& g, hipStream_t s) {
     if (P <= 0) return true;
-    if (P * TOK > TL_MAX_ROWS || out.K != DIM || out.N % 4) throw_error("token_self_attention_out: unsupported shape");
+    if (!decoder_tokens_supported(T) || P * T > TL_MAX_ROWS || out.K != DIM || out.N % 4)
+        throw_error("token_self_attention_out: unsupported shape");
     // what the 64 x 64 plain tile computes, and nothing else: otherwise the caller launches the two on their own
     if (const char* err = gemm_check(g)) throw_error(err);
     const bool plain = !g.out_l && !g.resid_h && !g.ln_stats && !g.stats_out && g.act == ACT_NONE && g.M % SAG_BM == 0 &&
@@ -916,29 +962,38 @@ bool token_self_attention_out_with_gemm(const float* q, const float* kx, const f
     if (!plain) return false;
     const int tiles = (g.M / SAG_BM) * (g.N / SAG_BN);
     const int bx = out.N / 4, by = (P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE;
-    hipLaunchKernelGGL(self_attn_out_and_gemm_kernel, dim3(tiles + bx * by), dim3(256), SAG_LDS, s, g, tiles, q, kx, v, out, P, bx);
+    // the tiles sit behind the self-attention's workgroups and find their XCD by their own index (xcd_remap): that is the
+    // XCD the hardware gave them only if a multiple of 8 workgroups stands in front
+    if ((bx * by) % 8) return false;
+    DLIMG_FOR_TOKENS(T, "token_self_attention_out",
+        hipLaunchKernelGGL(self_attn_out_and_gemm_kernel<TOK>, dim3(tiles + bx * by), dim3(256), SAG_LDS<TOK>, s, g, tiles, q, kx, v,
+                           out, P, bx);)
     return true;
 }
 
 void token_merge_linear(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenLinear& next, int P,
-                        hipStream_t s) {
+                        int T, hipStream_t s) {
     if (P <= 0) return;
-    if (P * TOK > TL_MAX_ROWS || out.K != INNER || out.N != DIM || out.resid.add || next.K != DIM || next.N % 64 || next.resid.x)
+    if (!decoder_tokens_supported(T) || P * T > TL_MAX_ROWS || out.K != INNER || out.N != DIM || out.resid.add || next.K != DIM ||
+        next.N % 64 || next.resid.x)
         throw_error("token_merge_linear: unsupported shape");
-    auto launch = [&](auto cols_tag, k::LdsOptIn& opt_in) {
-        constexpr int COLS = decltype(cols_tag)::value;
-        opt_in.ensure((const void*)token_merge_linear_kernel<COLS>, TML_LDS, "token_merge_linear: the device refuses the kernel's LDS size");
-        hipLaunchKernelGGL(token_merge_linear_kernel<COLS>, dim3(next.N / COLS, P), dim3(256), TML_LDS, s, scratch, out, out_wt, next, P);
+    auto launch = [&](auto tok_tag, auto cols_tag) {
+        constexpr int TOK = decltype(tok_tag)::value, COLS = decltype(cols_tag)::value;
+        static k::LdsOptIn opt_in;          // one per instantiation of this lambda's call operator: per (TOK, COLS)
+        opt_in.ensure((const void*)token_merge_linear_kernel<TOK, COLS>, TML_LDS<TOK>, "token_merge_linear: the device refuses the kernel's LDS size");
+        hipLaunchKernelGGL((token_merge_linear_kernel<TOK, COLS>), dim3(next.N / COLS, P), dim3(256), TML_LDS<TOK>, s, scratch, out, out_wt,
+                           next, P);
     };
-    static k::LdsOptIn opt16, opt32, opt64;
     // the smallest workgroups that still fit the chip in one round (256 CUs, one workgroup each: 150 KB of LDS)
-    if ((next.N / 16) * P <= 256) launch(std::integral_constant<int, 16>{}, opt16);
-    else if ((next.N / 32) * P <= 256) launch(std::integral_constant<int, 32>{}, opt32);
-    else launch(std::integral_constant<int, 64>{}, opt64);
+    DLIMG_FOR_TOKENS(T, "token_merge_linear",
+        const std::integral_constant<int, TOK> tok;
+        if ((next.N / 16) * P <= 256) launch(tok, std::integral_constant<int, 16>{});
+        else if ((next.N / 32) * P <= 256) launch(tok, std::integral_constant<int, 32>{});
+        else launch(tok, std::integral_constant<int, 64>{});)
 }
 
 void token_to_image_partials(const float* q, const TokenLinear* q_proj, const half_t* K, int ldk, const half_t* V, int ldv,
-                             float* scratch, int P, hipStream_t s) {
+                             float* scratch, int P, int T, hipStream_t s) {
     if (P <= 0) return;
     if (ldk % 8 || ldv % 8 || (((uintptr_t)K | (uintptr_t)V) & 15))
         throw_error("token_to_image_attention: K/V rows must be 16-byte aligned");
@@ -950,15 +1005,17 @@ void token_to_image_partials(const float* q, const TokenLinear* q_proj, const ha
     } else if (!q) {
         throw_error("token_to_image_attention: neither queries nor their projection given");
     }
-    hipLaunchKernelGGL(token_to_image_partial_kernel, dim3(P * HEADS * T2I_GROUPS), dim3(T2I_THREADS), 0, s, q, qp, K, ldk, V,
-                       ldv, scratch);
+    DLIMG_FOR_TOKENS(T, "token_to_image_attention",
+        hipLaunchKernelGGL(token_to_image_partial_kernel<TOK>, dim3(P * HEADS * T2I_GROUPS), dim3(T2I_THREADS), 0, s, q, qp, K, ldk, V,
+                           ldv, scratch);)
 }
 
 void output_heads(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenRows& norm,
-                  const HeadWeights& hw, float* hyper, float* iou, int P, hipStream_t s) {
+                  const HeadWeights& hw, float* hyper, float* iou, int P, int T, hipStream_t s) {
     if (P <= 0) return;
     if (out.K != INNER || out.N != DIM || !norm.ln_w) throw_error("output_heads: unsupported shape");
-    hipLaunchKernelGGL(output_heads_kernel, dim3(P, 5), dim3(HEAD_THREADS), 0, s, scratch, out, out_wt, norm, hw, hyper, iou);
+    DLIMG_FOR_TOKENS(T, "output_heads",
+        hipLaunchKernelGGL(output_heads_kernel<TOK>, dim3(P, 5), dim3(HEAD_THREADS), 0, s, scratch, out, out_wt, norm, hw, hyper, iou);)
 }
 
 }  // namespace k

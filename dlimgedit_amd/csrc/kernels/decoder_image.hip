@@ -9,10 +9,11 @@
 #include "device_common.hpp"
 #include "kernels.hpp"
 
+#include <type_traits>
+
 namespace dlimg {
 namespace {
 
-constexpr int TOK = 7;
 constexpr int DIM = 256;
 constexpr int INNER = 128;
 constexpr int NTOK_IMG = 4096;
@@ -28,8 +29,8 @@ DLIMG_DEVICE float sum_over_groups(float v) {
 
 // ---------------------------------------------------------------------------------------------
 // keys <- LayerNorm(keys + attention(image -> tokens) Wo + bo), with the f16 copy the next projection reads.
-//   attention: an image position attends to the 7 tokens of its prompt, 8 heads x 16 (q: f16 [rows][ldq], token k / v:
-//              fp32 [P][7][128]); lane (row m = lane % 16, group g = lane / 16) does heads 2g and 2g + 1 of its row, so its
+//   attention: an image position attends to the TOK (7 or 8) tokens of its prompt, 8 heads x 16 (q: f16 [rows][ldq],
+//              token k / v: fp32 [P][TOK][128]); lane (row m = lane % 16, group g = lane / 16) does heads 2g and 2g + 1 of its row, so its
 //              32 outputs ARE the A fragments of the projection for k = 32 g + 8 kk .. + 7, kk = 0 .. 3
 //   projection: 128 -> 256 on v_mfma_f32_16x16x32_f16, Wo (f16 [256][128]) in LDS for the workgroup's 64 rows
 //   epilogue  : + bias + residual (the keys, fp32), LayerNorm over the 256 columns of a row (64 values in the lane, the
@@ -38,7 +39,7 @@ DLIMG_DEVICE float sum_over_groups(float v) {
 // round trip through HBM per prompt become one launch that reads q and the keys once and writes the keys once.
 constexpr int IU_ROWS = 64;
 constexpr int IU_WSTRIDE = INNER + 8;        // halves per row of Wo in LDS: 272 B, so the 16 rows of a fragment read spread over the banks
-constexpr size_t IU_LDS = (size_t)DIM * IU_WSTRIDE * 2 + 2 * TOK * INNER * 4 + 3 * DIM * 4;
+template <int TOK> constexpr size_t IU_LDS = (size_t)DIM * IU_WSTRIDE * 2 + 2 * TOK * INNER * 4 + 3 * DIM * 4;
 
 struct ImageUpdate {
     const half_t* q; int ldq;
@@ -48,10 +49,12 @@ struct ImageUpdate {
     float* keys; half_t* keys_h;
 };
 
+template <int TOK>
 __global__ __launch_bounds__(256) void image_update_kernel(ImageUpdate a) {
+    static_assert(TOK * INNER / 4 <= 256, "a thread stages one float4 of the prompt's token k and v");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     half_t* w_lds = reinterpret_cast<half_t*>(smem);                                   // [256][IU_WSTRIDE]
-    float* sk = reinterpret_cast<float*>(smem + (size_t)DIM * IU_WSTRIDE * 2);         // [7][128]
+    float* sk = reinterpret_cast<float*>(smem + (size_t)DIM * IU_WSTRIDE * 2);         // [TOK][128]
     float* sv = sk + TOK * INNER;
     float* cb = sv + TOK * INNER;                                                      // bias | ln_w | ln_b
     const int tid = threadIdx.x, lane = lane_id(), wave = tid >> 6;
@@ -95,7 +98,7 @@ __global__ __launch_bounds__(256) void image_update_kernel(ImageUpdate a) {
     cb[2 * DIM + tid] = c2;
     __syncthreads();
 
-    // attention of this lane's row over the 7 tokens, heads 2g and 2g + 1
+    // attention of this lane's row over the prompt's tokens, heads 2g and 2g + 1
     half8_t afrag[4];
 #pragma unroll
     for (int hh = 0; hh < 2; ++hh) {
@@ -396,14 +399,20 @@ __global__ __launch_bounds__(256) void upscale_logits_kernel(Upscale a) {
 namespace k {
 
 void image_update(const half_t* q, int ldq, const float* tk, const float* tv, const half_t* W, const float* bias,
-                  const float* ln_w, const float* ln_b, float eps, float* keys, half_t* keys_h, int P, hipStream_t s) {
+                  const float* ln_w, const float* ln_b, float eps, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
     if (P <= 0) return;
-    if (ldq % 8 || (((uintptr_t)q | (uintptr_t)W | (uintptr_t)keys | (uintptr_t)keys_h) & 15))
+    if (ldq % 8 || (((uintptr_t)q | (uintptr_t)W | (uintptr_t)keys | (uintptr_t)keys_h | (uintptr_t)tk | (uintptr_t)tv) & 15))
         throw_error("image_update: operands must be 16-byte aligned");
-    static k::LdsOptIn opt_in;
-    opt_in.ensure((const void*)image_update_kernel, IU_LDS, "image_update: the device refuses the kernel's LDS size");
     ImageUpdate a{q, ldq, tk, tv, W, bias, ln_w, ln_b, eps, keys, keys_h};
-    hipLaunchKernelGGL(image_update_kernel, dim3(P * NTOK_IMG / IU_ROWS), dim3(256), IU_LDS, s, a);
+    auto launch = [&](auto tok_tag) {
+        constexpr int TOK = decltype(tok_tag)::value;
+        static k::LdsOptIn opt_in;          // one per token count
+        opt_in.ensure((const void*)image_update_kernel<TOK>, IU_LDS<TOK>, "image_update: the device refuses the kernel's LDS size");
+        hipLaunchKernelGGL(image_update_kernel<TOK>, dim3(P * NTOK_IMG / IU_ROWS), dim3(256), IU_LDS<TOK>, s, a);
+    };
+    if (T == 7) launch(std::integral_constant<int, 7>{});
+    else if (T == 8) launch(std::integral_constant<int, 8>{});
+    else throw_error("image_update: 7 or 8 tokens per prompt");
 }
 
 

@@ -137,8 +137,14 @@ void attention_global(const half_t* qkv, const half_t* rel_h, const half_t* rel_
                       int heads, int hd, hipStream_t);
 
 // ---- mask decoder (token side is tiny: fp32 VALU kernels) ------------------------------------
+// Every launcher of the token side takes T, the token rows per prompt: 5 output tokens (iou + 4 mask tokens) + the prompt's
+// points, 7 (a point and its pad token, or a box) or 8 (a point and a box).  A launch never mixes counts, and one launch
+// holds at most 112 token rows: decoder_max_prompts(T) prompts.
+constexpr int kDecoderMaxRows = 112;
+constexpr bool decoder_tokens_supported(int T) { return T == 7 || T == 8; }
+constexpr int decoder_max_prompts(int T) { return kDecoderMaxRows / T; }
 // floats of workspace for the per-key-group partial results of token_to_image_partials
-size_t token_to_image_scratch_floats(int P);
+size_t token_to_image_scratch_floats(int P, int T);
 // A [rows][256] fp32 token matrix as a consumer sees it: optionally LayerNorm'ed (over the 256 columns) and with another
 // matrix added behind the LayerNorm (the query positional encoding), both applied while the rows are read.
 struct TokenRows {
@@ -160,53 +166,57 @@ struct TokenLinear {
     int N = 0;
     int relu = 0;
 };
-// The prompts of one decode (at most 16 per launch), passed to the first kernel by value: coords [P][2][2] in the
-// 1024-pixel frame, labels [P][2], and per prompt the DEVICE address of its image embedding ([4096][256] fp32).
+// The prompts of one decode (at most 16 per launch); the part a launch uses travels in the first kernel's arguments.  With
+// n = T - 5 points per prompt (2 or 3): coords [P][n][2] in the 1024-pixel frame, labels [P][n], both tightly packed, and per prompt the DEVICE address
+// of its image embedding ([4096][256] fp32).
 constexpr int kDecoderMaxPrompts = 16;
+constexpr int kDecoderMaxPoints = 3;
 struct DecoderPrompts {
-    float coords[kDecoderMaxPrompts * 4];
-    float labels[kDecoderMaxPrompts * 2];
+    float coords[kDecoderMaxPrompts * kDecoderMaxPoints * 2];
+    float labels[kDecoderMaxPrompts * kDecoderMaxPoints];
     const float* emb[kDecoderMaxPrompts];
 };
-// First launch of a decode.  tokens [P,7,256]: iou token, 4 mask tokens, 2 prompt tokens (the positional part later steps
+// First launch of a decode.  tokens [P,T,256]: iou token, 4 mask tokens, T - 5 prompt tokens (the positional part later steps
 // add); `first` (n_first <= 5 layers, K = 256, no LayerNorm / residual; their `in` is ignored) are applied to those same
 // rows in this launch.  Image side: keys = emb[p] + no_mask (fp32 + f16) for all prompts.
 void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, hipStream_t s);
-// up to 5 layers over the same rows (<= 112) in one launch
-void token_linears(const TokenLinear* ops, int count, int rows, hipStream_t);
-// self-attention among the 7 tokens of each prompt + its output projection `out` (K = 256) in one launch
-void token_self_attention_out(const float* q, const float* k, const float* v, const TokenLinear& out, int P, hipStream_t);
+                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s);
+// up to 5 layers over the same rows (<= 112, whole prompts of T rows) in one launch
+void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t);
+// self-attention among the T tokens of each prompt + its output projection `out` (K = 256) in one launch
+void token_self_attention_out(const float* q, const float* k, const float* v, const TokenLinear& out, int P, int T, hipStream_t);
 // The same launch carrying a plain GEMM (no activation, no folded LayerNorm, fp32 bias / residual, f16 or fp32 result) that
 // neither depends on it nor it on the GEMM: its 64 x 64 tiles are extra workgroups of the launch (decoder.hip).  Returns false
-// without launching anything when `g` is not of that kind (the caller then launches both on their own).
-bool token_self_attention_out_with_gemm(const float* q, const float* k, const float* v, const TokenLinear& out, int P,
+// without launching anything when `g` is not of that kind, or when the self-attention's workgroups are not a multiple of 8
+// (the tiles behind them keep their XCDs only then); the caller then launches both on their own.
+bool token_self_attention_out_with_gemm(const float* q, const float* k, const float* v, const TokenLinear& out, int P, int T,
                                         const GemmArgs& g, hipStream_t);
 // token-to-image attention.  partials: per key group (max, sum, output) of every (prompt, head, token); the queries
-// are q [P,7,128], or are computed in the launch as q_proj (256 -> 128, LayerNorm / positional part on the fly).  The
+// are q [P,T,128], or are computed in the launch as q_proj (256 -> 128, LayerNorm / positional part on the fly).  The
 // fold of the partials + output projection `out` (128 -> 256, out_wt = its weight transposed [128][256]) + residual is
 // done by the consumer's launch: token_merge_linear (writes out.Y and applies `next`, a K = 256 layer whose input is
 // next.in's LayerNorm of out.Y) or output_heads.
 void token_to_image_partials(const float* q, const TokenLinear* q_proj, const half_t* K, int ldk, const half_t* V, int ldv,
-                             float* scratch, int P, hipStream_t);
+                             float* scratch, int P, int T, hipStream_t);
 void token_merge_linear(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenLinear& next, int P,
-                        hipStream_t);
+                        int T, hipStream_t);
 // The image positions' half of a two-way block in one launch (kernels/decoder_image.hip):
 // keys <- LayerNorm(keys + attention(q -> token k / v) Wo + bias), fp32 in place + f16 copy.  q: f16 [P*4096][ldq] (128 wide),
-// tk / tv: fp32 [P][7][128], W: f16 [256][128].
+// tk / tv: fp32 [P][T][128], W: f16 [256][128].
 void image_update(const half_t* q, int ldq, const float* tk, const float* tv, const half_t* W, const float* bias,
-                  const float* ln_w, const float* ln_b, float eps, float* keys, half_t* keys_h, int P, hipStream_t);
+                  const float* ln_w, const float* ln_b, float eps, float* keys, half_t* keys_h, int P, int T, hipStream_t);
 // Up-scaling path + mask product in one launch (kernels/decoder_image.hip): logits [P,4,256,256] from the f16 keys, the two
 // transposed convolutions as GEMM weights (W1 [256][256], rows = sub-pixel * 64 + channel; W2 [128][64], rows = sub-pixel * 32
 // + channel), the LayerNorm2d between them and the hyper vectors [P,4,32].
 void upscale_logits(const half_t* keys_h, const half_t* W1, const float* b1, const float* ln_w, const float* ln_b, float eps,
                     const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t);
 // hyper-network MLPs (4 x 256->256->256->32) and IoU head (256->256->256->4) on the output tokens: the launch finishes the
-// final token-to-image attention (scratch, out, out_wt as above) for the five tokens it needs and applies `norm` to them
+// final token-to-image attention (scratch, out, out_wt as above) for the five tokens it needs (rows 0..4 of each prompt's
+// T) and applies `norm` to them
 struct HeadWeights { const float* w[5][3]; const float* b[5][3]; };
 void output_heads(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenRows& norm /*ln_w, ln_b, eps*/,
-                  const HeadWeights& hw, float* hyper /*[P,4,32]*/, float* iou /*[P,4]*/, int P, hipStream_t);
+                  const HeadWeights& hw, float* hyper /*[P,4,32]*/, float* iou /*[P,4]*/, int P, int T, hipStream_t);
 
 // ---- mask post-processing (K16) --------------------------------------------------------------
 // For each of `count` jobs: logits plane job.src (256x256 f32, device) -> two-stage bilinear

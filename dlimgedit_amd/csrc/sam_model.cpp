@@ -884,7 +884,7 @@ void SamModel::reserve_decoder(int count) {
     logits_.reserve(P * 4 * kLowRes * kLowRes);
     iou_.reserve(P * 4);
     hyper_.reserve(P * 4 * 32);
-    const size_t T = P * kDecTokens;
+    const size_t T = P * kDecMaxTokens;
     tokens_.reserve(T * 256);
     queries_.reserve(T * 256);
     tk_.reserve(T * 256);
@@ -894,25 +894,31 @@ void SamModel::reserve_decoder(int count) {
     sv_.reserve(T * 256);
     tsa_.reserve(T * 256);
     tt2i_.reserve(T * 256);
-    t2i_part_.reserve(k::token_to_image_scratch_floats((int)P));
+    t2i_part_.reserve(k::token_to_image_scratch_floats((int)P, kDecMaxTokens));
     tmlp_.reserve(T * 2048);
     dec_count_ = count;
 }
 
-void SamModel::decode(float const* const* emb, float const* coords, float const* labels, int count) {
+void SamModel::decode(float const* const* emb, float const* coords, float const* labels, int count, int points) {
     DLIMG_ASSERT(count > 0);
+    DLIMG_ASSERT(points >= 2 && points <= k::kDecoderMaxPoints);
+    static_assert(5 + k::kDecoderMaxPoints == kDecMaxTokens && k::decoder_tokens_supported(kDecTokens) &&
+                  k::decoder_tokens_supported(kDecMaxTokens), "the kernels are built for these token counts");
     reserve_decoder(count);
-    // the token-side kernels take at most 16 prompts (112 rows) per launch: larger requests run in chunks that share
-    // the workspaces (stream order) and write their own part of logits() / iou()
-    constexpr int kChunk = 16;
-    for (int c0 = 0; c0 < count; c0 += kChunk)
-        decode_chunk(emb + c0, coords + (size_t)c0 * 4, labels + (size_t)c0 * 2, std::min(kChunk, count - c0), c0);
+    // the token-side kernels take at most 112 token rows per launch (16 prompts of 7 rows, 14 of 8): larger requests run
+    // in chunks that share the workspaces (stream order) and write their own part of logits() / iou()
+    const int chunk = k::decoder_max_prompts(5 + points);
+    for (int c0 = 0; c0 < count; c0 += chunk)
+        decode_chunk(emb + c0, coords + (size_t)c0 * points * 2, labels + (size_t)c0 * points, std::min(chunk, count - c0), c0,
+                     points);
     mark_activity();
 }
 
-void SamModel::decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first) {
+void SamModel::decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first,
+                            int points) {
     SamWeights const& W = *weights_;
-    const int P = count, M = P * kTokens, T = P * kDecTokens;
+    const int TOK = 5 + points;                      // token rows per prompt
+    const int P = count, M = P * kTokens, T = P * TOK;
     hipStream_t s = stream_;
     float* logits_out = logits_.get() + (size_t)first * 4 * kLowRes * kLowRes;
     float* iou_out = iou_.get() + (size_t)first * 4;
@@ -920,8 +926,8 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
     auto body = [&] {
         // prompts travel as kernel arguments of the first launch
         k::DecoderPrompts prompts{};
-        std::memcpy(prompts.coords, coords, (size_t)P * 4 * sizeof(float));
-        std::memcpy(prompts.labels, labels, (size_t)P * 2 * sizeof(float));
+        std::memcpy(prompts.coords, coords, (size_t)P * points * 2 * sizeof(float));
+        std::memcpy(prompts.labels, labels, (size_t)P * points * sizeof(float));
         for (int i = 0; i < P; ++i) prompts.emb[i] = emb[i];
 
         // Token side.  `cur` is the running token matrix as its consumers read it: un-normalised rows plus the
@@ -959,7 +965,7 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             k::TokenLinear qkv[3] = {lin({}, 256, L.self_attn.q, {}, sq_.get(), 0), lin({}, 256, L.self_attn.k, {}, sk_.get(), 0),
                                      lin({}, 256, L.self_attn.v, {}, sv_.get(), 0)};
             k::decoder_start(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
-                             W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, s);
+                             W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, TOK, s);
         }
         for (int i = 0; i < 2; ++i) {
             DecoderLayer const& L = W.dec_[i];
@@ -971,19 +977,19 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             const k::TokenLinear self_out = lin({}, 256, L.self_attn.o, i == 0 ? k::TokenRows{} : cur, tsa_.get(), 0);
             // (DLIMGEDIT_DECODER_RIDE=0: measurement aid, the two launches on their own)
             static const bool ride = [] { const char* e = std::getenv("DLIMGEDIT_DECODER_RIDE"); return !e || std::atoi(e) != 0; }();
-            if (!ride || !k::token_self_attention_out_with_gemm(sq_.get(), sk_.get(), sv_.get(), self_out, P, img_gemm_args(L.img_kqv, L.pos_kqv), s)) {
-                k::token_self_attention_out(sq_.get(), sk_.get(), sv_.get(), self_out, P, s);
+            if (!ride || !k::token_self_attention_out_with_gemm(sq_.get(), sk_.get(), sv_.get(), self_out, P, TOK, img_gemm_args(L.img_kqv, L.pos_kqv), s)) {
+                k::token_self_attention_out(sq_.get(), sk_.get(), sv_.get(), self_out, P, TOK, s);
                 img_gemm(L.img_kqv, L.pos_kqv);
             }
             const k::TokenRows q1 = normed(tsa_.get(), L.ln1);
             const k::TokenLinear tq = lin(rows_of(q1, true), 256, L.t2i_q, {}, nullptr, 0);
-            k::token_to_image_partials(nullptr, &tq, kqv_h_.get(), 384, kqv_h_.get() + 256, 384, t2i_part_.get(), P, s);
+            k::token_to_image_partials(nullptr, &tq, kqv_h_.get(), 384, kqv_h_.get() + 256, 384, t2i_part_.get(), P, TOK, s);
             const k::TokenRows q2 = normed(tt2i_.get(), L.ln2);
             // (3) token MLP
             k::token_merge_linear(t2i_part_.get(), lin({}, 128, L.t2i_o, q1, tt2i_.get(), 0), L.t2i_o_t.get(),
-                                  lin(q2, 256, L.mlp1, {}, tmlp_.get(), 1), P, s);
+                                  lin(q2, 256, L.mlp1, {}, tmlp_.get(), 1), P, TOK, s);
             k::TokenLinear m2 = lin(plain(tmlp_.get()), 2048, L.mlp2, q2, queries_.get(), 0);
-            k::token_linears(&m2, 1, T, s);
+            k::token_linears(&m2, 1, T, TOK, s);
             const k::TokenRows q3 = normed(queries_.get(), L.ln3);
             // (4) image -> tokens.  Everything else that reads the same rows q3 rides in this launch: the next layer's
             // self-attention projections, or (last layer) the query projection of the final token -> image attention.
@@ -998,14 +1004,14 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             } else {
                 kv[n_ops++] = lin(rows_of(q3, true), 256, W.final_q_, {}, sq_.get(), 0);
             }
-            k::token_linears(kv, n_ops, T, s);
+            k::token_linears(kv, n_ops, T, TOK, s);
             k::image_update(kqv_h_.get() + 128, 384, tk_.get(), tv_.get(), L.i2t_o.w.get(), L.i2t_o.b.get(), L.ln4.w.get(),
-                            L.ln4.b.get(), kDecLnEps, keys_.get(), keys_h_.get(), P, s);
+                            L.ln4.b.get(), kDecLnEps, keys_.get(), keys_h_.get(), P, TOK, s);
             cur = q3;
         }
         // final token -> image attention; its fold + output projection + norm_final_attn happen in output_heads
         img_gemm(W.final_kv_, W.final_pos_kv_);
-        k::token_to_image_partials(sq_.get(), nullptr, kqv_h_.get(), 256, kqv_h_.get() + 128, 256, t2i_part_.get(), P, s);
+        k::token_to_image_partials(sq_.get(), nullptr, kqv_h_.get(), 256, kqv_h_.get() + 128, 256, t2i_part_.get(), P, TOK, s);
 
         k::HeadWeights hw;
         for (int m = 0; m < 5; ++m)
@@ -1014,7 +1020,7 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
                 hw.b[m][j] = W.heads_[m][j].b.get();
             }
         k::output_heads(t2i_part_.get(), lin({}, 128, W.final_o_, cur, nullptr, 0), W.final_o_t_.get(), normed(nullptr, W.ln_final_),
-                        hw, hyper_.get(), iou_out, P, s);
+                        hw, hyper_.get(), iou_out, P, TOK, s);
         // upscaling ConvT(256->64) -> LN2d -> GELU -> ConvT(64->32) -> GELU and the product with the hyper vectors
         k::upscale_logits(keys_h_.get(), W.up1_.w.get(), W.up1_.b.get(), W.up_ln_.w.get(), W.up_ln_.b.get(), kLnEps,
                           W.up2_.w.get(), W.up2_.b.get(), hyper_.get(), logits_out, P, s);
@@ -1027,7 +1033,7 @@ std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() {
     const size_t T = kDecTokens;
     return {{"tokens", T * 256}, {"final_q", T * 128}, {"self_k", T * 256}, {"self_v", T * 256}, {"self_out", T * 256},
             {"t2i_out", T * 256}, {"mlp_hidden", T * 2048}, {"queries", T * 256}, {"i2t_k", T * 128}, {"i2t_v", T * 128},
-            {"final_partials", k::token_to_image_scratch_floats(1)}, {"hyper", 4 * 32}, {"iou", 4}, {"keys_head", 4096}};
+            {"final_partials", k::token_to_image_scratch_floats(1, kDecTokens)}, {"hyper", 4 * 32}, {"iou", 4}, {"keys_head", 4096}};
 }
 
 void SamModel::decoder_state(float* out) const {

@@ -27,7 +27,8 @@ constexpr int kTokens = 4096;       // 64 x 64 embedding grid
 constexpr int kEmbedDim = 256;      // channels of the image embedding
 constexpr int kPatchK = 768;        // 3 * 16 * 16
 constexpr int kImageSize = 1024;    // /root/reference/src/segmentation.cpp:17
-constexpr int kDecTokens = 7;
+constexpr int kDecTokens = 7;       // token rows of a two-point prompt (a point and its pad token, or a box): 5 + 2
+constexpr int kDecMaxTokens = 8;    // ... of a three-point prompt (a point and a box): the workspaces are sized by it
 constexpr int kLowRes = 256;
 
 struct LinearH {                    // f16 weight for MFMA GEMMs, fp32 bias
@@ -183,9 +184,10 @@ class SamModel {
     void encode(int batch, float* const* emb_dst = nullptr);
     float const* embeddings() const { return emb_.get(); }
 
-    // Decoder for `count` prompts. emb[i]: device embedding of prompt i's image; coords [count][2][2],
-    // labels [count][2] host arrays. Results stay on device: logits() [count][4][256][256], iou() [count][4].
-    void decode(float const* const* emb, float const* coords, float const* labels, int count);
+    // Decoder for `count` prompts of `points` points each (2 or 3: every prompt of a call has the same number, 5 + points
+    // token rows). emb[i]: device embedding of prompt i's image; coords [count][points][2], labels [count][points] host
+    // arrays. Results stay on device: logits() [count][4][256][256], iou() [count][4].
+    void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2);
     float const* logits() const { return logits_.get(); }
     // Diagnostic: the token-side workspaces as the last decode of ONE prompt left them (after synchronize()), one after
     // the other; names/sizes in decoder_state_layout().  What a parity or race hunt compares stage by stage.
@@ -263,7 +265,7 @@ class SamModel {
   private:
     void reserve_encoder(int batch);
     void reserve_decoder(int count);
-    void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first);
+    void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
     template <typename F> void timed(Stage st, double work, F&& launch);
     void flush_events();

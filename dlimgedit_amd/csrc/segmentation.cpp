@@ -24,15 +24,20 @@ void ResizeLongestSide::set(Extent image) {
     if (scale != 1) resized = Extent{scale_coord(image.width, scale), scale_coord(image.height, scale)};
 }
 
-void pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float coords[4],
-                 float labels[2]) {
-    DLIMG_ASSERT((point != nullptr) != (region != nullptr));
+int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float* coords, float* labels) {
+    DLIMG_ASSERT(point != nullptr || region != nullptr);
     auto set = [&](int index, Point p, int label) {
         Point t = rs.transform(p);
         coords[index * 2 + 0] = float(t.x);
         coords[index * 2 + 1] = float(t.y);
         labels[index] = float(label);
     };
+    if (point && region) {
+        set(0, *point, 1);           // PromptEncoder.forward: points first, then the corners; a box takes no padding point
+        set(1, region->top_left, 2);
+        set(2, region->bottom_right, 3);
+        return 3;
+    }
     if (point) {
         set(0, *point, 1);
         set(1, Point{0, 0}, -1);     // padding point of the exported decoder graph
@@ -40,7 +45,19 @@ void pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* 
         set(0, region->top_left, 2);
         set(1, region->bottom_right, 3);
     }
+    return 2;
 }
+
+namespace {
+// prompt i of a batch call: points [count][2], regions [count][4], either or both
+void pack_batch_prompt(ResizeLongestSide const& rs, int const* points, int const* regions, int i, float* coords, float* labels) {
+    Point p;
+    Region r;
+    if (points) p = Point{points[i * 2], points[i * 2 + 1]};
+    if (regions) r = Region{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
+    pack_prompt(rs, points ? &p : nullptr, regions ? &r : nullptr, coords, labels);
+}
+}  // namespace
 
 void check_image(dlimg_ImageView const& image) {
     if (!image.pixels) throw Exception("Image has no pixel data");
@@ -383,8 +400,12 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
     DLIMG_ASSERT(point || region);
     DLIMG_ASSERT(embedding_ != nullptr);
     if (invalid_) throw Exception(kOverflowMessage);
+    // a two-point prompt always: a given point wins and the region is ignored (reference: segmentation.cpp:146-152);
+    // the three-point form of pack_prompt belongs to the batch calls
+    if (point) region = nullptr;
     float coords[4], labels[2];
-    pack_prompt(image_size_, point, region, coords, labels);
+    const int npts = pack_prompt(image_size_, point, region, coords, labels);
+    DLIMG_ASSERT(npts == 2);
     const bool is_single_mask = out_masks[1] == nullptr;
     if (is_single_mask) {
         DLIMG_ASSERT(out_masks[0] != nullptr);
@@ -440,22 +461,17 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
 void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                           int const* regions, uint8_t* const* out_masks) {
     if (count <= 0) return;
-    DLIMG_ASSERT((points != nullptr) != (regions != nullptr));
+    DLIMG_ASSERT(points != nullptr || regions != nullptr);
+    const int npts = points && regions ? 3 : 2;          // points per prompt, the same for every entry of the call
     constexpr int kPromptChunk = 8;
     EnvironmentImpl& env = segs[0]->env_;
-    std::vector<float> coords((size_t)count * 4), labels((size_t)count * 2);
+    std::vector<float> coords((size_t)count * npts * 2), labels((size_t)count * npts);
     std::vector<int> used;
     for (int i = 0; i < count; ++i) {
         DLIMG_ASSERT(&segs[i]->env_ == &env);
         DLIMG_ASSERT(segs[i]->embedding_ != nullptr && out_masks[i] != nullptr);
         segs[i]->settle();                       // prompts of a batch go to any lane: the embeddings are complete first
-        if (points) {
-            Point p{points[i * 2], points[i * 2 + 1]};
-            pack_prompt(segs[i]->image_size_, &p, nullptr, &coords[i * 4], &labels[i * 2]);
-        } else {
-            Region r{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
-            pack_prompt(segs[i]->image_size_, nullptr, &r, &coords[i * 4], &labels[i * 2]);
-        }
+        pack_batch_prompt(segs[i]->image_size_, points, regions, i, &coords[(size_t)i * npts * 2], &labels[(size_t)i * npts]);
         if (std::find(used.begin(), used.end(), segs[i]->replica_) == used.end()) used.push_back(segs[i]->replica_);
     }
     for_each_replica(env, used, [&](int replica) {
@@ -481,12 +497,12 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
             for (size_t base = 0; base < mine.size(); base += kPromptChunk) {
                 const int n = (int)std::min<size_t>(kPromptChunk, mine.size() - base);
                 std::vector<float const*> emb(n);
-                std::vector<float> cc((size_t)n * 4), ll((size_t)n * 2);
+                std::vector<float> cc((size_t)n * npts * 2), ll((size_t)n * npts);
                 for (int j = 0; j < n; ++j) {
                     const int i = mine[base + j];
                     emb[j] = segs[i]->embedding_;
-                    std::copy_n(&coords[(size_t)i * 4], 4, &cc[(size_t)j * 4]);
-                    std::copy_n(&labels[(size_t)i * 2], 2, &ll[(size_t)j * 2]);
+                    std::copy_n(&coords[(size_t)i * npts * 2], npts * 2, &cc[(size_t)j * npts * 2]);
+                    std::copy_n(&labels[(size_t)i * npts], npts, &ll[(size_t)j * npts]);
                 }
                 SamModel& model = env.next_lane(replica);
                 // masks of a chunk are copied to the caller while the two chunks behind it are on the GPU
@@ -496,12 +512,12 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
                 Chunk& cur = chunks.back();
                 roctx::Range range("dlimg.compute_masks");
                 std::lock_guard<std::mutex> lock(model.mutex());
-                model.decode(emb.data(), cc.data(), ll.data(), n);
+                model.decode(emb.data(), cc.data(), ll.data(), n, npts);
                 for (int j = 0; j < n; ++j) {
                     const int i = mine[base + j];
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
-                    cur.jobs[j] = k::PostJob{model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4,
-                                             out_masks[i], o.width, o.height, r.width, r.height};
+                    cur.jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
+                                                  out_masks[i], o, r);
                 }
                 model.enqueue_masks(*cur.slot, cur.jobs.data(), n, 0);
             }
@@ -527,14 +543,15 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
                                                  int const* regions, int root_device, uint8_t* dev_out,
                                                  size_t* out_offsets) {
     if (count <= 0) return;
-    DLIMG_ASSERT((points != nullptr) != (regions != nullptr));
+    DLIMG_ASSERT(points != nullptr || regions != nullptr);
     DLIMG_ASSERT(dev_out != nullptr);
+    const int npts = points && regions ? 3 : 2;
     if (root_device < 0 || root_device >= EnvironmentImpl::device_count())
         throw Exception("root device " + std::to_string(root_device) + " is out of range: " +
                         std::to_string(EnvironmentImpl::device_count()) + " device(s) visible");
     constexpr int kPromptChunk = 8;
     EnvironmentImpl& env = segs[0]->env_;
-    std::vector<float> coords((size_t)count * 4), labels((size_t)count * 2);
+    std::vector<float> coords((size_t)count * npts * 2), labels((size_t)count * npts);
     std::vector<size_t> offsets(count);
     std::vector<int> used;
     size_t total = 0;
@@ -542,13 +559,7 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
         DLIMG_ASSERT(&segs[i]->env_ == &env);
         DLIMG_ASSERT(segs[i]->embedding_ != nullptr);
         segs[i]->settle();
-        if (points) {
-            Point p{points[i * 2], points[i * 2 + 1]};
-            pack_prompt(segs[i]->image_size_, &p, nullptr, &coords[i * 4], &labels[i * 2]);
-        } else {
-            Region r{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
-            pack_prompt(segs[i]->image_size_, nullptr, &r, &coords[i * 4], &labels[i * 2]);
-        }
+        pack_batch_prompt(segs[i]->image_size_, points, regions, i, &coords[(size_t)i * npts * 2], &labels[(size_t)i * npts]);
         offsets[i] = total;
         total += (size_t)segs[i]->image_size_.original.width * segs[i]->image_size_.original.height;
         if (std::find(used.begin(), used.end(), segs[i]->replica_) == used.end()) used.push_back(segs[i]->replica_);
@@ -580,24 +591,24 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
             for (size_t base = 0; base < mine.size(); base += kPromptChunk) {
                 const int n = (int)std::min<size_t>(kPromptChunk, mine.size() - base);
                 std::vector<float const*> emb(n);
-                std::vector<float> cc((size_t)n * 4), ll((size_t)n * 2);
+                std::vector<float> cc((size_t)n * npts * 2), ll((size_t)n * npts);
                 std::vector<k::PostJob> jobs(n);
                 for (int j = 0; j < n; ++j) {
                     const int i = mine[base + j];
                     emb[j] = segs[i]->embedding_;
-                    std::copy_n(&coords[(size_t)i * 4], 4, &cc[(size_t)j * 4]);
-                    std::copy_n(&labels[(size_t)i * 2], 2, &ll[(size_t)j * 2]);
+                    std::copy_n(&coords[(size_t)i * npts * 2], npts * 2, &cc[(size_t)j * npts * 2]);
+                    std::copy_n(&labels[(size_t)i * npts], npts, &ll[(size_t)j * npts]);
                 }
                 SamModel& model = env.next_lane(replica);
                 chunks.push_back(Chunk{&model, &model.acquire_mask_slot()});
                 roctx::Range range("dlimg.compute_masks_device");
                 std::lock_guard<std::mutex> lock(model.mutex());
-                model.decode(emb.data(), cc.data(), ll.data(), n);
+                model.decode(emb.data(), cc.data(), ll.data(), n, npts);
                 for (int j = 0; j < n; ++j) {
                     const int i = mine[base + j];
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
-                    jobs[j] = k::PostJob{model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4,
-                                         dev_out + offsets[i], o.width, o.height, r.width, r.height};
+                    jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
+                                              dev_out + offsets[i], o, r);
                 }
                 model.enqueue_masks_device(*chunks.back().slot, jobs.data(), n, root_device);
             }

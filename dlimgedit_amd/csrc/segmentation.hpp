@@ -32,9 +32,17 @@ struct ResizeLongestSide {
     int max_side_;
 };
 
-// Packs one prompt the way SegmentationImpl::compute_mask does (reference: segmentation.cpp:135-152).
-void pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float coords[4],
-                 float labels[2]);
+// Packs one prompt and returns its number of points.  A point OR a region: two points, the way
+// SegmentationImpl::compute_mask does (reference: segmentation.cpp:135-152; coords[4], labels[2]).  A point AND a region
+// (the batch calls only): three points as SAM's PromptEncoder.forward orders them, the point in front of the box corners
+// and no pad token, labels 1, 2, 3 (coords[6], labels[3]).
+int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float* coords, float* labels);
+// Which logits plane a single-mask query of `points` prompt points takes (SamOnnxModel.select_masks adds
+// (points - 2.5) * 1000 to prediction 0): with two points the best of planes 1..3, chosen on the device from the IoU
+// predictions; with three always plane 0.
+inline k::PostJob single_mask_job(float const* logits4, float const* iou4, int points, uint8_t* dst, Extent o, Extent r) {
+    return k::PostJob{logits4, points > 2 ? nullptr : iou4, dst, o.width, o.height, r.width, r.height};
+}
 
 class SegmentationImpl {
   public:
@@ -47,6 +55,8 @@ class SegmentationImpl {
 
     void compute_mask(Point const* point, Region const* region, uint8_t* const out_masks[3],
                       float out_accuracy[3]) const;
+    // points XOR regions: entry i is a point or a box query.  Both: entry i is the box regions[i] refined by the foreground
+    // point points[i], one three-point prompt (pack_prompt); every entry of a call has the same number of points.
     static void compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                    int const* regions, uint8_t* const* out_masks);
 

@@ -112,7 +112,11 @@ typedef struct dlimg_Api {
                                                     int count, dlimg_Environment env);
 
     /* One single-mask query per entry, decoded as one batch.  points: count x {x,y} or NULL;
-     * regions: count x {x0,y0,x1,y1} or NULL (exactly one of them non-null).  The same handle may
+     * regions: count x {x0,y0,x1,y1} or NULL (at least one of them non-null).  One array: entry i is a point
+     * or a box query, as get_segmentation_mask.  Both arrays: entry i is the box regions[i] refined by the
+     * foreground point points[i] -- SAM's combined prompt (point, top-left, bottom-right; labels 1, 2, 3; no
+     * padding point), whose single mask is the decoder's output 0.  [get_segmentation_mask keeps the
+     * reference's rule: given both, the point wins and the region is ignored.]  The same handle may
      * appear several times (several prompts on one cached embedding). out_masks[i]: width*height bytes. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);

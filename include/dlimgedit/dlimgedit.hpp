@@ -257,8 +257,13 @@ class Segmentation {
         return out;
     }
 
-    // One point query per segmentation, decoded as one batch (addition of this build).
-    static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs, std::vector<Point> const& points) {
+    // One single-mask query per segmentation, decoded as one batch (addition of this build): a point each, a region each
+    // (points empty), or -- both given -- the region regions[i] refined by the foreground point points[i] in one prompt.
+    static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs, std::vector<Point> const& points,
+                                                 std::vector<Region> const& regions = {}) {
+        if ((points.empty() && regions.empty()) || (!points.empty() && points.size() != segs.size()) ||
+            (!regions.empty() && regions.size() != segs.size()))
+            throw Exception("compute_mask_batch: one point and / or one region per segmentation");
         std::vector<dlimg_Segmentation> hs;
         std::vector<Image> out;
         std::vector<uint8_t*> ptrs;
@@ -267,7 +272,9 @@ class Segmentation {
             out.emplace_back(s->extent(), Channels::mask);
             ptrs.push_back(out.back().pixels());
         }
-        detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), &points.data()->x, nullptr, ptrs.data()));
+        static_assert(sizeof(Point) == 2 * sizeof(int) && sizeof(Region) == 4 * sizeof(int), "packed as the C table reads them");
+        detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), points.empty() ? nullptr : &points.data()->x,
+                                                   regions.empty() ? nullptr : &regions.data()->top_left.x, ptrs.data()));
         return out;
     }
 
