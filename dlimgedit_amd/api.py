@@ -608,12 +608,25 @@ class ext:
         _check(cls._l().dlimg_amd_copy_to_host(env.handle(), dst.ctypes.data, src, dst.nbytes))
 
     @staticmethod
-    def device_views(ptrs, width, height, channels=Channels.rgba):
+    def device_views(ptrs, width, height, channels=Channels.rgba, stride=None):
+        """Views of device-resident images for encode_and_mask / encode_only.  width, height, channels and stride are one
+        value for all views or one per view; stride defaults to packed rows.  Any size: the library resamples a view
+        whose longest side is not 1024 on the device, exactly as process() resamples a host image of that size."""
         n = len(ptrs)
-        return (_ImageView * n)(*[_ImageView(width, height, int(channels), width * count(channels), p) for p in ptrs])
+
+        def per_view(value):
+            return list(value) if isinstance(value, (list, tuple)) else [value] * n
+
+        ws, hs, cs, ss = per_view(width), per_view(height), per_view(channels), per_view(stride)
+        return (_ImageView * n)(*[_ImageView(ws[i], hs[i], int(cs[i]), ws[i] * count(cs[i]) if ss[i] is None else ss[i], ptrs[i])
+                                  for i in range(n)])
 
     @classmethod
     def encode_and_mask(cls, env, views, points, mask_ptrs) -> None:
+        """Queues one request per view: encode the device-resident image, decode points[i] (pixels of the view's own
+        width x height) and write the mask, width x height bytes, to the device buffer mask_ptrs[i].  Views may have any
+        size and differ from each other; requests of different sizes share a pass as requests of one size do.  Returns once
+        the requests are queued; synchronize() waits for the masks and reports what failed."""
         n = len(views)
         p = (C.c_int * (2 * n))(*[v for q in points for v in (q.x, q.y)])
         m = (C.c_void_p * n)(*mask_ptrs)
@@ -621,6 +634,7 @@ class ext:
 
     @classmethod
     def encode_only(cls, env, views) -> None:
+        """Encodes the device-resident images of `views` (any size, see device_views) in one pass; enqueues only."""
         _check(cls._l().dlimg_amd_encode_only(env.handle(), views, len(views)))
 
     @classmethod

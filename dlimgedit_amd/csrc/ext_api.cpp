@@ -20,14 +20,27 @@ namespace {
 
 using namespace extapi;
 
-// Shared by encode_and_mask / encode_only: images already on the device.
+// A device-resident view of any size; returns the extent it is encoded at (longest side 1024, as slots 3 / 13 encode a
+// host image of that size).
+Extent check_device_image(dlimg_ImageView const& view) {
+    check_image(view);
+    ResizeLongestSide rs;
+    rs.set(Extent{view.width, view.height});
+    if (rs.resized.width <= 0 || rs.resized.height <= 0)
+        throw Exception("Image is too narrow: its short side vanishes at the encoder's resolution");
+    return rs.resized;
+}
+
+// Shared by encode_and_mask / encode_only: images already on the device.  An image whose longest side is not 1024 is
+// resampled to it on the way into the patch matrix (SamModel::preprocess_device_images).
 void encode_device_images(SamModel& model, dlimg_ImageView const* imgs, int count) {
+    std::vector<int> resized((size_t)count * 2);
     for (int i = 0; i < count; ++i) {
-        check_image(imgs[i]);
-        if (std::max(imgs[i].width, imgs[i].height) != kImageSize)
-            throw Exception("device-resident images must have their longest side at 1024 pixels");
+        const Extent r = check_device_image(imgs[i]);
+        resized[i * 2] = r.width;
+        resized[i * 2 + 1] = r.height;
     }
-    model.preprocess_device_images(imgs, count);
+    model.preprocess_device_images(imgs, resized.data(), count);
     model.encode(count);
 }
 
@@ -340,10 +353,8 @@ DLIMG_API int dlimg_amd_encode_and_mask(dlimg_Environment env, dlimg_ImageView c
         DLIMG_ASSERT(dev_images != nullptr && points != nullptr && dev_masks != nullptr && count > 0);
         EnvironmentImpl& e = impl(env);
         for (int i = 0; i < count; ++i) {
-            check_image(dev_images[i]);
+            check_device_image(dev_images[i]);       // refused here, not when its pass is enqueued
             DLIMG_ASSERT(dev_masks[i] != nullptr);
-            if (std::max(dev_images[i].width, dev_images[i].height) != kImageSize)
-                throw Exception("device-resident images must have their longest side at 1024 pixels");
         }
         std::lock_guard<std::mutex> lock(e.pending_mutex);
         if (count >= step_queue_width(e)) {

@@ -177,6 +177,54 @@ DLIMG_DEVICE void store16_result(void* p, V v) {
 #endif
 }
 
+// Byte offsets of R, G, B inside one pixel of a dlimg::Channels code (mask=1, rgb=3, rgba=4, bgra=5, argb=6; reference:
+// create_image_tensor, segmentation.cpp:82-95) and the pixel's size.  Shared by the pre-processing kernel and the resize
+// that ends in it.
+struct ChannelMap { int bytes; int idx[3]; };
+
+__host__ __device__ inline ChannelMap channel_map(int channels) {
+    switch (channels) {
+    case 1: return {1, {0, 0, 0}};
+    case 3: return {3, {0, 1, 2}};
+    case 5: return {4, {2, 1, 0}};
+    case 6: return {4, {1, 2, 3}};
+    default: return {4, {0, 1, 2}};
+    }
+}
+
+// The tail every producer of the patch matrix shares (preprocess_kernel, resize_cols_preprocess_kernel): their bits must agree.
+// Normalisation constants of the encoder's in-graph pre-processing (export_models.py: pixel_mean / pixel_std).
+static __constant__ float c_mean[3] = {123.675f, 116.28f, 103.53f};
+static __constant__ float c_std[3] = {58.395f, 57.12f, 57.375f};
+DLIMG_DEVICE float normalise_pixel(float u8, int c) { return (u8 - c_mean[c]) / c_std[c]; }
+
+// Lane mapping of a patch-matrix writer launched as 512 workgroups of 256 threads per image: one wave covers two
+// horizontally adjacent patches; lane = iy*4 + p*2 + half owns 8 pixels (x0 .. x0+7) of image row y, so that 4 consecutive
+// lanes cover one 128-byte line of RGBA and the 32 lanes of one patch fill a contiguous 512-byte run per channel.
+struct PatchLane { int patch, iy, half, y, x0; };
+DLIMG_DEVICE PatchLane patch_lane() {
+    const int lane = lane_id();
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);       // patch pair index, 2048 per image
+    PatchLane l;
+    l.iy = lane >> 2;
+    l.half = lane & 1;
+    l.patch = pair * 2 + ((lane >> 1) & 1);
+    l.y = (l.patch >> 6) * 16 + l.iy;
+    l.x0 = (l.patch & 63) * 16 + l.half * 8;
+    return l;
+}
+// v[c][i]: normalised value of channel c at pixel x0 + i -> f16, column c*256 + iy*16 + ix of the patch's row; 16 bytes per channel
+DLIMG_DEVICE void store_patch_pixels(half_t* out, const PatchLane& l, const float (&v)[3][8]) {
+    half_t* dst = out + (size_t)l.patch * 768 + l.iy * 16 + l.half * 8;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        half8_t o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (half_t)v[c][i];
+        store16_result(dst + c * 256, o);
+    }
+}
+
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 

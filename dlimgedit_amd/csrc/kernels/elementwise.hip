@@ -16,25 +16,7 @@ namespace {
 // Output is the A operand of the patch-embedding GEMM: [4096 patches, 768] f16,
 // column = c*256 + iy*16 + ix.
 //
-// Mapping: one wave covers two horizontally adjacent patches; lane = iy*4 + p*2 + half reads
-// 8 pixels (32 B of RGBA) so that 4 consecutive lanes read one full 128-byte line, and writes
-// 16 B per channel so that the 32 lanes of one patch fill a contiguous 512-byte run per channel.
-
-__constant__ float c_mean[3] = {123.675f, 116.28f, 103.53f};
-__constant__ float c_std[3] = {58.395f, 57.12f, 57.375f};
-
-struct ChannelMap { int bytes; int idx[3]; };
-
-__host__ __device__ inline ChannelMap channel_map(int channels) {
-    // dlimg::Channels: mask=1, rgb=3, rgba=4, bgra=5, argb=6  (segmentation.cpp:82-95)
-    switch (channels) {
-    case 1: return {1, {0, 0, 0}};
-    case 3: return {3, {0, 1, 2}};
-    case 5: return {4, {2, 1, 0}};
-    case 6: return {4, {1, 2, 3}};
-    default: return {4, {0, 1, 2}};
-    }
-}
+// Lane mapping, normalisation constants and the store: patch_lane / normalise_pixel / store_patch_pixels (device_common.hpp).
 
 // Up to 16 images per launch (blockIdx.y = image): the images of one batched pass share a launch, and at 16 images the
 // kernel moves 168 MB, enough to be measured against the HBM rate instead of the launch floor (bench.py, hbm_kernels).
@@ -47,13 +29,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreJobs jobs) {
     const uint8_t* __restrict__ img = job.img;
     half_t* __restrict__ out = job.out;
     const int w = job.w, h = job.h, stride = job.stride, channels = job.channels;
-    const int lane = lane_id();
-    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6);       // patch pair index, 2048 per image
-    const int iy = lane >> 2, p = (lane >> 1) & 1, half = lane & 1;
-    const int patch = pair * 2 + p;
-    const int py = patch >> 6, px = patch & 63;
-    const int y = py * 16 + iy;
-    const int x0 = px * 16 + half * 8;
+    const PatchLane pl = patch_lane();
+    const int y = pl.y, x0 = pl.x0;
     const ChannelMap cm = channel_map(channels);
 
     float v[3][8];
@@ -74,7 +51,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreJobs jobs) {
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     float u = (float)((px32[i] >> (8 * cm.idx[c])) & 0xffu);
-                    v[c][i] = (u - c_mean[c]) / c_std[c];
+                    v[c][i] = normalise_pixel(u, c);
                 }
         } else {
 #pragma unroll
@@ -82,19 +59,12 @@ __global__ __launch_bounds__(256) void preprocess_kernel(PreJobs jobs) {
                 if (x0 + i < w) {
                     const uint8_t* px8 = row + (size_t)(x0 + i) * cm.bytes;
 #pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c][i] = ((float)px8[cm.idx[c]] - c_mean[c]) / c_std[c];
+                    for (int c = 0; c < 3; ++c) v[c][i] = normalise_pixel((float)px8[cm.idx[c]], c);
                 }
             }
         }
     }
-    half_t* dst = out + (size_t)patch * 768 + iy * 16 + half * 8;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        half8_t o;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) o[i] = (half_t)v[c][i];
-        store16_result(dst + c * 256, o);
-    }
+    store_patch_pixels(out, pl, v);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -113,6 +113,16 @@ struct ResizeAxis { const int* first; const int* count; const float* coef; int t
 void resize_srgb(const uint8_t* src, int w, int h, int stride, int C, const ResizeAxis& ax, const ResizeAxis& ay,
                  const float* decode_lut, const uint32_t* encode_tab, float* tmp, uint8_t* dst, hipStream_t);
 
+// ---- K18 longest-side resize fused with pre-processing, for the images of one pass ---------------------------
+// src u8 [h][stride] (dlimg::Channels code `channels`) -> resampled to ax.out x ay.out exactly as resize_srgb does and
+// written as preprocess writes it: f16 patch-major [4096, 768] with zero padding outside ax.out x ay.out.  The resampled
+// u8 image is never stored.  tmp: fp32 scratch of resize_preprocess_tmp_floats(h, ax.out, channels) floats, 32-byte
+// aligned, one area per image.  Two launches for up to 16 images.
+struct ResizeJob { const uint8_t* src; int w, h, stride, channels; ResizeAxis ax, ay; float* tmp; half_t* patches; };
+size_t resize_preprocess_tmp_floats(int h, int rw, int channels);
+void resize_preprocess_batch(const ResizeJob* jobs, int count, const float* decode_lut, const uint32_t* encode_tab,
+                             hipStream_t);
+
 // ---- elementwise -----------------------------------------------------------------------------
 // out_h[i] = f16(a[i] + (b ? b[i % b_mod] : 0)); out_f32 likewise (either may be null); n % 4 == 0
 void add_cast(const float* a, const float* b, size_t b_mod, size_t n, float* out_f32, half_t* out_h, hipStream_t);

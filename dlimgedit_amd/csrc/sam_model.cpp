@@ -574,24 +574,34 @@ void SamModel::preprocess_device_image(int slot, int batch, uint8_t const* dev_p
                                        int channels) {
     DLIMG_ASSERT(slot >= 0 && slot < batch);
     reserve_encoder(batch);
+    forget_staged_resize(slot);
     const int bytes = channels > 4 ? 4 : channels;
     timed(ST_PRE, (double)w * h * bytes + (double)kTokens * kPatchK * 2, [&] {
         k::preprocess(dev_pixels, w, h, stride, channels, patches_.get() + (size_t)slot * kTokens * kPatchK, stream_);
     });
 }
 
-void SamModel::preprocess_device_images(dlimg_ImageView const* views, int batch) {
-    DLIMG_ASSERT(views != nullptr && batch > 0);
+void SamModel::preprocess_device_images(dlimg_ImageView const* views, int const* resized_wh, int batch) {
+    DLIMG_ASSERT(views != nullptr && resized_wh != nullptr && batch > 0);
     reserve_encoder(batch);
-    std::vector<k::PreImage> images(batch);
+    staged_resizes_.clear();                     // every slot of the pass is filled here
+    std::vector<k::PreImage> images;
+    std::vector<ResizeRequest> resizes;
     double bytes = 0;
     for (int i = 0; i < batch; ++i) {
-        const int px = views[i].channels > 4 ? 4 : views[i].channels;
-        images[i] = k::PreImage{views[i].pixels, views[i].width, views[i].height, views[i].stride, views[i].channels,
-                                patches_.get() + (size_t)i * kTokens * kPatchK};
-        bytes += (double)views[i].width * views[i].height * px + (double)kTokens * kPatchK * 2;
+        dlimg_ImageView const& v = views[i];
+        const int rw = resized_wh[i * 2], rh = resized_wh[i * 2 + 1];
+        if (rw == v.width && rh == v.height) {
+            const int px = v.channels > 4 ? 4 : v.channels;
+            images.push_back(k::PreImage{v.pixels, v.width, v.height, v.stride, v.channels,
+                                         patches_.get() + (size_t)i * kTokens * kPatchK});
+            bytes += (double)v.width * v.height * px + (double)kTokens * kPatchK * 2;
+        } else {
+            resizes.push_back(ResizeRequest{v.pixels, v.width, v.height, v.stride, v.channels, rw, rh, i});
+        }
     }
-    timed(ST_PRE, bytes, [&] { k::preprocess_batch(images.data(), batch, stream_); });
+    if (!images.empty()) timed(ST_PRE, bytes, [&] { k::preprocess_batch(images.data(), (int)images.size(), stream_); });
+    if (!resizes.empty()) resize_into_patches(resizes.data(), (int)resizes.size());
 }
 
 // Packs `rows` rows of `row_bytes` bytes into the next entry of the pinned staging ring and returns it; *copied is the
@@ -665,25 +675,89 @@ std::shared_ptr<SamModel::AxisDev const> SamModel::axis_table(int in_size, int o
             std::rotate(axis_cache_.begin() + i, axis_cache_.begin() + i + 1, axis_cache_.end());
             return axis_cache_.back();
         }
+    // A size this lane has not seen (or no longer remembers): the tables are built on this thread and allocated once;
+    // they travel behind whatever the stream holds, nobody waits for them.
     AxisTable t = make_axis_table(in_size, out_size);
     auto a = std::make_shared<AxisDev>();
     a->in_size = in_size;
     a->out_size = out_size;
     a->taps = t.taps;
-    a->first.reserve(t.first.size());
-    a->count.reserve(t.count.size());
-    a->coef.reserve(t.coef.size());
-    HIP_CHECK(hipMemcpy(a->first.get(), t.first.data(), t.first.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(a->count.get(), t.count.data(), t.count.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(a->coef.get(), t.coef.data(), t.coef.size() * sizeof(float), hipMemcpyHostToDevice));
+    const size_t n_first = t.first.size() * sizeof(int), n_count = t.count.size() * sizeof(int);
+    const size_t n_coef = t.coef.size() * sizeof(float);
+    a->host.reserve(n_first + n_count + n_coef);
+    a->dev.reserve(n_first + n_count + n_coef);
+    uint8_t* host = static_cast<uint8_t*>(a->host.get());
+    std::memcpy(host, t.first.data(), n_first);
+    std::memcpy(host + n_first, t.count.data(), n_count);
+    std::memcpy(host + n_first + n_count, t.coef.data(), n_coef);
+    HIP_CHECK(hipMemcpyAsync(a->dev.get(), host, n_first + n_count + n_coef, hipMemcpyHostToDevice, stream_));
+    a->first = reinterpret_cast<int const*>(a->dev.get());
+    a->count = reinterpret_cast<int const*>(a->dev.get() + n_first);
+    a->coef = reinterpret_cast<float const*>(a->dev.get() + n_first + n_count);
     if (axis_cache_.size() >= kAxisCacheEntries) {
-        // The entry's device tables may still be read by a resize kernel queued on this lane's stream; callers hold
-        // their own reference for the duration of the call, but the kernel outlives the call.
+        // The only wait of this path, and only once a lane has seen more than kAxisCacheEntries (in, out) pairs: the
+        // evicted entry's device tables may still be read by a resize queued on this lane's stream, and its pinned copy by
+        // the upload in front of that.  Callers hold their own reference for the duration of the call, but the kernel
+        // outlives the call.
         HIP_CHECK(hipStreamSynchronize(stream_));
         axis_cache_.erase(axis_cache_.begin());
     }
     axis_cache_.push_back(a);
     return a;
+}
+
+void SamModel::resize_into_patches(ResizeRequest const* requests, int count) {
+    // At most as many images at a time as the table cache has entries for (two axes each): no lookup then evicts -- and
+    // frees -- a table that an earlier lookup of the same group returned while its launches are still to come.  A later
+    // group may evict an earlier group's tables; eviction waits for the stream first (axis_table).
+    constexpr int kGroup = (int)(kAxisCacheEntries / 2);
+    if (count > kGroup) {
+        for (int base = 0; base < count; base += kGroup) resize_into_patches(requests + base, std::min(kGroup, count - base));
+        return;
+    }
+    if (!srgb_decode_.get()) {               // first resize of this lane
+        float lut[256];
+        srgb_decode_table(lut);
+        srgb_decode_.reserve(256);
+        srgb_encode_.reserve(104);
+        HIP_CHECK(hipMemcpy(srgb_decode_.get(), lut, sizeof(lut), hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(srgb_encode_.get(), kSrgbEncodeTab4, sizeof(kSrgbEncodeTab4), hipMemcpyHostToDevice));
+    }
+    // the tables are held by value until the launch: looking up one axis may evict the entry of another
+    std::vector<std::shared_ptr<AxisDev const>> held((size_t)count * 2);
+    std::vector<size_t> offset(count);
+    size_t floats = 0;
+    double bytes = 0;
+    for (int i = 0; i < count; ++i) {
+        ResizeRequest const& r = requests[i];
+        DLIMG_ASSERT(r.slot >= 0 && r.slot < enc_batch_);
+        DLIMG_ASSERT(r.w > 0 && r.h > 0 && r.rw > 0 && r.rh > 0 && r.rw <= kImageSize && r.rh <= kImageSize);
+        held[i * 2] = axis_table(r.w, r.rw);
+        held[i * 2 + 1] = axis_table(r.h, r.rh);
+        offset[i] = floats;
+        floats += k::resize_preprocess_tmp_floats(r.h, r.rw, r.channels);
+        bytes += (double)r.w * r.h * (r.channels > 4 ? 4 : r.channels) + (double)kTokens * kPatchK * 2;
+    }
+    // Every image of the pass has its own fp32 rows; the area as a whole is re-used by the next pass in stream order.
+    // Growing it frees memory that queued kernels may still read, so everything queued runs first (a pass larger than
+    // any before it on this lane; never in steady state).
+    if (floats > resize_tmp_.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        resize_tmp_.reserve(floats);
+    }
+    std::vector<k::ResizeJob> jobs(count);
+    for (int i = 0; i < count; ++i) {
+        ResizeRequest const& r = requests[i];
+        AxisDev const& ax = *held[i * 2];
+        AxisDev const& ay = *held[i * 2 + 1];
+        jobs[i] = k::ResizeJob{r.pixels, r.w, r.h, r.stride, r.channels,
+                               k::ResizeAxis{ax.first, ax.count, ax.coef, ax.taps, r.rw},
+                               k::ResizeAxis{ay.first, ay.count, ay.coef, ay.taps, r.rh},
+                               resize_tmp_.get() + offset[i], patches_.get() + (size_t)r.slot * kTokens * kPatchK};
+    }
+    timed(ST_PRE, bytes, [&] {
+        k::resize_preprocess_batch(jobs.data(), count, srgb_decode_.get(), srgb_encode_.get(), stream_);
+    });
 }
 
 void SamModel::upload_and_resize_image(int slot, int batch, uint8_t const* pixels, int w, int h, int stride, int channels,
@@ -693,47 +767,48 @@ void SamModel::upload_and_resize_image(int slot, int batch, uint8_t const* pixel
     reserve_encoder(batch);
     const int bytes = channels > 4 ? 4 : channels;
     const size_t row = (size_t)w * bytes;
-    if (!srgb_decode_.get()) {
-        float lut[256];
-        srgb_decode_table(lut);
-        srgb_decode_.reserve(256);
-        srgb_encode_.reserve(104);
-        HIP_CHECK(hipMemcpy(srgb_decode_.get(), lut, sizeof(lut), hipMemcpyHostToDevice));
-        HIP_CHECK(hipMemcpy(srgb_encode_.get(), kSrgbEncodeTab4, sizeof(kSrgbEncodeTab4), hipMemcpyHostToDevice));
-    }
-    // both tables are held by value: looking up the second axis may evict the entry of the first
-    const std::shared_ptr<AxisDev const> axp = axis_table(w, rw), ayp = axis_table(h, rh);
-    AxisDev const& ax = *axp;
-    AxisDev const& ay = *ayp;
-    // the source image and its fp32 intermediate are re-used by the next resize in stream order; growing them
-    // frees memory that queued kernels may still read, so everything queued runs first
-    if (row * h > resize_src_.capacity() || (size_t)h * rw * bytes > resize_tmp_.capacity())
+    forget_staged_resize(slot);
+    if ((int)resize_src_.size() <= slot) resize_src_.resize(slot + 1);
+    DeviceBuffer<uint8_t>& src = resize_src_[slot];
+    // the slot's source buffer is re-used by the next pass in stream order; growing it frees memory that queued kernels
+    // may still read, so everything queued runs first (the uploads of this pass lie in other slots' buffers)
+    if (row * h > src.capacity()) {
         HIP_CHECK(hipStreamSynchronize(stream_));
-    resize_src_.reserve(row * h);
-    resize_tmp_.reserve((size_t)h * rw * bytes);
+        src.reserve(row * h);
+    }
     if ((size_t)stride == row && image_memory_is_pinned(pixels, row * h)) {
-        HIP_CHECK(hipMemcpyAsync(resize_src_.get(), pixels, row * h, hipMemcpyHostToDevice, stream_));     // as upload_image
+        HIP_CHECK(hipMemcpyAsync(src.get(), pixels, row * h, hipMemcpyHostToDevice, stream_));     // as upload_image
         HIP_CHECK(hipEventRecord(caller_copied_, stream_));
         caller_copy_pending_ = true;
     } else {
         hipEvent_t copied = nullptr;
         uint8_t* pin = stage_rows(pixels, row, h, stride, &copied);
-        HIP_CHECK(hipMemcpyAsync(resize_src_.get(), pin, row * h, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipMemcpyAsync(src.get(), pin, row * h, hipMemcpyHostToDevice, stream_));
         HIP_CHECK(hipEventRecord(copied, stream_));
     }
-    uint8_t* dev = img_dev_.get() + (size_t)slot * kImageSize * kImageSize * 4;
-    k::ResizeAxis kx{ax.first.get(), ax.count.get(), ax.coef.get(), ax.taps, rw};
-    k::ResizeAxis ky{ay.first.get(), ay.count.get(), ay.coef.get(), ay.taps, rh};
-    timed(ST_PRE, (double)row * h + (double)rw * rh * bytes, [&] {
-        k::resize_srgb(resize_src_.get(), w, h, (int)row, bytes, kx, ky, srgb_decode_.get(), srgb_encode_.get(),
-                       resize_tmp_.get(), dev, stream_);
-    });
-    preprocess_device_image(slot, batch, dev, rw, rh, rw * bytes, channels);
+    // the same launch as the device-resident path, for all resized images of the pass together (run_staged_resizes)
+    staged_resizes_.push_back(ResizeRequest{src.get(), w, h, (int)row, channels, rw, rh, slot});
+}
+
+void SamModel::forget_staged_resize(int slot) {
+    // only a pass that was given up between staging and encode() leaves anything behind here
+    staged_resizes_.erase(std::remove_if(staged_resizes_.begin(), staged_resizes_.end(),
+                                         [slot](ResizeRequest const& r) { return r.slot == slot; }),
+                          staged_resizes_.end());
+}
+
+void SamModel::run_staged_resizes(int batch) {
+    if (staged_resizes_.empty()) return;
+    std::vector<ResizeRequest> now;
+    now.swap(staged_resizes_);               // whatever happens below, nothing stays staged
+    now.erase(std::remove_if(now.begin(), now.end(), [batch](ResizeRequest const& r) { return r.slot >= batch; }), now.end());
+    if (!now.empty()) resize_into_patches(now.data(), (int)now.size());
 }
 
 void SamModel::encode(int batch, float* const* emb_dst) {
     SamWeights const& W = *weights_;
     DLIMG_ASSERT(batch > 0 && batch <= enc_batch_);
+    run_staged_resizes(batch);                   // host images of other sizes: resampled into their slots, one launch per stage
     // one image, and no other lane of this GPU has anything in flight: the pass may trade CU time for latency
     alone_ = batch == 1 && shared_gpu_ && board_ && board_->others_idle(lane_index_);
     if (board_ && batch == 1) board_->count_pass(alone_);

@@ -172,13 +172,16 @@ class SamModel {
     void upload_image(int slot, int batch, uint8_t const* pixels, int w, int h, int stride, int channels);
     void wait_caller_copies();           // mutex() held or not: the event is this lane's own, re-recorded under mutex()
     // Host image whose longest side is not 1024: uploaded at its own size and resampled on the device to
-    // rw x rh (reference: dlimg::resize through stb, /root/reference/src/image.cpp:37-51).
+    // rw x rh (reference: dlimg::resize through stb, /root/reference/src/image.cpp:37-51).  The upload is enqueued
+    // here; the resize of all such images of the pass is one launch per stage in front of encode().
     void upload_and_resize_image(int slot, int batch, uint8_t const* pixels, int w, int h, int stride, int channels,
                                  int rw, int rh);
     // Device-resident image variant (used by the batch benchmark so PCIe is outside the timed region).
     void preprocess_device_image(int slot, int batch, uint8_t const* dev_pixels, int w, int h, int stride, int channels);
-    // All `batch` slots from device-resident images in ONE launch (views carry device pixel pointers).
-    void preprocess_device_images(dlimg_ImageView const* views, int batch);
+    // All `batch` slots from device-resident images of any size (views carry device pixel pointers).  resized[i] is the
+    // extent image i is encoded at (ResizeLongestSide); an image already of that extent takes the pre-processing launch,
+    // the others are resampled on the way by the fused resize: one launch per stage for all of them.
+    void preprocess_device_images(dlimg_ImageView const* views, int const* resized_wh, int batch);
     // Runs the encoder on `batch` uploaded images; embeddings [batch][4096][256] fp32 in embeddings() and, where
     // emb_dst[i] is given, in that device buffer too (batch 1: written there directly).
     void encode(int batch, float* const* emb_dst = nullptr);
@@ -304,18 +307,38 @@ class SamModel {
     static bool split_stream_allowed();
 
     // ---- longest-side resize (images whose longest side is not 1024)
+    // Contributor tables of one axis, cached per lane by (in, out).  The host copy lives in pinned memory for as long as
+    // the entry does: the tables reach the device by one stream-ordered copy, so a miss blocks nobody and a hit costs
+    // a lookup (no allocation, no copy, no synchronisation).
     struct AxisDev {
         int in_size = 0, out_size = 0, taps = 0;
-        DeviceBuffer<int> first, count;
-        DeviceBuffer<float> coef;
+        PinnedBuffer host;                   // first [out] | count [out] | coef [out][taps]
+        DeviceBuffer<uint8_t> dev;           // the same bytes
+        int const* first = nullptr;
+        int const* count = nullptr;
+        float const* coef = nullptr;
     };
     std::shared_ptr<AxisDev const> axis_table(int in_size, int out_size);
     static constexpr size_t kAxisCacheEntries = 64;
     std::vector<std::shared_ptr<AxisDev const>> axis_cache_;     // least recently used first
     DeviceBuffer<float> srgb_decode_;
     DeviceBuffer<uint32_t> srgb_encode_;
-    DeviceBuffer<uint8_t> resize_src_;
-    DeviceBuffer<float> resize_tmp_;
+    // host images: the upload at its own size, one buffer per slot of the pass, and the resizes staged so far -- they
+    // run as ONE launch per stage when the pass is encoded (encode()), not one after the other as the images arrive.
+    // Every function that fills a slot drops what was staged for it (preprocess_device_image, upload_and_resize_image,
+    // preprocess_device_images).
+    // Memory: a slot's buffer and the fp32 rows grow to the largest need seen and stay for the life of the lane: per
+    // lane at most  sum over the slots of the largest source image seen in that slot  +  the largest pass's fp32 rows
+    // (3 x h x 1024 x 4 bytes per image).  One 4000 x 3000 RGBA image at a time: 48 + 37 MB; a four-image pass of such
+    // images (the most slot 13 puts into one pass): 192 + 148 MB on the lane that ran it.
+    std::vector<DeviceBuffer<uint8_t>> resize_src_;
+    DeviceBuffer<float> resize_tmp_;         // fp32 rows between the two stages, one area per image of the pass
+    // Device pixels at their own size -> slot `slot` of the patch matrix at rw x rh, all images in one launch per stage
+    struct ResizeRequest { uint8_t const* pixels; int w, h, stride, channels, rw, rh, slot; };
+    void resize_into_patches(ResizeRequest const* requests, int count);
+    std::vector<ResizeRequest> staged_resizes_;
+    void forget_staged_resize(int slot);     // the slot is being filled anew
+    void run_staged_resizes(int batch);
 
     // ---- decoder workspace (sized for dec_count_ prompts)
     int dec_count_ = 0;

@@ -52,7 +52,11 @@ DLIMG_API int dlimg_amd_copy_to_host(dlimg_Environment env, void* dst_host, void
 /* One pass of the hot path over `count` images already in HBM: pre-process, encode (one batched
  * pass), decode one point prompt per image (single-mask mode) and write the 0/255 masks to
  * dev_masks[i] (width*height bytes each, device memory).  Views carry DEVICE pixel pointers.
- * points: count x {x,y}.  Asynchronous: returns once the request is accepted; call dlimg_amd_synchronize to wait.
+ * A view may have any size, channel order and row stride that slot 3 accepts for a host image, and the views of one
+ * call or one pass may differ: an image whose longest side is not 1024 pixels is resampled to it on the device, bit for
+ * bit as slot 3 resamples a host image of that size (stb_image_resize, sRGB), inside the pre-processing stage -- one
+ * launch per stage for all images of the pass, no copy of the resampled image.  The mask has the view's own width x height.
+ * points: count x {x,y} in pixels of the view (scaled as slot 4 scales them).  Asynchronous: returns once the request is accepted; call dlimg_amd_synchronize to wait.
  * The passes are put on the lanes' streams by one host thread per lane (DLIMGEDIT_STEP_WORKERS=0: by the calling thread);
  * a pass that cannot be enqueued drops its own requests only, and dlimg_amd_synchronize reports how many and why.
  * Independent single-image requests are coalesced into batched passes of DLIMGEDIT_COALESCE images (default 2, 1 = off;
@@ -60,7 +64,8 @@ DLIMG_API int dlimg_amd_copy_to_host(dlimg_Environment env, void* dst_host, void
  * partner is launched by the next request or by dlimg_amd_synchronize (which deals what is left evenly over the lanes). */
 DLIMG_API int dlimg_amd_encode_and_mask(dlimg_Environment env, dlimg_ImageView const* dev_images, int count,
                                         int const* points, uint8_t* const* dev_masks);
-/* Encode only / decode only variants of the above, for per-stage rates. */
+/* Encode only / decode only variants of the above, for per-stage rates.  dlimg_amd_encode_only takes views of any size,
+ * as dlimg_amd_encode_and_mask does, and encodes them in one pass. */
 DLIMG_API int dlimg_amd_encode_only(dlimg_Environment env, dlimg_ImageView const* dev_images, int count);
 /* Waits for every execution lane of the environment. */
 DLIMG_API int dlimg_amd_synchronize(dlimg_Environment env);
