@@ -48,6 +48,7 @@ SOURCES = [
     "kernels/resize.hip",
     "kernels/objects.hip",
     "resize_tables.cpp",
+    "gemm_plan.cpp",
     "image_io.cpp",
     "image_memory.cpp",
     "jpeg_decode.cpp",

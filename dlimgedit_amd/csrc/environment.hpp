@@ -90,7 +90,7 @@ class EnvironmentImpl {
     // launched yet: independent single-image requests are coalesced into ONE batched pass of `coalesce` images (dynamic
     // batching, as a serving host would do): with two images per pass the N = 768 GEMMs (patch, proj, fc2) reach 96
     // tiles of the 256 x 256 kernel instead of 96 of the 128 x 256 one.  Results are bit-identical to single-image
-    // passes (kernels/gemm.hip, tile choice).  DLIMGEDIT_COALESCE = 1 switches it off; dlimg_amd_synchronize flushes.
+    // passes (gemm_plan.cpp, tile choice).  DLIMGEDIT_COALESCE = 1 switches it off; dlimg_amd_synchronize flushes.
     // process_images_for_segmentation calls in flight (any thread): the pass size adapts to it (segmentation.cpp)
     std::atomic<int> batch_calls_in_flight{0};
     // Passes are handed to the lane with the least work in flight, and at most `step_depth` passes wait on a lane's

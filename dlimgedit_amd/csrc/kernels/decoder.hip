@@ -5,6 +5,7 @@
 // VALU work, kept in fp32 end to end.
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "gemm_plan.hpp"      // kStatRegs of gemm_f16_tile.inc
 
 #include <cstring>
 #include <mutex>

@@ -24,6 +24,7 @@
 // gemm16_f16_kernel on v_mfma_f32_16x16x32_f16 (BK 32), whose operand fragments travel one K tile ahead in registers.
 #include "device_common.hpp"
 #include "kernels.hpp"
+#include "gemm_plan.hpp"
 
 #include <hip/hip_ext.h>
 
@@ -41,8 +42,6 @@ namespace {
 #else
 #define DLIMG_STAMPS(a) (static_cast<unsigned long long*>(nullptr))
 #endif
-
-constexpr int BK_CHECK = 64;    // K must be a multiple of this for every configuration
 
 // tuning build only: the stream writers skip their residual read (WRONG results) -- what 4 of the epilogue's 10 bytes per
 // element cost
@@ -289,9 +288,7 @@ constexpr int kPPHalfBytes = 128 * 128;
 constexpr int kPPBufBytes = 4 * kPPHalfBytes;
 // Auxiliary area behind the operand buffers: rowstat [BM] (mean, rstd), colvec [2][256] (bias, LayerNorm column sums), then
 // EITHER rowpart [BM][4] (EPI_STATS: the waves' 64-column partials) OR the raw row-statistic partials of an EPI_NORM tile as
-// the producer left them, [group][BM] (sum, M2), kPPStatGroups groups at most (ping-pong producers leave 3 / 4 / 5 for
-// ViT-B / L / H; the 128- and 96-column tiles of a pass without other lanes up to 10)
-constexpr int kPPStatGroups = 12;
+// the producer left them, [group][BM] (sum, M2), kPPStatGroups groups at most (gemm_plan.hpp)
 constexpr int pp_aux_bytes(int bm) { return bm * 8 + 2 * 256 * 4 + (bm * 4 * 8 > kPPStatGroups * bm * 8 ? bm * 4 * 8 : kPPStatGroups * bm * 8); }
 constexpr int kPPAuxBytes = pp_aux_bytes(256);
 constexpr int kPPLds = 2 * kPPBufBytes + kPPAuxBytes;
@@ -957,9 +954,26 @@ void launch_flavour(GemmKernel const (&kernels)[5], k::LdsOptIn (&opt_in)[5], co
         hipLaunchKernelGGL(kernels[index], dim3(grid), dim3(threads), lds, s, a);
 }
 
-template <int BM, int BN, int WGM, int WGN, int NSTAGE, int MINW>
+// One launcher per row of k::kGemmTiles (gemm_plan.hpp), TILE its index: grid, workgroup size and LDS come from the row,
+// and every instantiation asserts that its kernel is the one the row describes.  stat_capacity: ln_groups its EPI_NORM
+// flavour can merge.
+template <int TILE>
+constexpr bool tile_row_is(int bm, int bn, int threads, size_t lds, k::TileFamily family, int stat_capacity) {
+    constexpr k::GemmTile row = k::kGemmTiles[TILE];
+    return row.bm == bm && row.bn == bn && row.threads == threads && (size_t)row.lds == lds && row.family == family &&
+           row.pair_stream == (family == k::TileFamily::pingpong) && row.stat_groups <= stat_capacity &&
+           row.lds * row.per_cu <= 160 * 1024;
+}
+template <int TILE>
+void launch_tile(GemmKernel const (&kernels)[5], k::LdsOptIn (&opt_in)[5], const k::GemmArgs& a, hipStream_t s, Timing t) {
+    constexpr k::GemmTile row = k::kGemmTiles[TILE];
+    launch_flavour(kernels, opt_in, a, (a.M / row.bm) * (a.N / row.bn), row.threads, row.lds, s, t);
+}
+
+template <int TILE, int BM, int BN, int WGM, int WGN, int NSTAGE, int MINW>
 void launch16(const k::GemmArgs& a, hipStream_t s, Timing t) {
-    const size_t lds = (size_t)NSTAGE * (BM + BN) * 64 + aux_bytes(BM, BN);
+    static_assert(tile_row_is<TILE>(BM, BN, 64 * WGM * WGN, (size_t)NSTAGE * (BM + BN) * 64 + aux_bytes(BM, BN), k::TileFamily::ring16,
+                                    kStatRegs * (64 * WGM * WGN / BM)), "gemm16_f16_kernel: the kernel and its row of k::kGemmTiles disagree");
     static const GemmKernel kernels[5] = {
         gemm16_f16_kernel<BM, BN, WGM, WGN, NSTAGE, MINW, k::ACT_NONE, EPI_PLAIN>,
         gemm16_f16_kernel<BM, BN, WGM, WGN, NSTAGE, MINW, k::ACT_GELU, EPI_PLAIN>,
@@ -968,12 +982,13 @@ void launch16(const k::GemmArgs& a, hipStream_t s, Timing t) {
         gemm16_f16_kernel<BM, BN, WGM, WGN, NSTAGE, MINW, k::ACT_NONE, EPI_STATS>,
     };
     static k::LdsOptIn attr_once[5];
-    launch_flavour(kernels, attr_once, a, (a.M / BM) * (a.N / BN), 64 * WGM * WGN, lds, s, t);
+    launch_tile<TILE>(kernels, attr_once, a, s, t);
 }
 
-template <int BM, int BN, int WGM, int WGN, int BKT, int NSTAGE, int MINW>
+template <int TILE, int BM, int BN, int WGM, int WGN, int BKT, int NSTAGE, int MINW>
 void launch(const k::GemmArgs& a, hipStream_t s, Timing t) {
-    const size_t lds = (size_t)NSTAGE * (BM + BN) * BKT * 2 + aux_bytes(BM, BN);
+    static_assert(tile_row_is<TILE>(BM, BN, 64 * WGM * WGN, (size_t)NSTAGE * (BM + BN) * BKT * 2 + aux_bytes(BM, BN), k::TileFamily::ring32,
+                                    kStatRegs * (64 * WGM * WGN / BM)), "gemm_f16_kernel: the kernel and its row of k::kGemmTiles disagree");
 #ifdef DLIMG_TUNING     // tuning build only (python -m dlimgedit_amd.build --tuning): ablated variants with WRONG results
     static const int ablate = [] { const char* e = std::getenv("DLIMGEDIT_GEMM_ABLATE"); return e ? std::atoi(e) : 0; }();
 #endif
@@ -989,189 +1004,49 @@ void launch(const k::GemmArgs& a, hipStream_t s, Timing t) {
         gemm_f16_kernel<BM, BN, WGM, WGN, BKT, NSTAGE, MINW, k::ACT_NONE, EPI_STATS>,
     };
     static k::LdsOptIn attr_once[5];
-    launch_flavour(kernels, attr_once, a, (a.M / BM) * (a.N / BN), 64 * WGM * WGN, lds, s, t);
+    launch_tile<TILE>(kernels, attr_once, a, s, t);
 }
 
+template <int TILE>
 void launch_pp(const k::GemmArgs& a, hipStream_t s, Timing t) {
+    static_assert(tile_row_is<TILE>(256, 256, 512, kPPLds, k::TileFamily::pingpong, kPPStatGroups), "gemm_pp_kernel: the kernel and its row of k::kGemmTiles disagree");
     static const GemmKernel kernels[5] = {
         gemm_pp_kernel<k::ACT_NONE, EPI_PLAIN>, gemm_pp_kernel<k::ACT_GELU, EPI_PLAIN>, gemm_pp_kernel<k::ACT_NONE, EPI_NORM>,
         gemm_pp_kernel<k::ACT_GELU, EPI_NORM>,  gemm_pp_kernel<k::ACT_NONE, EPI_STATS>,
     };
     static k::LdsOptIn attr_once[5];
-    launch_flavour(kernels, attr_once, a, (a.M / 256) * (a.N / 256), 512, kPPLds, s, t);
+    launch_tile<TILE>(kernels, attr_once, a, s, t);
 }
 
-template <int BM>
+template <int TILE, int BM>
 void launch_pp128(const k::GemmArgs& a, hipStream_t s, Timing t) {
+    static_assert(tile_row_is<TILE>(BM, 256, 512, pp128_lds(BM), k::TileFamily::pingpong, kPPStatGroups), "gemm_pp128_kernel: the kernel and its row of k::kGemmTiles disagree");
     static const GemmKernel kernels[5] = {
         gemm_pp128_kernel<BM, k::ACT_NONE, EPI_PLAIN>, gemm_pp128_kernel<BM, k::ACT_GELU, EPI_PLAIN>,
         gemm_pp128_kernel<BM, k::ACT_NONE, EPI_NORM>,  gemm_pp128_kernel<BM, k::ACT_GELU, EPI_NORM>,
         gemm_pp128_kernel<BM, k::ACT_NONE, EPI_STATS>,
     };
     static k::LdsOptIn attr_once[5];
-    launch_flavour(kernels, attr_once, a, (a.M / BM) * (a.N / 256), 512, pp128_lds(BM), s, t);
+    launch_tile<TILE>(kernels, attr_once, a, s, t);
 }
+
+typedef void (*TileLauncher)(const k::GemmArgs&, hipStream_t, Timing);
+constexpr TileLauncher kLaunchers[k::kGemmNumTiles] = {
+    launch<0, 128, 384, 2, 2, 64, 2, 1>, launch<1, 128, 288, 4, 1, 64, 3, 1>, launch<2, 128, 128, 2, 2, 64, 2, 4>,
+    launch<3, 128, 96, 4, 1, 64, 4, 1>,  launch<4, 128, 64, 2, 2, 64, 2, 3>,  launch<5, 64, 64, 2, 2, 64, 2, 4>,
+    launch<6, 256, 256, 2, 4, 32, 4, 2>, launch16<7, 256, 256, 2, 4, 4, 2>,   launch16<8, 128, 128, 2, 2, 4, 2>,
+    launch_pp<9>,                        launch_pp128<10, 128>,               launch_pp128<11, 64>,
+};
 
 }  // namespace
 
 namespace k {
 
-const char* gemm_check(const GemmArgs& a) {
-    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return "gemm: empty problem";
-    if (a.M % 64 || a.N % 64 || a.K % BK_CHECK) return "gemm: M, N must be multiples of 64 and K of 64";
-    if (a.lda % 8 || a.ldw % 8) return "gemm: operand leading dimensions must be multiples of 8 (16-byte rows)";
-    if (a.lda < a.K || a.ldw < a.K) return "gemm: leading dimension smaller than K";
-    if (((uintptr_t)a.A | (uintptr_t)a.W) & 15) return "gemm: operands must be 16-byte aligned";
-    if (a.resid && (a.resid_mod <= 0 || a.resid_mod % 64)) return "gemm: resid_mod must be a positive multiple of 64";
-    if (!a.out_f32 && !a.out_h) return "gemm: no output";
-    if (a.out_l && (a.out_f32 || !a.out_h || ((uintptr_t)a.out_l & 7))) return "gemm: an f16-pair result needs out_h and out_l (8-byte aligned) and no out_f32";
-    if ((a.resid_h != nullptr) != (a.resid_l != nullptr) || (a.resid_h && a.resid))
-        return "gemm: the residual is either fp32 or an f16 pair (resid_h and resid_l)";
-    if (a.resid_h && ((((uintptr_t)a.resid_h | (uintptr_t)a.resid_l) & 7) || a.ldrs % 4 || a.resid_mod <= 0 || a.resid_mod % 64))
-        return "gemm: f16-pair residual rows must be 8-byte aligned, resid_mod a positive multiple of 64";
-    if ((a.bias && ((uintptr_t)a.bias & 15)) || (a.resid && (((uintptr_t)a.resid & 15) || a.ldr % 4)) ||
-        (a.out_f32 && (((uintptr_t)a.out_f32 & 15) || a.ldc32 % 4)) ||
-        (a.out_h && (((uintptr_t)a.out_h & 7) || a.ldc16 % 4)))
-        return "gemm: bias/residual/output rows must be 16-byte (f16 output: 8-byte) aligned";
-    if (a.ln_stats && (!a.ln_colsum || ((uintptr_t)a.ln_colsum & 15) || a.ln_groups <= 0 || a.K % a.ln_groups ||
-                       a.ln_groups > kStatRegs * 2))
-        return "gemm: folded LayerNorm needs aligned column sums and 1..24 statistic groups that divide K";
-    if (a.stats_out && (a.ln_stats || a.act != ACT_NONE))
-        return "gemm: row statistics cannot be combined with an activation or a folded LayerNorm";
-    return nullptr;
-}
-
-// Tile configurations.  At batch 1 (M = 4096) a GEMM is only a few hundred workgroups, so what matters
-// is how evenly they cover the 256 CUs: every configuration is scored by (fill of the last round of
-// workgroup slots) x (relative efficiency of the tile) and the best one is launched.
-struct TileCfg { int bm, bn, per_cu; float eff; };
-constexpr TileCfg kTiles[] = {
-    {128, 384, 1, 1.00f},   // 0: 2x2 waves (64x192 each), BK 64, 2 stages, 128 KB LDS
-    {128, 288, 1, 1.00f},   // 1: 4x1 waves (32x288 each), BK 64, 3 stages, 156 KB LDS
-    {128, 128, 2, 0.80f},   // 2: 2x2 waves, BK 64, 2 stages, 64 KB LDS
-    {128, 96, 1, 0.70f},    // 3: 4x1 waves, BK 64, 4 stages, 112 KB LDS
-    {128, 64, 3, 0.55f},    // 4: 2x2 waves, BK 64, 2 stages, 48 KB LDS
-    {64, 64, 4, 0.40f},     // 5: 2x2 waves, BK 64, 2 stages, 32 KB LDS
-    {256, 256, 1, 0.00f},   // 6: 8 waves 2x4 (128x64 each), BK 32, 4 stages, 128 KB LDS (shared-GPU mode or forced)
-    {256, 256, 1, 0.00f},   // 7: as 6 on v_mfma_f32_16x16x32_f16, fragments one K tile ahead (4096^3: 1010 TFLOP/s); forced only
-    {128, 128, 2, 0.00f},   // 8: 2x2 waves on 16x16x32, BK 32, 4 stages, 64 KB LDS (forced only until measured)
-    {256, 256, 1, 1.60f},   // 9: ping-pong kernel (gemm_pp_kernel): 8 waves in two groups one barrier apart, BK 64
-                            //    (4096^3: 1300 TFLOP/s at the 1.4 GHz the chip holds under that load)
-    {128, 256, 1, 0.00f},   // 10: 128 x 256 ping-pong kernel (gemm_pp128_kernel), one read slot + one MFMA slot per K tile
-    {64, 256, 1, 0.00f},    // 11: the same kernel with 64-row tiles: twice the workgroups for a pass that has the GPU to itself
-};
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
-
-// GemmArgs::shared_gpu -- with several execution lanes the GPU is shared between kernels of different images: tiles
-// that leave room for a second workgroup on the CU (<= 64 KB LDS) let those kernels overlap, which is worth more
-// than the better isolated efficiency of the one-workgroup-per-CU tiles (measured: +8 % images/s).  It is a property
-// of the caller (SamModel knows how many lanes share its device), not process state.
-bool gemm_tile_fits(const GemmArgs& a, int tile) {
-    if (tile < 0 || tile >= kNumTiles) return false;
-    const TileCfg& t = kTiles[tile];
-    if ((a.out_l || a.resid_h) && !(tile >= 9 && tile <= 11)) return false;      // f16-pair stream: ping-pong epilogue only
-    if (tile >= 9 && tile <= 11 && a.ln_stats && a.ln_groups > kPPStatGroups) return false;   // room for the raw partials
-    return a.M % t.bm == 0 && a.N % t.bn == 0 && !((a.resid || a.resid_h) && a.resid_mod % t.bm != 0);
-}
-
-int gemm_pick_tile(const GemmArgs& a) {
-    if (a.tile >= 0) return gemm_tile_fits(a, a.tile) ? a.tile : -1;     // chosen earlier (pick once, use twice) or forced
-    const int forced = -1;
-    int best = -1;
-    float best_score = -1.f;
-    const int unit = (a.unit_rows > 0 && a.M % a.unit_rows == 0) ? a.unit_rows : a.M;   // rows the choice is made for
-    // a residual that wraps (row m % resid_mod) must wrap on tile boundaries: the epilogue adds row offsets to the
-    // tile's first residual row without a modulo per element
-    auto wraps_inside = [&](int bm) { return (a.resid || a.resid_h) && a.resid_mod % bm != 0; };
-    const bool shared = a.shared_gpu;
-    // 256x256 workgroups use a CU about 2.5x better than 128x128 ones (LDS fill rate per FLOP); with other lanes on
-    // the remaining CUs that is worth having even when they cover a quarter of the chip (ViT-H proj / fc2: 80
-    // workgroups, +2 % images/s; at 48, ViT-B proj / fc2, the longer kernel costs more than it frees)
-    if (shared && forced < 0 && unit % 256 == 0 && a.N % 256 == 0 &&
-        (unit / 256) * (a.N / 256) >= 64 && !wraps_inside(256)) {
-        // one image with the GPU to itself and fewer than half the CUs covered (ViT-H's proj / fc2: 80 tiles): the
-        // 128-row tiles double the workgroups (160); same bits for a stream writer (not for a LayerNorm-folded consumer)
-        if (a.alone && !a.ln_stats && a.M == unit && (unit / 256) * (a.N / 256) < 128 && (unit / 128) * (a.N / 256) <= 256 &&
-            !wraps_inside(128))
-            return 10;
-        return 9;
-    }
-    // The same with the rows of a whole BATCHED pass (several images stacked in M): two images give ViT-B's proj / fc2
-    // 96 tiles of 256 x 256.  Tiles 9 and 10 compute the same bits (BN = 256, the same MFMA, K order, epilogue
-    // arithmetic and 64-column statistics groups), so the result does not depend on which one a pass uses -- the
-    // batch-equals-single tests assert it.
-    // (only where a single unit would run tile 10: the other tiles use a different MFMA shape, i.e. another summation order)
-    // too few 256 x 256 tiles (ViT-B proj / fc2: 48): the 128 x 256 ping-pong kernel doubles them
-#ifdef DLIMG_TUNING     // A/B switches of the tuning build only; the product's choice is not steerable from outside
-    static const bool use_pp128 = [] { const char* e = std::getenv("DLIMGEDIT_GEMM_PP128"); return !e || std::atoi(e) != 0; }();
-    static const bool batch_pp = [] { const char* e = std::getenv("DLIMGEDIT_GEMM_BATCH_PP"); return !e || std::atoi(e) != 0; }();
-    // r06 A/B (the form it proposes): proj -- the stream writer with K = N -- on the 128-row tile, whose
-    // 64 spare registers take the residual before the K loop, while fc2 keeps the 256-row tile
-    static const bool proj128 = [] { const char* e = std::getenv("DLIMGEDIT_GEMM_PROJ128"); return e && std::atoi(e) != 0; }();
-#else
-    constexpr bool use_pp128 = true, batch_pp = true, proj128 = false;
-#endif
-    if (use_pp128 && shared && forced < 0 && unit % 128 == 0 && a.N % 256 == 0 && (unit / 128) * (a.N / 256) >= 64 &&
-        !wraps_inside(128)) {
-        // (not for a LayerNorm-folded consumer: its row statistics are merged in an order that depends on the tile height
-        // -- RowStats, threads per row -- so a consumer that lands in this branch keeps tile 10 whatever the pass looks like;
-        // ViT-B / L / H consumers never do: their N gives >= 64 tiles of 256 x 256)
-        if (a.ln_stats) return 10;
-        if (proj128 && a.resid_h && a.K == a.N) return 10;
-        if (batch_pp && a.M % 256 == 0 && (a.M / 256) * (a.N / 256) >= 96 && !wraps_inside(256)) return 9;
-        // one image with the GPU to itself: 64-row tiles while they still fit the chip in one round (ViT-B's patch / proj /
-        // fc2: 96 -> 192 workgroups; ViT-H's 160 would become 320, more than one round: stays)
-        if (a.alone && a.M == unit && unit % 64 == 0 && (unit / 64) * (a.N / 256) <= 256 && !wraps_inside(64)) return 11;
-        return 10;
-    }
-    for (int i = 0; i < kNumTiles; ++i) {
-        const TileCfg& t = kTiles[i];
-        if (unit % t.bm || a.N % t.bn || wraps_inside(t.bm) || !gemm_tile_fits(a, i)) continue;
-        if (i == forced) return i;
-        if (shared && forced < 0) {
-            // shared GPU: other lanes fill the CUs this launch leaves free, so the only question is operand
-            // traffic per FLOP -- the 256x256 tile (128 FLOP/B) whenever it yields enough workgroups,
-            // otherwise the tiles that can share a CU
-            if (t.per_cu < 2) continue;
-        }
-        const float eff = t.eff;
-        const int blocks = (unit / t.bm) * (a.N / t.bn);
-        const int slots = 256 * t.per_cu;
-        const int rounds = (blocks + slots - 1) / slots;
-        const float score = eff * (float)blocks / (float)(rounds * slots);
-        if (score > best_score) { best_score = score; best = i; }
-    }
-    return best;
-}
-
-int gemm_choose_tile(GemmArgs& a) {
-    if (const char* err = gemm_check(a)) throw_error(err);
-    if (!gemm_tile_fits(a, a.tile)) a.tile = -1;      // a tile set beforehand (test hooks) stays if it can run the problem
-    a.tile = gemm_pick_tile(a);
-    if (a.tile < 0) throw_error("gemm: no tile configuration fits this shape");
-    return kTiles[a.tile].bn;
-}
-
 void gemm(const GemmArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     if (const char* err = gemm_check(a)) throw_error(err);
-    const Timing t{start, stop};
-    const int tile = gemm_pick_tile(a);
-    if ((a.out_l || a.resid_h) && !(tile >= 9 && tile <= 11)) throw_error("gemm: the f16-pair stream needs a ping-pong tile (N % 256 == 0, shared GPU)");
-    switch (tile) {
-    case 0: return launch<128, 384, 2, 2, 64, 2, 1>(a, s, t);
-    case 1: return launch<128, 288, 4, 1, 64, 3, 1>(a, s, t);
-    case 2: return launch<128, 128, 2, 2, 64, 2, 4>(a, s, t);
-    case 3: return launch<128, 96, 4, 1, 64, 4, 1>(a, s, t);
-    case 4: return launch<128, 64, 2, 2, 64, 2, 3>(a, s, t);
-    case 5: return launch<64, 64, 2, 2, 64, 2, 4>(a, s, t);
-    case 6: return launch<256, 256, 2, 4, 32, 4, 2>(a, s, t);
-    case 7: return launch16<256, 256, 2, 4, 4, 2>(a, s, t);
-    case 8: return launch16<128, 128, 2, 2, 4, 2>(a, s, t);
-    case 9: return launch_pp(a, s, t);
-    case 10: return launch_pp128<128>(a, s, t);
-    case 11: return launch_pp128<64>(a, s, t);
-    default: throw_error("gemm: no tile configuration fits this shape");
-    }
+    const int tile = gemm_pick_tile(a);          // fits the problem (gemm_plan.cpp), or -1
+    if (tile < 0) gemm_no_tile(a);
+    kLaunchers[tile](a, s, Timing{start, stop});
 }
 
 }  // namespace k

@@ -1,6 +1,6 @@
 // gemm_f16_kernel (v_mfma_f32_32x32x16_f16, K tile 64 or 32, 4 or 8 waves) with its operand staging, folded-LayerNorm
 // helpers and epilogue: textually included by gemm.hip (every tile configuration) and by decoder.hip (one configuration,
-// inside a launch of its own).  Expects device_common.hpp and kernels.hpp; lives in the including file's anonymous namespace.
+// inside a launch of its own).  Expects device_common.hpp and gemm_plan.hpp; lives in the including file's anonymous namespace.
 // LDS rows hold BKT halves (128 or 64 bytes).  The 16-byte chunk index is XOR-swizzled with row bits so that
 // the 16 rows a ds_read_b128 lane group touches land on 16 different 16-byte slots of the 256-byte bank row.
 template <int BKT> DLIMG_DEVICE int swz(int row) { return BKT == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
@@ -45,8 +45,7 @@ enum { EPI_PLAIN = 0, EPI_NORM = 1, EPI_STATS = 2 };
 //     first operand tiles are in flight, and the epilogue applies  y = rstd_m * (acc - mean_m * colsum_n) + bias'_n .
 // No atomics, fixed summation order: results do not depend on timing.  Nothing is added to the MFMA loops (VALU work
 // there costs the GEMM 10-20 %, measured).
-constexpr int kStatRegs = 12;                    // partials per lane: N/BN <= 12 * (threads per row)
-
+// (kStatRegs, partials per lane: gemm_plan.hpp)
 template <int BM, int NTHREADS, int EPI>
 struct RowStats {
     static constexpr int TPR = NTHREADS / BM;    // adjacent lanes that share a row

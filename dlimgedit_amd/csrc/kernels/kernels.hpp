@@ -73,7 +73,7 @@ struct GemmArgs {
     // needs the tile width beforehand (stats_out layout) and the launch agree by construction.
     bool shared_gpu = false;
     // alone: the pass this GEMM belongs to has the GPU to itself (no other lane has work in flight: a synchronous caller).
-    // A one-image launch may then use tiles that double its workgroups at a worse cost per FLOP (gemm.hip, tile 11);
+    // A one-image launch may then use tiles that double its workgroups at a worse cost per FLOP (gemm_plan.hpp, tile 11);
     // the bits do not depend on it.
     bool alone = false;
     int tile = -1;
@@ -85,7 +85,8 @@ struct GemmArgs {
     unsigned long long* stamps = nullptr;
 };
 const char* gemm_check(const GemmArgs&);
-bool gemm_tile_fits(const GemmArgs&, int tile);   // may `tile` (index into gemm.hip's table) run this problem?
+bool gemm_tile_fits(const GemmArgs&, int tile);   // may `tile` (index into k::kGemmTiles, gemm_plan.hpp) run this problem?
+int gemm_pick_tile(const GemmArgs&);          // the tile gemm() launches: a.tile if set (-1 unless it fits), else the choice; -1: none fits
 int gemm_choose_tile(GemmArgs&);              // sets a.tile; returns BN (columns per tile) of that configuration
 // start/stop (both or neither): events attached to the kernel's own dispatch (hipExtLaunchKernelGGL): their elapsed time
 // is the kernel's execution time as a profiler reports it, without the marker packets an hipEventRecord pair adds.

@@ -1,4 +1,5 @@
 #include "sam_model.hpp"
+#include "gemm_plan.hpp"
 #include "image_memory.hpp"
 #include "mask_pieces.hpp"
 
@@ -260,7 +261,7 @@ SamWeights::SamWeights(std::string const& weight_path, int device_index) : devic
         k::GemmArgs g;
         g.A = pe_h.get(); g.lda = 256; g.W = l.w.get(); g.ldw = 256;
         g.out_f32 = dst.get(); g.ldc32 = l.out; g.M = kTokens; g.N = with_pos; g.K = 256;
-        g.unit_rows = kTokens;
+        SamModel::plan_inputs(g, /*shared_gpu*/ false, /*alone*/ false);     // a load has the stream to itself
         k::gemm(g, stream_);
     };
     ld.f32("dec.iou_token", {256}, iou_token_);
@@ -467,9 +468,7 @@ template <typename F> void SamModel::timed(Stage st, double work, F&& launch) {
 
 void SamModel::gemm(k::GemmArgs const& args, Stage shape) {
     k::GemmArgs a = args;
-    a.shared_gpu = shared_gpu_;
-    a.alone = alone_;
-    a.unit_rows = kTokens;
+    plan_inputs(a, shared_gpu_, alone_);
     if (!profiling_) {
         k::gemm(a, stream_);
         return;
@@ -555,7 +554,7 @@ void SamModel::reserve_encoder(int batch) {
     if (split_stream_) xlo_.reserve(M * D);
     else x_.reserve(M * D);
     xn_.reserve(M * D);
-    xstat_.reserve(M * 24 * 2);              // at most 24 tile column blocks per row (kernels/gemm.hip)
+    xstat_.reserve(M * k::kGemmMaxStatGroups * 2);   // (sum, M2) per tile column block and row
     qkv_.reserve(M * 3 * D);
     att_.reserve(M * std::max<size_t>(D, kEmbedDim));
     hid_.reserve(M * wide);
@@ -839,9 +838,7 @@ void SamModel::encode(int batch, float* const* emb_dst) {
         else { a.out_f32 = x_.get(); a.ldc32 = D; }
         if (fused) {
             a.out_h = xn_.get(); a.ldc16 = D; a.stats_out = xstat_.get();
-            a.shared_gpu = shared_gpu_;
-            a.alone = alone_;
-            a.unit_rows = kTokens;
+            plan_inputs(a, shared_gpu_, alone_);
             stat_groups = D / k::gemm_choose_tile(a);    // the launch below uses exactly this tile (a.tile)
         }
     };
@@ -1026,8 +1023,7 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             g.A = keys_h_.get(); g.lda = 256; g.W = l.w.get(); g.ldw = 256; g.bias = l.b.get();
             g.resid = pos.get(); g.ldr = l.out; g.resid_mod = kTokens;
             g.out_h = kqv_h_.get(); g.ldc16 = l.out; g.M = M; g.N = l.out; g.K = 256;
-            g.shared_gpu = shared_gpu_;
-            g.unit_rows = kTokens;
+            plan_inputs(g, shared_gpu_, /*alone*/ false);        // decodes run beside whatever the other lanes do
             return g;
         };
         auto img_gemm = [&](LinearH const& l, DeviceBuffer<float> const& pos) { k::gemm(img_gemm_args(l, pos), s); };

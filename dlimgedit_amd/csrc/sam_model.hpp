@@ -117,7 +117,7 @@ struct StageStats {
 // enqueues (encode, decode, mask transfer).  A lane that starts an encoder pass asks whether every OTHER lane's marker has
 // been reached: then the pass has the GPU to itself -- the situation of a synchronous caller of slots 3 / 4, which is what
 // every existing user of the reference is (/root/reference/src/include/dlimgedit/detail/dlimgedit.impl.hpp:70-116) -- and
-// its one-image GEMMs may trade CU time for latency (kernels/gemm.hip, tile 11).  hipEventQuery on an event another
+// its one-image GEMMs may trade CU time for latency (gemm_plan.cpp, tile 11).  hipEventQuery on an event another
 // thread is re-recording is allowed; a stale answer only costs or gains a tile choice, never a result (same bits).
 class LaneBoard {
   public:
@@ -262,6 +262,10 @@ class SamModel {
     void wait_and_recycle(hipEvent_t e);      // no mutex needed
     bool poll_and_recycle(hipEvent_t e);      // no mutex needed: true (and the event is taken back) once it has completed
 
+    // What the GEMM planner (gemm_plan.cpp) is told about the caller, for every GEMM of the model: whether other lanes share
+    // the device, whether the pass has it to itself, and the rows of one image.
+    static void plan_inputs(k::GemmArgs& a, bool shared_gpu, bool alone) { a.shared_gpu = shared_gpu; a.alone = alone; a.unit_rows = kTokens; }
+
     void set_profiling(bool on);
     StageStats take_stats();
 
@@ -275,7 +279,7 @@ class SamModel {
     hipEvent_t take_event();
 
     int device_ = 0;
-    bool shared_gpu_ = false;            // other lanes run on this device too (GEMM tile choice, kernels/gemm.hip)
+    bool shared_gpu_ = false;            // other lanes run on this device too (GEMM tile choice, gemm_plan.cpp)
     std::shared_ptr<LaneBoard> board_;   // activity of the sibling lanes (null: a lane on its own)
     int lane_index_ = 0;
     bool alone_ = false;                 // the encoder pass being enqueued found every other lane idle (set by encode())

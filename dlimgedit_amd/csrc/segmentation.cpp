@@ -265,7 +265,7 @@ void SegmentationImpl::process_batch(EnvironmentImpl& env, SegmentationImpl* con
     }
     (void)G;
     static const bool trace = std::getenv("DLIMGEDIT_TIMING") != nullptr;     // diagnostic: host time of the two phases
-    // Images per batched encoder pass.  Results do not depend on it (kernels/gemm.hip: the tiles a pass may use compute
+    // Images per batched encoder pass.  Results do not depend on it (gemm_plan.cpp: the tiles a pass may use compute
     // the same bits); throughput does: every lane should get a pass, and passes of two or more images run the N = 768
     // GEMMs on 256 x 256 tiles (8 images through one host thread, ViT-B: 601 images/s as 2 x 4, 649 as 8 x 1, 674 as
     // 4 x 2).  Default: the GPU's share spread over its lanes, at most 4 per pass -- unless other threads have batch calls

@@ -3,6 +3,7 @@
 // `hbm_kernels` leg.  NOT part of the product library: python -m dlimgedit_amd.build links this file into
 // lib/libdlimgedit_test.so (same objects as the product plus this one) and into the tuning library only.
 #include "ext_common.hpp"
+#include "gemm_plan.hpp"
 #include "step_queue.hpp"
 #include "mask_pieces.hpp"
 #include "resize_tables.hpp"
@@ -21,7 +22,7 @@ namespace {
 
 using namespace extapi;
 
-// dlimg_amd_test_force_gemm_tile() forces a tile configuration of kernels/gemm.hip in the single-kernel hooks below
+// dlimg_amd_test_force_gemm_tile() forces a tile configuration (gemm_plan.hpp) in the single-kernel hooks below
 // wherever it fits the problem.  An explicit call on this library's own state: nothing can steer the product's tile choice.
 std::atomic<int> g_forced_test_tile{-1};
 std::atomic<int> g_forced_consumer_tile{-1};     // LayerNorm-folded consumers only; -1: as g_forced_test_tile
@@ -246,7 +247,7 @@ DLIMG_API int dlimg_amd_test_gemm_ln(int M, int D, int K1, int N, uint16_t const
         Upload<half_t> w1(reinterpret_cast<half_t const*>(W1), (size_t)D * K1);
         Upload<half_t> wg(reinterpret_cast<half_t const*>(Wg), (size_t)N * D);
         Upload<float> b1(bias1, bias1 ? D : 0), r(resid, resid ? (size_t)M * D : 0), cs(colsum, N), b2(bias2, bias2 ? N : 0);
-        DeviceBuffer<float> x((size_t)M * D), y((size_t)M * N), stats((size_t)M * 24 * 2);
+        DeviceBuffer<float> x((size_t)M * D), y((size_t)M * N), stats((size_t)M * k::kGemmMaxStatGroups * 2);
         DeviceBuffer<half_t> xh((size_t)M * D);
         k::GemmArgs g;      // producer: writes the stream, its f16 copy and the per-tile row statistics
         g.A = a1.get(); g.lda = K1; g.W = w1.get(); g.ldw = K1; g.bias = bias1 ? b1.get() : nullptr;
@@ -271,7 +272,9 @@ DLIMG_API int dlimg_amd_test_gemm_ln(int M, int D, int K1, int N, uint16_t const
 
 // One stream-writing GEMM of the encoder, x = A.W^T + bias + resid with the per-tile row statistics, in either
 // representation of the stream: fp32 + f16 copy (pair == 0: resid_hi / resid_lo are summed to the fp32 residual on the host
-// side of the kernel, out_x and out_hi are written) or the f16 pair (pair == 1: out_hi / out_lo).  stats: M * 24 * 2 floats.
+// side of the kernel, out_x and out_hi are written) or the f16 pair (pair == 1: out_hi / out_lo).  stats: M * k::kGemmMaxStatGroups * 2 floats
+// (gemm_plan.hpp); api.py's ext.test_gemm_stream allocates M * 48.
+static_assert(k::kGemmMaxStatGroups * 2 == 48, "ext.test_gemm_stream (api.py) sizes the statistics array with this number");
 DLIMG_API int dlimg_amd_test_gemm_stream(int M, int D, int K, uint16_t const* A, uint16_t const* W, float const* bias,
                                          uint16_t const* resid_hi, uint16_t const* resid_lo, int pair, float* out_x,
                                          uint16_t* out_hi, uint16_t* out_lo, float* out_stats) {
@@ -290,9 +293,9 @@ DLIMG_API int dlimg_amd_test_gemm_stream(int M, int D, int K, uint16_t const* A,
         for (size_t i = 0; i < sum.size(); ++i)
             sum[i] = (float)reinterpret_cast<half_t const*>(resid_hi)[i] + (float)reinterpret_cast<half_t const*>(resid_lo)[i];
         Upload<float> r(sum.data(), sum.size());
-        DeviceBuffer<float> x(pair ? 0 : n), stats((size_t)M * 24 * 2);
+        DeviceBuffer<float> x(pair ? 0 : n), stats((size_t)M * k::kGemmMaxStatGroups * 2);
         DeviceBuffer<half_t> hi(n), lo(pair ? n : 0);
-        HIP_CHECK(hipMemset(stats.get(), 0, (size_t)M * 24 * 2 * sizeof(float)));
+        HIP_CHECK(hipMemset(stats.get(), 0, (size_t)M * k::kGemmMaxStatGroups * 2 * sizeof(float)));
         k::GemmArgs g;
         g.A = a.get(); g.lda = K; g.W = w.get(); g.ldw = K; g.bias = bias ? b.get() : nullptr; g.resid_mod = M;
         if (resid_hi && pair) { g.resid_h = rh.get(); g.resid_l = rl.get(); g.ldrs = D; }
@@ -307,7 +310,7 @@ DLIMG_API int dlimg_amd_test_gemm_stream(int M, int D, int K, uint16_t const* A,
         download(out_x, x.get(), pair ? 0 : n);
         download(reinterpret_cast<half_t*>(out_hi), hi.get(), n);
         download(reinterpret_cast<half_t*>(out_lo), lo.get(), pair ? n : 0);
-        download(out_stats, stats.get(), (size_t)M * 24 * 2);
+        download(out_stats, stats.get(), (size_t)M * k::kGemmMaxStatGroups * 2);
     });
 }
 
@@ -604,14 +607,14 @@ DLIMG_API int dlimg_amd_bench_gemm_stamps(int M, int N, int K, int act, int flav
             HIP_CHECK(hipMemset(pair_in.get(), 0, (size_t)M * N * 4));
             g.bias = bias.get(); g.resid_h = pair_in.get(); g.resid_l = pair_in.get() + (size_t)M * N; g.ldrs = N; g.resid_mod = M;
             g.out_l = pair_out.get();
-            if (flavour == 5) { stats.reserve((size_t)M * 24 * 2); g.stats_out = stats.get(); }
+            if (flavour == 5) { stats.reserve((size_t)M * k::kGemmMaxStatGroups * 2); g.stats_out = stats.get(); }
         } else if (flavour >= 2) {
             o32.reserve((size_t)M * N);
             HIP_CHECK(hipMemset(o32.get(), 0, (size_t)M * N * 4));
             g.bias = bias.get(); g.resid = o32.get(); g.ldr = N; g.resid_mod = M; g.out_f32 = o32.get(); g.ldc32 = N;
             g.out_h = nullptr;
             if (flavour == 3) {
-                stats.reserve((size_t)M * 24 * 2);
+                stats.reserve((size_t)M * k::kGemmMaxStatGroups * 2);
                 g.out_h = o.get(); g.stats_out = stats.get();
             }
         }
@@ -641,7 +644,7 @@ DLIMG_API int dlimg_amd_bench_gemm_stamps(int M, int N, int K, int act, int flav
                 HIP_CHECK(hipMemset(outs32[i].get(), 0, (size_t)M * N * 4));
                 gs[i].out_f32 = outs32[i].get(); gs[i].resid = outs32[i].get();
             }
-            if (g.stats_out) { stat_bufs[i].reserve((size_t)M * 24 * 2); gs[i].stats_out = stat_bufs[i].get(); }
+            if (g.stats_out) { stat_bufs[i].reserve((size_t)M * k::kGemmMaxStatGroups * 2); gs[i].stats_out = stat_bufs[i].get(); }
         }
         hipEvent_t e0, e1;
         HIP_CHECK(hipEventCreate(&e0));

@@ -1,7 +1,8 @@
 // ASan + UBSan harness for the pure host planners (tests/test_sanitizers.py): csrc/step_queue.hpp (which lane takes which
 // requests), csrc/mask_pieces.hpp (how a batch of masks is cut into transfer pieces) and csrc/resize_tables.cpp (the
-// contributor tables the resize kernels index with) on a few hundred thousand random inputs, with the invariants the
-// callers rely on checked on every one.
+// contributor tables the resize kernels index with) and csrc/gemm_plan.cpp (which tile configuration runs a GEMM) on a few
+// hundred thousand random inputs, with the invariants the callers rely on checked on every one.
+#include "gemm_plan.hpp"
 #include "mask_pieces.hpp"
 #include "resize_tables.hpp"
 #include "step_queue.hpp"
@@ -19,7 +20,113 @@ static uint32_t rnd(uint32_t n) {
     return (uint32_t)((rng_state >> 11) % (n ? n : 1));
 }
 
+struct PlanError { const char* msg; };
+namespace dlimg { void throw_error(const char* msg) { throw PlanError{msg}; } }
+
+// csrc/gemm_plan.cpp: valid and invalid GemmArgs (the planner reads addresses for their alignment only).  What gemm.hip's
+// launchers rely on: a picked tile fits, and a tile that fits divides the problem, takes the f16-pair stream only on a
+// ping-pong kernel and has room for the consumer's statistic groups.  What the batch-equals-single tests rely on: a batch
+// of units runs the tile of one unit, or -- not for a LayerNorm-folded consumer -- another ping-pong tile (same bits).
+static bool is_pingpong(int tile) { return tile >= 0 && k::kGemmTiles[tile].family == k::TileFamily::pingpong; }
+static const char* check_pick(k::GemmArgs const& a, int* picked) {
+    const int t = *picked = k::gemm_pick_tile(a);
+    if (t != -1 && !k::gemm_tile_fits(a, t)) return "picked a tile that does not fit";
+    if (a.tile >= 0 && t != (k::gemm_tile_fits(a, a.tile) ? a.tile : -1)) return "a preset tile is returned exactly when it fits";
+    return nullptr;
+}
+static const char* fuzz_gemm_plan_once(int* valid) {
+    alignas(16) static char mem[32];
+    auto addr = [&](int odds_bad) { return mem + (rnd(odds_bad) ? 0 : 1 + rnd(15)); };
+    auto dim = [&] { const int d = 64 * (1 + (int)rnd(80)); return rnd(12) ? d : rnd(2) ? d + 1 + (int)rnd(63) : (int)rnd(3) - 1; };
+    k::GemmArgs a;
+    a.unit_rows = rnd(3) ? 64 * (1 + (int)rnd(64)) : rnd(3) ? 0 : (int)rnd(5000);
+    a.M = (a.unit_rows > 0 && rnd(2)) ? a.unit_rows : dim();
+    a.N = rnd(3) ? 256 * (1 + (int)rnd(20)) : dim();
+    a.ln_groups = (int)rnd(31);
+    a.K = (a.ln_groups > 0 && rnd(4)) ? a.ln_groups * 64 * (1 + (int)rnd(4)) : dim();
+    a.A = reinterpret_cast<half_t*>(addr(40)); a.W = reinterpret_cast<half_t*>(addr(40));
+    a.lda = rnd(20) ? a.K + 8 * (int)rnd(3) : a.K - 8 + (int)rnd(12);
+    a.ldw = rnd(20) ? a.K + 8 * (int)rnd(3) : a.K - 8 + (int)rnd(12);
+    if (rnd(2)) a.bias = reinterpret_cast<float*>(addr(40));
+    const int resid = (int)rnd(rnd(20) ? 3 : 5);         // none, fp32, pair; rarely half a pair, or both kinds
+    if (resid == 1 || resid == 4) { a.resid = reinterpret_cast<float*>(addr(40)); a.ldr = a.N + (rnd(20) ? 0 : 1 + (int)rnd(3)); }
+    if (resid >= 2) { a.resid_h = reinterpret_cast<half_t*>(addr(40)); a.ldrs = a.N + (rnd(20) ? 0 : 1 + (int)rnd(3)); }
+    if (resid == 2 || resid == 4) a.resid_l = reinterpret_cast<half_t*>(addr(40));
+    const uint32_t mod = rnd(8);
+    a.resid_mod = mod < 3 ? a.M : mod < 5 ? a.unit_rows : mod < 7 ? 64 * (1 + (int)rnd(8)) : (int)rnd(200) - 10;
+    const int out = (int)rnd(rnd(20) ? 4 : 6);           // fp32, f16, both, pair; rarely none, or a pair beside fp32
+    if (out == 0 || out == 2 || out == 5) { a.out_f32 = reinterpret_cast<float*>(addr(40)); a.ldc32 = a.N + (rnd(20) ? 0 : 2); }
+    if (out == 1 || out == 2 || out == 3 || out == 5) { a.out_h = reinterpret_cast<half_t*>(addr(40)); a.ldc16 = a.N + (rnd(20) ? 0 : 2); }
+    if (out == 3 || out == 5) a.out_l = reinterpret_cast<half_t*>(addr(40));
+    if (!rnd(4)) a.stats_out = reinterpret_cast<float*>(mem);
+    if (!rnd(3)) { a.ln_stats = reinterpret_cast<float*>(mem); a.ln_colsum = rnd(30) ? reinterpret_cast<float*>(addr(40)) : nullptr; }
+    a.act = rnd(3) ? k::ACT_NONE : k::ACT_GELU;
+    a.shared_gpu = rnd(2) != 0; a.alone = rnd(2) != 0;
+    a.tile = rnd(4) ? -1 : (int)rnd(15) - 2;             // preset: -2 .. 12
+    if (k::gemm_check(a)) return nullptr;
+    ++*valid;
+    int picked;
+    if (const char* bad = check_pick(a, &picked)) return bad;
+    for (int t = -1; t <= k::kGemmNumTiles; ++t) {
+        if (!k::gemm_tile_fits(a, t)) continue;
+        if (t < 0 || t >= k::kGemmNumTiles) return "a tile outside the table fits";
+        k::GemmTile const& row = k::kGemmTiles[t];
+        if (a.M % row.bm || a.N % row.bn || ((a.resid || a.resid_h) && a.resid_mod % row.bm)) return "a tile that fits does not divide the problem";
+        if ((a.out_l || a.resid_h) && !(row.pair_stream && is_pingpong(t))) return "f16-pair stream on a tile without the ping-pong epilogue";
+        if (a.ln_stats && a.ln_groups > row.stat_groups) return "more statistic groups than the tile merges";
+    }
+    k::GemmArgs once = a;
+    try {
+        const int bn = k::gemm_choose_tile(once);
+        k::GemmArgs twice = once;
+        if (once.tile < 0 || bn != k::kGemmTiles[once.tile].bn || k::gemm_choose_tile(twice) != bn || twice.tile != once.tile)
+            return "gemm_choose_tile twice differs";
+        if (k::gemm_pick_tile(once) != once.tile) return "the launch would not use the chosen tile";
+    } catch (PlanError const&) {
+        k::GemmArgs free_choice = a;
+        if (!k::gemm_tile_fits(a, a.tile)) free_choice.tile = -1;
+        if (k::gemm_pick_tile(free_choice) != -1) return "gemm_choose_tile refuses a problem that has a tile";
+    }
+    if (a.tile < 0 && a.unit_rows > 0 && a.M == a.unit_rows) {           // one unit against a batch of them
+        k::GemmArgs batch = a;
+        batch.M = a.M * (2 + (int)rnd(7));
+        if ((a.resid || a.resid_h) && a.resid_mod == a.M && rnd(2)) batch.resid_mod = batch.M;      // the stream itself as residual
+        if (k::gemm_check(batch)) return "a batch of valid units is refused";
+        int batch_picked;
+        if (const char* bad = check_pick(batch, &batch_picked)) return bad;
+        if (batch_picked != picked && (a.ln_stats || !is_pingpong(picked) || !is_pingpong(batch_picked)))
+            return "a batch runs another tile than its units";
+    }
+    return nullptr;
+}
+static void print_gemm(k::GemmArgs const& a) {
+    std::printf("M %d N %d K %d resid %d/%d mod %d pair out %d stats %d ln %d groups %d shared %d alone %d unit %d tile %d\n", a.M, a.N, a.K,
+                a.resid != nullptr, a.resid_h != nullptr, a.resid_mod, a.out_l != nullptr, a.stats_out != nullptr, a.ln_stats != nullptr,
+                a.ln_groups, (int)a.shared_gpu, (int)a.alone, a.unit_rows, a.tile);
+}
+static bool fuzz_gemm_plan() {
+    int valid = 0;
+    for (int iter = 0; iter < 100000; ++iter)
+        if (const char* bad = fuzz_gemm_plan_once(&valid)) { std::printf("gemm plan: %s (iteration %d)\n", bad, iter); return false; }
+    if (valid < 30000) { std::printf("gemm plan: only %d of the random problems pass gemm_check\n", valid); return false; }
+    // A LayerNorm-folded consumer beside other lanes whose shape asks for a ping-pong tile (N % 256 == 0, >= 64 tiles) but
+    // whose producer left more groups than those kernels have LDS room for: any tile but a ping-pong one
+    alignas(16) static char mem[16];
+    for (int groups = kPPStatGroups + 1; groups <= k::kGemmMaxStatGroups; ++groups)
+        for (int variant = 0; variant < 8; ++variant) {
+            k::GemmArgs a;
+            a.A = a.W = reinterpret_cast<half_t*>(mem); a.out_h = reinterpret_cast<half_t*>(mem);
+            a.ln_stats = a.ln_colsum = reinterpret_cast<float*>(mem); a.ln_groups = groups;
+            a.unit_rows = 4096; a.M = (variant & 1) ? 8192 : 4096; a.N = (variant & 2) ? 1024 : 2304 + 256; a.K = groups * 64;
+            a.lda = a.ldw = a.K; a.ldc16 = a.N; a.shared_gpu = true; a.alone = (variant & 4) != 0;
+            const int t = k::gemm_check(a) ? -1 : k::gemm_pick_tile(a);
+            if (t < 0 || is_pingpong(t) || !k::gemm_tile_fits(a, t)) { std::printf("gemm plan: consumer with %d groups on tile %d\n", groups, t); print_gemm(a); return false; }
+        }
+    return true;
+}
+
 int main() {
+    if (!fuzz_gemm_plan()) return 1;
     for (int iter = 0; iter < 200000; ++iter) {
         StepQueueState st;
         const int lanes = 1 + (int)rnd(8);
