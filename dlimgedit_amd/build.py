@@ -53,6 +53,10 @@ SOURCES = [
     "image_memory.cpp",
     "jpeg_decode.cpp",
     "weights.cpp",
+    "lane_board.cpp",
+    "stage_clock.cpp",
+    "mask_transport.cpp",
+    "sam_weights.cpp",
     "sam_model.cpp",
     "environment.cpp",
     "segmentation.cpp",

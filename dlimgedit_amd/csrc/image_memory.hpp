@@ -4,7 +4,7 @@
 // consumer loaded from a file and the Image that Segmentation::compute_mask(point) returns both live in memory this library
 // chose.  Once a GPU environment exists in the process that memory is pinned (hipHostMalloc, kept in a free list by size):
 // process() then sends such an image to the GPU from where it lies, and the post-processing kernel writes such a mask where
-// the consumer will read it -- no staging copy on either side (csrc/sam_model.cpp: upload_image, enqueue_masks).
+// the consumer will read it -- no staging copy on either side (csrc/sam_model.cpp: upload_image; csrc/mask_transport.hpp).
 // Memory that came from anywhere else (a caller's own buffer) takes the staged path as before.
 #pragma once
 

@@ -1,0 +1,184 @@
+#include "mask_transport_exec.hpp"
+#include "image_memory.hpp"
+
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+
+namespace dlimg {
+
+namespace {
+
+constexpr double kLogitBytes = 256.0 * 256.0 * 4.0;     // what the kernel reads per mask: the low-resolution logits
+
+// Direct xGMI copies between two GPUs need peer access switched on once per direction (without it the runtime stages
+// the copy through host memory: still correct, slower).  Failures are not errors: the copy falls back by itself.
+void enable_peer_access(int from_device, int to_device) {
+    static std::mutex m;
+    static std::vector<std::pair<int, int>> done;
+    std::lock_guard<std::mutex> lock(m);
+    for (auto& d : done)
+        if (d.first == from_device && d.second == to_device) return;
+    done.emplace_back(from_device, to_device);
+    if (from_device == to_device) return;
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, from_device, to_device) == hipSuccess && can) {
+        (void)hipSetDevice(from_device);
+        if (hipDeviceEnablePeerAccess(to_device, 0) != hipSuccess) (void)hipGetLastError();
+    }
+    if (hipDeviceCanAccessPeer(&can, to_device, from_device) == hipSuccess && can) {
+        (void)hipSetDevice(to_device);
+        if (hipDeviceEnablePeerAccess(from_device, 0) != hipSuccess) (void)hipGetLastError();
+    }
+    (void)hipSetDevice(prev);
+}
+
+void fill_sizes(std::vector<size_t>& sizes, k::PostJob const* jobs, int count) {
+    sizes.resize(count > 0 ? count : 0);
+    for (int i = 0; i < count; ++i) sizes[i] = (size_t)jobs[i].out_w * jobs[i].out_h;
+}
+
+}  // namespace
+
+MaskTransport::~MaskTransport() {
+    for (auto& m : slots_) {
+        if (m->done) (void)hipEventDestroy(m->done);
+        for (auto e : m->piece_done) (void)hipEventDestroy(e);
+    }
+}
+
+MaskSlot& MaskTransport::acquire() {
+    {
+        std::lock_guard<std::mutex> lock(mutex_);
+        if (!free_.empty()) {
+            MaskSlot* s = free_.back();
+            free_.pop_back();
+            return *s;
+        }
+    }
+    // as many slots come into being as there are mask requests in flight on this lane at once
+    auto fresh = std::make_unique<MaskSlot>();
+    HIP_CHECK(hipSetDevice(device_));
+    HIP_CHECK(hipEventCreateWithFlags(&fresh->done, hipEventDisableTiming));
+    std::lock_guard<std::mutex> lock(mutex_);
+    slots_.push_back(std::move(fresh));
+    return *slots_.back();
+}
+
+void MaskTransport::release(MaskSlot& s) {
+    std::lock_guard<std::mutex> lock(mutex_);
+    free_.push_back(&s);
+}
+
+hipEvent_t MaskTransport::piece_event(MaskSlot& slot, int i) {
+    while ((int)slot.piece_done.size() <= i) {
+        hipEvent_t e = nullptr;
+        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        slot.piece_done.push_back(e);
+    }
+    return slot.piece_done[i];
+}
+
+// The plan of the slot, step by step, on the lane's stream; slot.done behind the last of them.
+void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device) {
+    MaskTransportPlan const& p = slot.plan;
+    // the slot is ours, and its previous user waited for the slot's event before letting go of it
+    slot.dev.reserve(p.reserve_device);
+    slot.pin.reserve(p.reserve_pinned);
+    uint8_t* const dev = slot.dev.get();
+    uint8_t* const pin = static_cast<uint8_t*>(slot.pin.get());
+    uint8_t* const staging = p.mode == MaskMode::direct ? pin : dev;
+    slot.kernel_jobs.assign(jobs, jobs + count);
+    for (int i = 0; i < count; ++i)
+        if (p.kernel_dst[i] != kCallersPointer) slot.kernel_jobs[i].dst = staging + p.kernel_dst[i];
+    if (p.mode == MaskMode::device_staged) enable_peer_access(device_, dst_device);
+    auto address = [&](MaskMem mem, size_t offset, int mask) -> uint8_t* {
+        switch (mem) {
+            case MaskMem::iou: return reinterpret_cast<uint8_t*>(const_cast<float*>(iou)) + offset;
+            case MaskMem::device: return dev + offset;
+            case MaskMem::pinned: return pin + offset;
+            default: return jobs[mask].dst + offset;
+        }
+    };
+    for (MaskStep const& s : p.steps) {
+        if (s.kind == MaskStep::launch) {
+            double bytes = 0;
+            for (int i = s.first; i < s.first + s.count; ++i) bytes += kLogitBytes + (double)slot.input.sizes[i];
+            clock_.timed(ST_POST, bytes, [&] { k::postprocess_masks(&slot.kernel_jobs[s.first], s.count, stream_); });
+        } else if (s.kind == MaskStep::event) {
+            HIP_CHECK(hipEventRecord(piece_event(slot, s.first), stream_));
+        } else if (s.to == MaskMem::peer) {
+            HIP_CHECK(hipMemcpyPeerAsync(address(s.to, s.to_offset, s.mask), dst_device, address(s.from, s.from_offset, s.mask), device_, s.bytes, stream_));
+        } else {
+            HIP_CHECK(hipMemcpyAsync(address(s.to, s.to_offset, s.mask), address(s.from, s.from_offset, s.mask), s.bytes,
+                                     s.to == MaskMem::device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream_));
+        }
+    }
+    HIP_CHECK(hipEventRecord(slot.done, stream_));
+}
+
+void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count) {
+    if (count <= 0) return;
+    // DLIMGEDIT_DIRECT_MASKS=0: measurement aid (always the copy path)
+    static const bool direct_allowed = [] { const char* e = std::getenv("DLIMGEDIT_DIRECT_MASKS"); return !e || std::atoi(e) != 0; }();
+    MaskTransportInput& in = slot.input;
+    fill_sizes(in.sizes, jobs, count);
+    in.iou_count = iou_count;
+    in.direct_allowed = direct_allowed;
+    in.others_idle = mask_mode_asks_idle(count, direct_allowed) && (!board_ || board_->others_idle(lane_index_));
+    // a destination in pinned image memory of the library (the Image the reference's wrapper allocates for the result
+    // through create_image).  Direct mode looks at every destination, staged mode only asks whether all of them are pinned:
+    // no lookup behind the first that is not
+    const bool every = mask_transport_is_direct(in);
+    in.dst_pinned.assign(count, 0);
+    for (int i = 0; i < count; ++i) {
+        in.dst_pinned[i] = image_memory_is_pinned(jobs[i].dst, in.sizes[i]);
+        if (!in.dst_pinned[i] && !every) break;
+    }
+    plan_mask_transport(in, slot.plan);
+    run(slot, jobs, count, iou, device_);
+    if (board_) board_->mark(lane_index_, stream_);
+}
+
+void MaskTransport::finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) {
+    if (count <= 0) return;
+    static const bool trace = std::getenv("DLIMGEDIT_TIMING") != nullptr;     // diagnostic: host time of the two phases
+    const auto t0 = std::chrono::steady_clock::now();
+    MaskTransportPlan const& p = slot.plan;
+    uint8_t const* pin = static_cast<uint8_t const*>(slot.pin.get());
+    // piece by piece: what has arrived is copied to the callers' buffers while the rest is still on its way
+    double waited_us = 0;
+    MaskCursor cursor;
+    size_t begin = 0;
+    for (size_t i = 0; i < p.piece_end.size(); ++i) {
+        const auto w0 = std::chrono::steady_clock::now();
+        HIP_CHECK(hipEventSynchronize(slot.piece_done[i]));
+        waited_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+        for (MaskCopy const& c : mask_copies_in_piece(slot.input.sizes, begin, p.piece_end[i], cursor))
+            if (!p.in_place[c.mask]) std::memcpy(jobs[c.mask].dst + c.mask_offset, pin + c.staging_offset, c.bytes);
+        begin = p.piece_end[i];
+    }
+    HIP_CHECK(hipEventSynchronize(slot.done));
+    const auto t1 = std::chrono::steady_clock::now();
+    if (iou_out && iou_count > 0) std::memcpy(iou_out, pin + p.iou_offset, (size_t)iou_count * sizeof(float));
+    if (trace)
+        std::fprintf(stderr, "finish_masks: %.1f us in all, %.1f us of them waiting for the %zu pieces (%zu bytes)\n",
+                     std::chrono::duration<double, std::micro>(t1 - t0).count(), waited_us, p.piece_end.size(), p.iou_offset);
+}
+
+void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device) {
+    if (count <= 0) return;
+    // test hook: take the staging + peer-copy path even when the destination is this lane's own GPU (a one-GPU box
+    // has no second device to copy to; the path is the same code, the copy degenerates to device-to-device)
+    const char* fp = std::getenv("DLIMGEDIT_FORCE_PEER_COPY");       // read per call: the tests switch it on and off
+    const bool force_peer = fp && std::atoi(fp) != 0;
+    fill_sizes(slot.input.sizes, jobs, count);
+    plan_mask_transport_device(slot.input.sizes, dst_device == device_ && !force_peer, slot.plan);
+    run(slot, jobs, count, nullptr, dst_device);
+}
+
+void MaskTransport::wait(MaskSlot& slot) { HIP_CHECK(hipEventSynchronize(slot.done)); }
+
+}  // namespace dlimg

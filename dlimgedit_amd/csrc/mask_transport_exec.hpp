@@ -1,0 +1,61 @@
+// MaskTransport: the mask slots of one execution lane and the executor of their plans (mask_transport.hpp).
+//   slot = acquire()                         any thread, no lock needed: a free slot (or a new one: never blocks), the
+//                                            caller's until release()
+//   enqueue(slot, jobs, n, iou, n_iou)       under the lane's mutex: plans the request and gives the plan's steps to the
+//                                            lane's stream -- kernel, copy commands, one event per piece, slot.done last
+//   finish(slot, jobs, n, iou_out, n_iou)    no lock: waits piece by piece and copies what the plan left in the slot's
+//                                            pinned buffer into jobs[i].dst (HOST pointers of out_w*out_h bytes) and iou_out
+//   enqueue_device / wait                    the same for destinations in DEVICE memory of any GPU; slot.done only
+// Contract: acquire / release are thread-safe (a mutex of the component's own around the free list, nothing else); a slot
+// has one user at a time, who waits for slot.done before letting go of it, so its buffers and its plan need no lock.  The
+// lane hands in what is the lane's: its stream and stage clock (used under the lane's mutex, as by the lane itself), its
+// board, and per request the IoU predictions of the last decode.  The component outlives every request it was given.
+#pragma once
+
+#include "kernels/kernels.hpp"
+#include "lane_board.hpp"
+#include "mask_transport.hpp"
+#include "stage_clock.hpp"
+
+namespace dlimg {
+
+struct MaskSlot {
+    DeviceBuffer<uint8_t> dev;
+    PinnedBuffer pin;
+    hipEvent_t done = nullptr;
+    std::vector<hipEvent_t> piece_done;     // one per piece of the largest plan so far
+    MaskTransportInput input;               // of the request the slot holds, kept for finish(); the vectors below are
+    MaskTransportPlan plan;                 // re-used from request to request like these
+    std::vector<k::PostJob> kernel_jobs;    // the caller's jobs with the destinations the plan gives the kernel
+};
+
+class MaskTransport {
+  public:
+    MaskTransport(int device, hipStream_t stream, StageClock& clock, LaneBoard* board, int lane_index)
+        : device_(device), stream_(stream), clock_(clock), board_(board), lane_index_(lane_index) {}
+    ~MaskTransport();
+    MaskTransport(MaskTransport const&) = delete;
+    MaskTransport& operator=(MaskTransport const&) = delete;
+
+    MaskSlot& acquire();
+    void release(MaskSlot& s);
+    void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count);
+    void finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
+    void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device);
+    void wait(MaskSlot& slot);
+
+  private:
+    hipEvent_t piece_event(MaskSlot& slot, int i);
+    void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device);
+
+    int device_;
+    hipStream_t stream_;
+    StageClock& clock_;
+    LaneBoard* board_;                      // null: a lane on its own
+    int lane_index_;
+    std::mutex mutex_;                      // guards the two lists, nothing else
+    std::vector<std::unique_ptr<MaskSlot>> slots_;      // all ever made (owned)
+    std::vector<MaskSlot*> free_;                       // those not handed out
+};
+
+}  // namespace dlimg

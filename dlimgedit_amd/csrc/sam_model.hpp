@@ -10,12 +10,15 @@
 #include "common.hpp"
 
 #include <dlimgedit/dlimgedit.h>
+#include "completion_events.hpp"
 #include "kernels/kernels.hpp"
+#include "lane_board.hpp"
+#include "mask_transport_exec.hpp"
 #include "resize_tables.hpp"
+#include "stage_clock.hpp"
 #include "weights.hpp"
 
 #include <array>
-#include <atomic>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -96,51 +99,10 @@ struct SamWeights {
 
 };
 
-// Stage clock for roofline accounting (HIP events on the executor's own stream).
-// ST_GEMM is the sum over all GEMM launches of the encoder; ST_GEMM_* split the same launches by kernel flavour (what
-// the by-grid table of a kernel trace tells apart): residual-stream writers with row statistics (patch / proj / fc2),
-// LayerNorm-folded consumers without / with GELU (qkv / fc1), everything else (neck).
-enum Stage { ST_PRE = 0, ST_GEMM, ST_LAYERNORM, ST_ATTN_WINDOW, ST_ATTN_GLOBAL, ST_ENC_OTHER, ST_DECODER, ST_POST,
-             ST_GEMM_STATS, ST_GEMM_NORM, ST_GEMM_NORM_GELU, ST_GEMM_OTHER,
-             // r06: the stream writers (ST_GEMM_STATS) once more by shape -- they share a kernel and a grid, so no profiler
-             // table can tell them apart, and proj (K = D: 152 FLOP per byte at ViT-B) sits on the other side of the ridge
-             // from fc2 (K = 4 D)
-             ST_GEMM_PATCH, ST_GEMM_PROJ, ST_GEMM_FC2, ST_COUNT };
-
-struct StageStats {
-    double ms[ST_COUNT] = {0};
-    double work[ST_COUNT] = {0};     // algorithmic FLOPs (MFMA stages) or bytes (HBM stages)
-    long launches[ST_COUNT] = {0};
-};
-
-// Which execution lanes of a GPU have work in flight: one marker event per lane, re-recorded behind everything the lane
-// enqueues (encode, decode, mask transfer).  A lane that starts an encoder pass asks whether every OTHER lane's marker has
-// been reached: then the pass has the GPU to itself -- the situation of a synchronous caller of slots 3 / 4, which is what
-// every existing user of the reference is (/root/reference/src/include/dlimgedit/detail/dlimgedit.impl.hpp:70-116) -- and
-// its one-image GEMMs may trade CU time for latency (gemm_plan.cpp, tile 11).  hipEventQuery on an event another
-// thread is re-recording is allowed; a stale answer only costs or gains a tile choice, never a result (same bits).
-class LaneBoard {
-  public:
-    LaneBoard(int device, int lanes);
-    ~LaneBoard();
-    LaneBoard(LaneBoard const&) = delete;
-    LaneBoard& operator=(LaneBoard const&) = delete;
-    void begin(int lane);                         // the lane starts enqueuing a pass: busy until the next mark() / end()
-    void end(int lane) noexcept;                  // (no event: for the error path of an enqueue)
-    void mark(int lane, hipStream_t stream);      // behind what the lane has just enqueued
-    bool others_idle(int lane) const;
-    // diagnostics: encoder passes of one image enqueued so far, and how many of them found every other lane idle
-    void count_pass(bool alone) { passes_.fetch_add(1, std::memory_order_relaxed); if (alone) alone_.fetch_add(1, std::memory_order_relaxed); }
-    long passes() const { return passes_.load(std::memory_order_relaxed); }
-    long alone_passes() const { return alone_.load(std::memory_order_relaxed); }
-
-  private:
-    std::atomic<long> passes_{0}, alone_{0};
-    std::vector<hipEvent_t> marker_;
-    std::unique_ptr<std::atomic<bool>[]> armed_;
-    std::unique_ptr<std::atomic<bool>[]> enqueuing_;
-};
-
+// One execution lane.  What is the lane's own here: the encoder, the decoder, image intake (staging ring, resize tables,
+// staged resizes) and the pass flags with DeferredPass.  The rest are components with contracts of their own, which the
+// methods below only forward to: StageClock (stage_clock.hpp; under mutex()), CompletionEvents (completion_events.hpp;
+// thread-safe) and MaskTransport (mask_transport_exec.hpp; slots thread-safe, enqueuing under mutex()).
 class SamModel {
   public:
     // One execution lane: own stream, workspaces and staging buffers over shared weights.  Several lanes
@@ -198,36 +160,17 @@ class SamModel {
     void decoder_state(float* out) const;
     float const* iou() const { return iou_.get(); }
 
-    // Post-process to host masks in two steps so that the wait happens outside mutex():
-    //   slot = acquire_mask_slot()               no mutex needed; a free staging slot (or a new one: never blocks),
-    //                                            the caller's until release_mask_slot
-    //   enqueue_masks(slot, jobs, n, n_iou)      under mutex(): kernel -> device staging -> pinned staging (async),
-    //                                            plus the first n_iou IoU predictions of the last decode()
-    //   finish_masks(slot, jobs, n, iou_out)     no mutex: waits for the slot's event, copies into jobs[i].dst (HOST
-    //                                            pointers of out_w*out_h bytes) and iou_out
-    struct MaskSlot {
-        DeviceBuffer<uint8_t> dev;
-        PinnedBuffer pin;
-        hipEvent_t done = nullptr;
-        size_t iou_offset = 0;
-        // masks whose destination is pinned image memory of the library (csrc/image_memory.hpp) and were written there by
-        // the kernel itself: finish_masks has nothing to copy for them
-        std::vector<char> in_place;
-        // the staging area travels to the host in a few pieces, each with its own event, so that the host copies piece i
-        // to the caller's buffers while piece i + 1 is still on the bus (enqueue_masks / finish_masks)
-        std::vector<hipEvent_t> piece_done;
-        std::vector<size_t> piece_end;
-    };
-    MaskSlot& acquire_mask_slot();
-    void release_mask_slot(MaskSlot& s);
-    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count);
-    void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
-    // Masks to DEVICE memory that may belong to ANOTHER GPU ("all masks on one device"): jobs[i].dst are
-    // pointers valid on HIP device dst_device.  Same device as this lane's: the kernel writes them directly.  Another
-    // device: the kernel writes the slot's staging memory and one hipMemcpyPeerAsync per mask moves it over xGMI.
-    // slot.done is recorded behind the last write; wait_masks() (no mutex needed) waits for it.
-    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device);
-    void wait_masks(MaskSlot& slot);
+    // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):
+    // acquire_mask_slot (no mutex needed), enqueue_masks with the first n_iou IoU predictions of the last decode() (under
+    // mutex()), finish_masks (no mutex), release_mask_slot.  enqueue_masks_device / wait_masks: jobs[i].dst are pointers
+    // valid on HIP device dst_device, which may be ANOTHER GPU ("all masks on one device").
+    using MaskSlot = dlimg::MaskSlot;
+    MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
+    void release_mask_slot(MaskSlot& s) { masks_.release(s); }
+    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count) { masks_.enqueue(slot, jobs, count, iou_.get(), iou_count); }
+    void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) { masks_.finish(slot, jobs, count, iou_out, iou_count); }
+    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device) { masks_.enqueue_device(slot, jobs, count, dst_device); }
+    void wait_masks(MaskSlot& slot) { masks_.wait(slot); }
     // Blocking convenience form of the three calls above (mutex() held throughout).
     void masks_to_host(k::PostJob const* jobs, int count);
     // Same kernel, but jobs[i].dst are DEVICE pointers and nothing is copied or waited for.
@@ -235,7 +178,7 @@ class SamModel {
 
     void synchronize();
     // Event recorded behind everything enqueued so far; wait for it WITHOUT mutex(), then give it back.
-    hipEvent_t completion();
+    hipEvent_t completion() { return done_events_.record(); }
     // Overflow report of the encoder pass enqueued last (valid under mutex(), right after encode()): an int in pinned host
     // memory that the pass sets to 1 when an activation left the f16 range somewhere in the image (an infinity or a NaN
     // reached the last LayerNorm of the neck).  Read it after the pass's completion event; slots are reused after
@@ -259,24 +202,21 @@ class SamModel {
     };
     // Under mutex(), right after encode(): completion() + last_pass_flag() of that pass as one object.
     std::shared_ptr<DeferredPass> defer_last_pass();
-    void wait_and_recycle(hipEvent_t e);      // no mutex needed
-    bool poll_and_recycle(hipEvent_t e);      // no mutex needed: true (and the event is taken back) once it has completed
+    void wait_and_recycle(hipEvent_t e) { done_events_.wait_and_recycle(e); }             // no mutex needed
+    bool poll_and_recycle(hipEvent_t e) { return done_events_.poll_and_recycle(e); }      // no mutex needed: true (and the event is taken back) once it has completed
 
     // What the GEMM planner (gemm_plan.cpp) is told about the caller, for every GEMM of the model: whether other lanes share
     // the device, whether the pass has it to itself, and the rows of one image.
     static void plan_inputs(k::GemmArgs& a, bool shared_gpu, bool alone) { a.shared_gpu = shared_gpu; a.alone = alone; a.unit_rows = kTokens; }
 
-    void set_profiling(bool on);
-    StageStats take_stats();
+    void set_profiling(bool on) { clock_.set_profiling(on); }
+    StageStats take_stats() { return clock_.take_stats(); }
 
   private:
     void reserve_encoder(int batch);
     void reserve_decoder(int count);
     void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
-    template <typename F> void timed(Stage st, double work, F&& launch);
-    void flush_events();
-    hipEvent_t take_event();
 
     int device_ = 0;
     bool shared_gpu_ = false;            // other lanes run on this device too (GEMM tile choice, gemm_plan.cpp)
@@ -349,21 +289,17 @@ class SamModel {
     DeviceBuffer<float> keys_, logits_, iou_, hyper_;
     DeviceBuffer<half_t> keys_h_, kqv_h_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
-    std::vector<std::unique_ptr<MaskSlot>> mask_slots_;     // all ever made (owned), guarded by done_mutex_
-    std::vector<MaskSlot*> mask_free_;                      // those not handed out, guarded by done_mutex_
 
-    // ---- profiling
-    bool profiling_ = false;
-    struct Pending { hipEvent_t a, b; Stage st; double work; Stage also = ST_COUNT; Stage shape = ST_COUNT; };
-    std::vector<Pending> pending_;
-    std::vector<hipEvent_t> event_pool_;
-    StageStats stats_;
-    std::mutex done_mutex_;
+    // ---- pass flags
     int* pass_flags_ = nullptr;          // [kPassFlags] pinned, host-visible; pass_flag_ = the slot of the pass enqueued last
     int* pass_flag_ = nullptr;
     unsigned pass_counter_ = 0;
     std::shared_ptr<DeferredPass> flag_owner_[kPassFlags];   // deferred passes by the flag they report through
-    std::vector<hipEvent_t> done_pool_;   // completion() events, guarded by done_mutex_ (taken without mutex_)
+
+    // ---- components (declared last: they are made after the stream and go before everything above)
+    StageClock clock_;
+    CompletionEvents done_events_;
+    MaskTransport masks_;
 };
 
 }  // namespace dlimg

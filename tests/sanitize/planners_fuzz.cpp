@@ -1,9 +1,11 @@
 // ASan + UBSan harness for the pure host planners (tests/test_sanitizers.py): csrc/step_queue.hpp (which lane takes which
-// requests), csrc/mask_pieces.hpp (how a batch of masks is cut into transfer pieces) and csrc/resize_tables.cpp (the
-// contributor tables the resize kernels index with) and csrc/gemm_plan.cpp (which tile configuration runs a GEMM) on a few
-// hundred thousand random inputs, with the invariants the callers rely on checked on every one.
+// requests), csrc/mask_pieces.hpp (how a batch of masks is cut into transfer pieces), csrc/mask_transport.hpp (which road
+// the masks of a request take to the caller), csrc/resize_tables.cpp (the contributor tables the resize kernels index
+// with) and csrc/gemm_plan.cpp (which tile configuration runs a GEMM) on a few hundred thousand random inputs,
+// with the invariants the callers rely on checked on every one.
 #include "gemm_plan.hpp"
 #include "mask_pieces.hpp"
+#include "mask_transport.hpp"
 #include "resize_tables.hpp"
 #include "step_queue.hpp"
 
@@ -125,8 +127,118 @@ static bool fuzz_gemm_plan() {
     return true;
 }
 
+// csrc/mask_transport.hpp: 1-33 masks of 1 B to 12 MB with random pinned destinations, idle flags and IoU counts (and the
+// device form of the same masks).  What the executor and finish_masks rely on: the layout is 256-aligned and strictly
+// increasing, the pieces are strictly increasing and end where the reservation does, walking them with
+// mask_copies_in_piece copies every byte of every mask that is not in place exactly once from where the kernel was told to
+// write it (and nothing of a mask in place), a direct piece is not waited for before its mask is complete, and no launch,
+// copy command or host copy leaves the reservation.
+static const char* fuzz_mask_transport_once(MaskTransportInput& in, MaskTransportPlan& p) {
+    const int count = 1 + (int)rnd(33);
+    in.sizes.resize(count);
+    in.dst_pinned.resize(count);
+    const uint32_t pinned_odds = rnd(3);         // none, about half, all
+    for (int i = 0; i < count; ++i) {
+        in.sizes[i] = 1 + rnd(rnd(3) ? 12000000 : rnd(2) ? 70000 : 600);
+        in.dst_pinned[i] = pinned_odds == 0 ? 0 : pinned_odds == 2 ? 1 : (char)rnd(2);
+    }
+    in.iou_count = rnd(3) ? 4 * (int)rnd(count + 1) : 0;
+    in.direct_allowed = rnd(8) != 0;
+    in.others_idle = rnd(2) != 0;
+    plan_mask_transport(in, p);
+    const bool direct = in.direct_allowed && (count == 1 || (count <= 6 && in.others_idle));
+    if ((p.mode == MaskMode::direct) != direct || (!direct && p.mode != MaskMode::staged)) return "mode";
+    if ((int)p.kernel_dst.size() != count || (int)p.in_place.size() != count) return "a vector per mask has another length";
+    std::vector<size_t> off(count);
+    size_t total = 0;
+    for (int i = 0; i < count; ++i) {
+        off[i] = total;
+        if (off[i] % 256 || (i && off[i] <= off[i - 1])) return "offsets not aligned or not increasing";
+        total += padded_mask_bytes(in.sizes[i]);
+    }
+    const size_t with_iou = total + 4 * (size_t)in.iou_count;
+    if (p.iou_offset != total || p.reserve_device != with_iou || p.reserve_pinned != with_iou) return "reservation";
+    for (int i = 0; i < count; ++i) {
+        if (p.kernel_dst[i] == kCallersPointer ? !(direct && in.dst_pinned[i]) : p.kernel_dst[i] != off[i]) return "kernel destination";
+        if (p.kernel_dst[i] != kCallersPointer && p.kernel_dst[i] + in.sizes[i] > with_iou) return "a mask leaves the reservation";
+        if (direct && (p.kernel_dst[i] == kCallersPointer) != (p.in_place[i] != 0)) return "direct: in place without the kernel writing there";
+    }
+    if (p.piece_end.empty() || p.piece_end.back() != with_iou) return "the pieces do not end where the reservation does";
+    for (size_t i = 1; i < p.piece_end.size(); ++i)
+        if (p.piece_end[i] <= p.piece_end[i - 1]) return "pieces not increasing";
+    if (direct)
+        for (int i = 0; i < count; ++i)
+            if ((int)p.piece_end.size() != count || p.piece_end[i] < off[i] + in.sizes[i]) return "direct: a piece ends before its mask";
+    // the steps: every mask launched once and in order, an event per piece in order, copies inside the reservation; in
+    // staged mode what reaches the pinned buffer piece by piece is the device buffer at the same offsets
+    int launched = 0, events = 0;
+    size_t arrived = 0;                           // staged pieces: the pinned buffer holds the staging area up to here
+    std::vector<size_t> sent(count, 0);           // bytes of mask i a copy command took to its destination
+    for (MaskStep const& s : p.steps) {
+        if (s.kind == MaskStep::launch) {
+            if (s.first != launched || s.count <= 0 || (direct ? s.count != 1 : s.count != count)) return "launch";
+            launched += s.count;
+        } else if (s.kind == MaskStep::event) {
+            if (s.first != events++ || launched < (direct ? s.first + 1 : count)) return "event";
+        } else {
+            if (s.bytes == 0 || launched == 0) return "empty or early copy";
+            if (s.from == MaskMem::iou) {
+                if (s.from_offset != 0 || s.bytes != 4 * (size_t)in.iou_count || s.to_offset != total || s.to != (direct ? MaskMem::pinned : MaskMem::device)) return "IoU copy";
+            } else if (s.from != MaskMem::device || s.from_offset + s.bytes > with_iou) {
+                return "copy from outside the device buffer";
+            } else if (s.to == MaskMem::caller) {
+                if (s.mask < 0 || s.mask >= count || !p.in_place[s.mask] || s.from_offset != off[s.mask] || s.to_offset != 0 || s.bytes != in.sizes[s.mask]) return "copy to a caller";
+                sent[s.mask] += s.bytes;
+            } else if (s.to == MaskMem::pinned) {
+                if (s.to_offset != s.from_offset || s.to_offset + s.bytes > with_iou) return "copy to the pinned buffer";
+                if (s.from_offset == arrived) arrived += s.bytes;
+            } else {
+                return "copy to nowhere";
+            }
+        }
+    }
+    if (launched != count || p.launches != (direct ? count : 1) || events != (int)p.piece_end.size()) return "launches or events";
+    // finish_masks' walk
+    MaskCursor cursor;
+    size_t begin = 0;
+    std::vector<size_t> copied(count, 0);
+    for (size_t end : p.piece_end) {
+        for (MaskCopy const& c : mask_copies_in_piece(in.sizes, begin, end, cursor)) {
+            if (p.in_place[c.mask]) continue;
+            if (c.staging_offset != p.kernel_dst[c.mask] + c.mask_offset || c.mask_offset != copied[c.mask]) return "host copy not from where the kernel wrote";
+            if (!direct && c.staging_offset + c.bytes > arrived) return "host copy of bytes no copy command brought";
+            copied[c.mask] += c.bytes;
+        }
+        begin = end;
+    }
+    for (int i = 0; i < count; ++i) {
+        if (copied[i] != (p.in_place[i] ? 0 : in.sizes[i])) return "host copies do not cover the masks";
+        if (!direct && sent[i] != (p.in_place[i] ? in.sizes[i] : 0)) return "copy commands do not cover the masks in place";
+    }
+    // device form of the same masks
+    const bool own = rnd(2) != 0;
+    plan_mask_transport_device(in.sizes, own, p);
+    if (p.mode != (own ? MaskMode::device_direct : MaskMode::device_staged) || p.launches != 1 || !p.piece_end.empty()) return "device form: mode";
+    if (p.reserve_pinned != 0 || p.reserve_device != (own ? 0 : total)) return "device form: reservation";
+    if (p.steps.size() != (own ? 1u : 1u + count) || p.steps[0].kind != MaskStep::launch || p.steps[0].first != 0 || p.steps[0].count != count) return "device form: steps";
+    for (int i = 0; i < count; ++i) {
+        if (p.kernel_dst[i] != (own ? kCallersPointer : off[i])) return "device form: kernel destination";
+        if (own) continue;
+        MaskStep const& s = p.steps[1 + i];
+        if (s.kind != MaskStep::copy || s.from != MaskMem::device || s.to != MaskMem::peer || s.mask != i || s.from_offset != off[i] ||
+            s.to_offset != 0 || s.bytes != in.sizes[i] || s.from_offset + s.bytes > p.reserve_device) return "device form: peer copy";
+    }
+    return nullptr;
+}
+
 int main() {
     if (!fuzz_gemm_plan()) return 1;
+    {
+        MaskTransportInput in;                   // re-used like a slot's
+        MaskTransportPlan plan;
+        for (int iter = 0; iter < 30000; ++iter)
+            if (const char* bad = fuzz_mask_transport_once(in, plan)) { std::printf("mask transport: %s (iteration %d)\n", bad, iter); return 1; }
+    }
     for (int iter = 0; iter < 200000; ++iter) {
         StepQueueState st;
         const int lanes = 1 + (int)rnd(8);

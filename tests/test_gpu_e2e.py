@@ -317,7 +317,7 @@ def test_pinned_image_memory_is_bounded(api, session):
 @pytest.mark.parametrize("n_prompts", [2, 5, 6, 7])
 def test_masks_written_straight_to_host_memory_equal_the_copied_ones(api, session, n_prompts):
     """Up to six masks of a call leave as one post-processing launch each, straight into pinned host memory (while the other
-    lanes are idle; more go through a device buffer and piecewise copies: csrc/sam_model.cpp, enqueue_masks).  Either way the
+    lanes are idle; more go through a device buffer and piecewise copies: csrc/mask_transport.hpp, plan_mask_transport).  Either way the
     caller gets the masks of one-at-a-time queries, bit for bit -- on 1024 x 1024 and on a 1800 x 1200 image (2.1 MB masks at
     their own resolution, staging offsets padded to 256 bytes), single and multi-mask mode."""
     env, _, _, _, seg, _ = session

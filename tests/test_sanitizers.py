@@ -168,7 +168,8 @@ def test_lane_worker_and_its_hand_over_protocols_under_thread_sanitizer(tmp_path
 
 
 def test_planners_on_random_inputs_under_address_sanitizer(tmp_path):
-    """csrc/step_queue.hpp and csrc/mask_pieces.hpp on 220 000 random inputs, csrc/resize_tables.cpp on 1 500 axis pairs
+    """csrc/step_queue.hpp and csrc/mask_pieces.hpp on 220 000 random inputs, csrc/mask_transport.hpp on 30 000 requests of
+    1 to 33 masks (both forms), csrc/resize_tables.cpp on 1 500 axis pairs
     (1 pixel to 40 000, both filters) and csrc/gemm_plan.cpp on 100 000 random GEMM problems with ASan + UBSan, every result
     checked against the invariants its caller relies on (tests/sanitize/planners_fuzz.cpp)."""
     csrc = ROOT / "dlimgedit_amd" / "csrc"
