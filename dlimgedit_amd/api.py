@@ -302,6 +302,111 @@ class Mask:
     accuracy: float = 0.0
 
 
+MAX_CLICKS = 8               # clicks of one prompt (csrc/prompt_plan.hpp: kMaxClicks)
+TOKEN_ROWS_MAX = 112         # token rows of one decoder launch (csrc/kernels/kernels.hpp: kDecoderMaxRows)
+EMPTY_REGION = (0, 0, -1, -1)    # x1 < x0: "no box" for the head of a multi-click prompt
+
+
+@dataclass
+class ClickEntries:
+    """The entry lists of one multi-click batch call, as table slot 14 and its device form read them: entry i has the handle
+    index heads[i] (None: a continuation entry, one more click of the prompt in front of it), the click points[i] and the
+    four ints regions[i] -- the box of a head (EMPTY_REGION: none), (label, 0, 0, 0) of a continuation entry.
+    prompt_heads[j] is the entry that opened prompt j, token_rows[j] its token rows in the decoder (6 + clicks, 7 + clicks with
+    a box), and launches the decoder launches of one GPU: [(token rows, [prompt indices])], prompts grouped by their token
+    rows in order of first appearance and cut at the 112 rows a launch holds."""
+    heads: list
+    points: list
+    regions: list
+    prompt_heads: list
+    token_rows: list
+
+    @property
+    def launches(self) -> list:
+        out = []
+        for t in dict.fromkeys(self.token_rows):
+            group = [j for j, tj in enumerate(self.token_rows) if tj == t]
+            cut = TOKEN_ROWS_MAX // t
+            out += [(t, group[k:k + cut]) for k in range(0, len(group), cut)]
+        return out
+
+
+def pack_clicks(clicks, labels, region=None):
+    """One prompt as the decoder sees it, in the order SAM's PromptEncoder packs it: the clicks in the order given with labels
+    1 (foreground) / 0 (background), then the box's top-left and bottom-right (labels 2, 3); the padding point (0, 0) with label
+    -1 only when there is no box.  -> ([(x, y)], [label]) in image pixels."""
+    clicks, labels = _checked_clicks(clicks, labels)
+    pts = [(c.x, c.y) for c in clicks]
+    labs = list(labels)
+    if region is not None:
+        pts += [(region.top_left.x, region.top_left.y), (region.bottom_right.x, region.bottom_right.y)]
+        labs += [2, 3]
+    else:
+        pts.append((0, 0))
+        labs.append(-1)
+    return pts, labs
+
+
+def _checked_clicks(clicks, labels):
+    clicks = list(clicks)
+    labels = [1] * len(clicks) if labels is None else [int(v) for v in labels]
+    if not clicks:
+        raise Error("a prompt needs at least one click")
+    if len(clicks) > MAX_CLICKS:
+        raise Error(f"a prompt takes at most {MAX_CLICKS} clicks, not {len(clicks)}")
+    if len(labels) != len(clicks):
+        raise Error(f"{len(clicks)} clicks but {len(labels)} labels")
+    if any(v not in (0, 1) for v in labels):
+        raise Error("the label of a click is 1 (foreground) or 0 (background)")
+    if labels[0] != 1:
+        raise Error("the first click of a prompt is a foreground click: it travels in the head entry, which has no label")
+    return clicks, labels
+
+
+def click_entries(clicks, labels=None, regions=None) -> ClickEntries:
+    """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
+    labels[j] their labels (None: all foreground), regions[j] its box or None.  Pure host code."""
+    n = len(clicks)
+    labels = [None] * n if labels is None else list(labels)
+    regions = [None] * n if regions is None else list(regions)
+    if len(labels) != n or len(regions) != n:
+        raise Error("one list of labels and one region (or None) per prompt")
+    out = ClickEntries([], [], [], [], [])
+    for j in range(n):
+        cs, ls = _checked_clicks(clicks[j], labels[j])
+        r = regions[j]
+        out.prompt_heads.append(len(out.heads))
+        out.token_rows.append(5 + len(cs) + (2 if r is not None else 1))
+        for k, (c, lab) in enumerate(zip(cs, ls)):
+            out.heads.append(j if k == 0 else None)
+            out.points.append((c.x, c.y))
+            if k:
+                out.regions.append((lab, 0, 0, 0))
+            else:
+                out.regions.append(EMPTY_REGION if r is None else (r.top_left.x, r.top_left.y, r.bottom_right.x, r.bottom_right.y))
+    return out
+
+
+def _entry_calls(entries: ClickEntries) -> list:
+    """The calls that carry `entries`: [[entry indices], regions given].  One call with both arrays as soon as any prompt has a
+    second click.  Without any, the entries are today's point and box + point entries, in which an empty region has no
+    special meaning: the prompts without a box travel in a call without `regions`, those with one in a call with both."""
+    n = len(entries.heads)
+    if any(h is None for h in entries.heads):
+        return [(list(range(n)), True)]
+    plain = [i for i in range(n) if entries.regions[i] == EMPTY_REGION]
+    boxed = [i for i in range(n) if entries.regions[i] != EMPTY_REGION]
+    return [(sel, given) for sel, given in ((plain, False), (boxed, True)) if sel]
+
+
+def _entry_arrays(segs, entries: ClickEntries, sel, regions_given: bool):
+    n = len(sel)
+    handles = (C.c_void_p * n)(*[None if entries.heads[i] is None else segs[entries.heads[i]]._handle for i in sel])
+    p = (C.c_int * (2 * n))(*[v for i in sel for v in entries.points[i]])
+    r = (C.c_int * (4 * n))(*[v for i in sel for v in entries.regions[i]]) if regions_given else None
+    return n, handles, p, r
+
+
 class Segmentation:
     """dlimg::Segmentation: cached image embedding + mask queries."""
 
@@ -360,12 +465,36 @@ class Segmentation:
         masks, acc = self._query(point, None, 3)
         return [Mask(m, a) for m, a in zip(masks, acc)]
 
+    def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
+                            region: Optional[Region] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
+        an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0."""
+        return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
+                                               out=None if out is None else [out])[0]
+
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
-                           regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None) -> list:
+                           regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
+                           clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
-        point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0)."""
+        point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
+        `clicks` instead of `points`: prompt i is the clicks clicks[i] (1 .. 8) with labels[i] (1 / 0; None: foreground) and
+        the box regions[i] (None: no box); prompts of different sizes may share the call (click_entries builds the lists)."""
+        if clicks is not None:
+            if points is not None:
+                raise Error("compute_mask_batch: `points` or `clicks`, not both")
+            if len(clicks) != len(segs):
+                raise Error("compute_mask_batch: one list of clicks per segmentation")
+            outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
+            assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
+            entries = click_entries(clicks, labels, regions)
+            out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
+            for sel, given in _entry_calls(entries):
+                n, handles, p, r = _entry_arrays(segs, entries, sel, given)
+                ptrs = (C.c_void_p * n)(*[out_of[i].ctypes.data if i in out_of else None for i in sel])
+                _check(api().get_segmentation_masks(handles, n, p, r, ptrs))
+            return outs
         n = len(segs)
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
@@ -672,10 +801,29 @@ class ext:
         return r.value, d.value
 
     @classmethod
-    def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0) -> list:
-        """Device-output form of Segmentation.compute_mask_batch (points, regions or both, as there): masks land tightly
-        packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their embeddings live; returns the byte
-        offset of every mask."""
+    def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0, clicks=None,
+                                  labels=None) -> list:
+        """Device-output form of Segmentation.compute_mask_batch (points, regions or both, or clicks / labels / regions, as
+        there): masks land tightly packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their
+        embeddings live; returns the byte offset of every mask."""
+        if clicks is not None:
+            if points is not None:
+                raise Error("compute_mask_batch_device: `points` or `clicks`, not both")
+            if len(clicks) != len(segs):
+                raise Error("compute_mask_batch_device: one list of clicks per segmentation")
+            entries = click_entries(clicks, labels, regions)
+            calls = _entry_calls(entries)
+            if len(calls) > 1:      # one-click prompts with and without a box: a call each, so that the masks stay in order
+                calls = [([i], entries.regions[i] != EMPTY_REGION) for i in range(len(entries.heads))]
+            result, base = [], 0
+            for sel, given in calls:
+                n, handles, p, r = _entry_arrays(segs, entries, sel, given)
+                offsets = (C.c_size_t * n)()
+                _check(cls._l().dlimg_amd_get_segmentation_masks_device(handles, n, p, r, root_device, dev_out + base, offsets))
+                result += [base + offsets[k] for k, i in enumerate(sel) if entries.heads[i] is not None]
+                e = segs[entries.heads[sel[0]]].extent()
+                base += e.width * e.height if len(calls) > 1 else 0
+            return result
         n = len(segs)
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         p = r = None

@@ -148,10 +148,8 @@ dlimg_Result get_segmentation_masks(dlimg_Segmentation const* segs, int count, i
     return guarded([&] {
         DLIMG_ASSERT(segs != nullptr && out_masks != nullptr && count >= 0);
         std::vector<SegmentationImpl const*> s(count);
-        for (int i = 0; i < count; ++i) {
-            DLIMG_ASSERT(segs[i] != nullptr);
-            s[i] = &impl(segs[i]);
-        }
+        // a null handle is a continuation entry: one more click of the prompt in front of it (prompt_plan.hpp)
+        for (int i = 0; i < count; ++i) s[i] = segs[i] ? &impl(segs[i]) : nullptr;
         SegmentationImpl::compute_mask_batch(s.data(), count, points, regions, out_masks);
     });
 }

@@ -378,10 +378,8 @@ DLIMG_API int dlimg_amd_get_segmentation_masks_device(dlimg_Segmentation const* 
     return guarded([&] {
         DLIMG_ASSERT(segs != nullptr && count >= 0);
         std::vector<SegmentationImpl const*> s(count);
-        for (int i = 0; i < count; ++i) {
-            DLIMG_ASSERT(segs[i] != nullptr);
-            s[i] = &impl(segs[i]);
-        }
+        // a null handle is a continuation entry: one more click of the prompt in front of it (prompt_plan.hpp)
+        for (int i = 0; i < count; ++i) s[i] = segs[i] ? &impl(segs[i]) : nullptr;
         SegmentationImpl::compute_mask_batch_device(s.data(), count, points, regions, root_device, dev_out, out_offsets);
     });
 }

@@ -17,9 +17,10 @@ namespace {
 #include "gemm_f16_tile.inc"
 
 // Tokens per prompt: iou token + 4 mask tokens + the prompt's points -- 7 (a point and its pad token, or the two corners of
-// a box) or 8 (a point and a box).  It is the template parameter TOK of everything below that depends on it: the launchers
-// pick the instantiation, the 7-token code is what it was when TOK was a constant of this file, and a launch never mixes
-// counts.
+// a box), 8 (a point and a box), and up to 15 for several clicks (n clicks and the pad token: 6 + n, n clicks and a box:
+// 7 + n, n <= 8).  It is the template parameter TOK of everything below that depends on it: the launchers pick the
+// instantiation -- one per count, so a kernel sees exactly the packed token list and no attention has a key to mask --
+// the 7-token code is what it was when TOK was a constant of this file, and a launch never mixes counts.
 constexpr int OUT_TOK = 5;    // iou token + 4 mask tokens: the rows the heads read
 constexpr int DIM = 256;
 constexpr int INNER = 128;    // cross-attention width (downsample 2)
@@ -73,10 +74,12 @@ DLIMG_DEVICE void prompt_token_column(const Prompts& pr, int p, int c, const flo
 constexpr int RCHUNK = 8;               // rows a wave accumulates at a time in the token linears
 constexpr int TL_MAX_ROWS = k::kDecoderMaxRows;   // 16 prompts x 7 tokens, or 14 prompts x 8 tokens, per launch
 constexpr int TL_MAX_OPS = 5;
-constexpr int TL_PROMPT_SLICE = 2;           // prompts per workgroup of the fused attention-output kernels
 constexpr int TL_MAX_ROW_SLICE = 16;         // lane L of a wave finishes row L of a slice
-// rows per workgroup of token_linears_kernel (two prompts)
-template <int TOK> constexpr int TL_ROW_SLICE = TL_PROMPT_SLICE * TOK;
+// prompts per workgroup of the token linears and the fused attention-output kernels: two while two fit the 16 rows of a
+// slice, one from 9 token rows on (k::decoder_prompt_slice is the launchers' copy)
+template <int TOK> constexpr int TL_PROMPT_SLICE = k::decoder_prompt_slice(TOK);
+// rows per workgroup of token_linears_kernel (whole prompts)
+template <int TOK> constexpr int TL_ROW_SLICE = TL_PROMPT_SLICE<TOK> * TOK;
 
 struct LinJob { k::TokenLinear op[TL_MAX_OPS]; int count; int rows; };
 
@@ -158,7 +161,8 @@ DLIMG_DEVICE void stage_token_rows(const k::TokenRows& m, int row0, int rows, fl
 // residual entry with its LayerNorm scale / shift.  [Before r03 lane 0 fetched bias and residual after the sums: one more
 // round trip to L2 per call, which a workgroup that runs several columns per wave pays several times over.]
 struct TokenColumn { float4_t w; float bias, rx, radd, rlw, rlb; };
-static_assert(TL_ROW_SLICE<7> <= TL_MAX_ROW_SLICE && TL_ROW_SLICE<8> <= TL_MAX_ROW_SLICE, "lane L of a wave finishes row L of the slice");
+static_assert(TL_ROW_SLICE<7> <= TL_MAX_ROW_SLICE && TL_ROW_SLICE<8> <= TL_MAX_ROW_SLICE && TL_ROW_SLICE<9> <= TL_MAX_ROW_SLICE &&
+              TL_ROW_SLICE<k::kDecoderMaxTokens> <= TL_MAX_ROW_SLICE, "lane L of a wave finishes row L of the slice");
 DLIMG_DEVICE TokenColumn token_column_prefetch(const k::TokenLinear& op, int first_col, int row0, int row1) {
     const int lane = lane_id();
     const int n = first_col + (threadIdx.x >> 6);
@@ -435,15 +439,29 @@ __global__ __launch_bounds__(T2I_THREADS) void token_to_image_partial_kernel(con
     }
     // the four waves' partials of every query are folded here, in wave order: one triple per workgroup leaves
     __syncthreads();
-    if (tid < TOK * 18) {
-        const int t = tid / 18, e = tid % 18;
-        float M = wpart[t][0][0];
+    if constexpr (TOK * 18 <= T2I_THREADS) {
+        if (tid < TOK * 18) {
+            const int t = tid / 18, e = tid % 18;
+            float M = wpart[t][0][0];
 #pragma unroll
-        for (int w = 1; w < T2I_WAVES; ++w) M = fmaxf(M, wpart[t][w][0]);
-        float acc = 0.f;
+            for (int w = 1; w < T2I_WAVES; ++w) M = fmaxf(M, wpart[t][w][0]);
+            float acc = 0.f;
 #pragma unroll
-        for (int w = 0; w < T2I_WAVES; ++w) acc += (e == 0 ? 0.f : wpart[t][w][e]) * __expf(wpart[t][w][0] - M);
-        dst[(size_t)t * T2I_PARTS * 18 + e] = e == 0 ? M : acc;
+            for (int w = 0; w < T2I_WAVES; ++w) acc += (e == 0 ? 0.f : wpart[t][w][e]) * __expf(wpart[t][w][0] - M);
+            dst[(size_t)t * T2I_PARTS * 18 + e] = e == 0 ? M : acc;
+        }
+    } else {
+        // 15 token rows: 270 values, a second trip for the last few (the same arithmetic)
+        for (int i = tid; i < TOK * 18; i += T2I_THREADS) {
+            const int t = i / 18, e = i % 18;
+            float M = wpart[t][0][0];
+#pragma unroll
+            for (int w = 1; w < T2I_WAVES; ++w) M = fmaxf(M, wpart[t][w][0]);
+            float acc = 0.f;
+#pragma unroll
+            for (int w = 0; w < T2I_WAVES; ++w) acc += (e == 0 ? 0.f : wpart[t][w][e]) * __expf(wpart[t][w][0] - M);
+            dst[(size_t)t * T2I_PARTS * 18 + e] = e == 0 ? M : acc;
+        }
     }
 }
 
@@ -464,10 +482,10 @@ template <int TOK>
 DLIMG_DEVICE void token_self_attn_out_body(const float* __restrict__ q, const float* __restrict__ kx, const float* __restrict__ v,
                                            const k::TokenLinear& op, int P, const int block_x, const int block_y, float* lds) {
     // prompts are dealt to block_y in pairs (rows row0 .. row1 of the token matrix; LDS rows are local)
-    const int p0 = block_y * TL_PROMPT_SLICE, p1 = min(P, p0 + TL_PROMPT_SLICE);
+    const int p0 = block_y * TL_PROMPT_SLICE<TOK>, p1 = min(P, p0 + TL_PROMPT_SLICE<TOK>);
     const int row0 = p0 * TOK, row1 = p1 * TOK;
     float* att = lds;                                   // [rows of this slice][256]
-    float2_t* stat_res = reinterpret_cast<float2_t*>(att + (size_t)TL_PROMPT_SLICE * TOK * DIM) - row0;     // indexed by global row
+    float2_t* stat_res = reinterpret_cast<float2_t*>(att + (size_t)TL_PROMPT_SLICE<TOK> * TOK * DIM) - row0;     // indexed by global row
     const TokenColumn w_first = token_column_prefetch(op, block_x * 4, row0, row1);
     const int c = threadIdx.x;
     const float scale = 0.17677669529663687f;           // 32^-0.5
@@ -517,9 +535,10 @@ __global__ __launch_bounds__(256) void token_self_attn_out_kernel(const float* _
 // same bits -- in front of them the self-attention's workgroups.  Both parts use 256 threads.
 constexpr int SAG_BM = 64, SAG_BN = 64;
 constexpr size_t SAG_GEMM_LDS = (size_t)2 * (SAG_BM + SAG_BN) * 64 * 2 + aux_bytes(SAG_BM, SAG_BN);
-template <int TOK> constexpr size_t SA_TOKEN_LDS = (size_t)TL_PROMPT_SLICE * TOK * (DIM * 4 + 8);
+template <int TOK> constexpr size_t SA_TOKEN_LDS = (size_t)TL_PROMPT_SLICE<TOK> * TOK * (DIM * 4 + 8);
 template <int TOK> constexpr size_t SAG_LDS = SAG_GEMM_LDS > SA_TOKEN_LDS<TOK> ? SAG_GEMM_LDS : SA_TOKEN_LDS<TOK>;
-static_assert(SAG_LDS<7> <= 48 * 1024 && SAG_LDS<8> <= 48 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
+static_assert(SAG_LDS<7> <= 48 * 1024 && SAG_LDS<8> <= 48 * 1024 && SAG_LDS<k::kDecoderMaxTokens> <= 48 * 1024,
+              "below the default dynamic-LDS limit: no opt-in needed");
 template <int TOK>
 __global__ __launch_bounds__(256, 4) void self_attn_out_and_gemm_kernel(k::GemmArgs g, int gemm_tiles, const float* __restrict__ q,
                                                                         const float* __restrict__ kx, const float* __restrict__ v,
@@ -807,12 +826,15 @@ __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float*
 // 5-9 us of dependent latency.  The prompts travel as kernel arguments: no host-to-device copy in front of a decode.
 // They travel at the size of the launch's own token count (k::DecoderPrompts holds the largest): a two-point launch carries
 // the 512 bytes it always did.
+// Up to 8 token rows the arrays hold kDecoderMaxPrompts prompts, as they always did; from 9 on the prompts one launch of that
+// count can hold (decoder_max_prompts: 12 at 9 rows, 7 at 15), so the block stays under 1 KB at every count.
 template <int TOK>
 struct StartPrompts {
     static constexpr int NPTS = TOK - OUT_TOK;
-    float coords[k::kDecoderMaxPrompts * NPTS * 2];
-    float labels[k::kDecoderMaxPrompts * NPTS];
-    const float* emb[k::kDecoderMaxPrompts];
+    static constexpr int MAXP = TOK <= 8 ? k::kDecoderMaxPrompts : k::decoder_max_prompts(TOK);
+    float coords[MAXP * NPTS * 2];
+    float labels[MAXP * NPTS];
+    const float* emb[MAXP];
 };
 template <int TOK>
 struct DecoderStart {
@@ -823,6 +845,11 @@ struct DecoderStart {
     int lin_blocks, lin_cols;
     const float* no_mask; float* keys; half_t* keys_h; size_t n4_per_prompt; int P;
 };
+// kernel arguments are limited to 4 KB; the largest prompt block is the one of 14 token rows (8 prompts x 9 points, 928 bytes)
+static_assert(sizeof(DecoderStart<7>) <= 2048 && sizeof(DecoderStart<8>) <= 2048 && sizeof(DecoderStart<9>) <= 2048 &&
+              sizeof(DecoderStart<10>) <= 2048 && sizeof(DecoderStart<11>) <= 2048 && sizeof(DecoderStart<12>) <= 2048 &&
+              sizeof(DecoderStart<13>) <= 2048 && sizeof(DecoderStart<14>) <= 2048 && sizeof(DecoderStart<15>) <= 2048,
+              "the prompts travel as kernel arguments");
 template <int TOK>
 __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart<TOK> a) {
     __shared__ __attribute__((aligned(16))) float rows[TL_ROW_SLICE<TOK> * DIM];
@@ -870,10 +897,14 @@ __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart<TOK> a)
 }  // namespace
 
 // the body once for each supported token count (k::decoder_tokens_supported)
+#define DLIMG_TOKENS_CASE(N, ...) else if (tokens_ == N) { constexpr int TOK = N; __VA_ARGS__ }
 #define DLIMG_FOR_TOKENS(T, who, ...)                                        \
-    if ((T) == 7) { constexpr int TOK = 7; __VA_ARGS__ }                     \
-    else if ((T) == 8) { constexpr int TOK = 8; __VA_ARGS__ }                \
-    else { throw_error(who ": 7 or 8 tokens per prompt"); }
+    if (const int tokens_ = (T); tokens_ == 7) { constexpr int TOK = 7; __VA_ARGS__ } \
+    DLIMG_TOKENS_CASE(8, __VA_ARGS__) DLIMG_TOKENS_CASE(9, __VA_ARGS__) DLIMG_TOKENS_CASE(10, __VA_ARGS__)  \
+    DLIMG_TOKENS_CASE(11, __VA_ARGS__) DLIMG_TOKENS_CASE(12, __VA_ARGS__) DLIMG_TOKENS_CASE(13, __VA_ARGS__) \
+    DLIMG_TOKENS_CASE(14, __VA_ARGS__) DLIMG_TOKENS_CASE(15, __VA_ARGS__)    \
+    else { throw_error(who ": 7 to 15 tokens per prompt"); }
+static_assert(k::kDecoderMaxTokens == 15, "DLIMG_FOR_TOKENS names every supported count");
 
 namespace k {
 
@@ -881,7 +912,7 @@ void decoder_start(const DecoderPrompts& prompts, const float* gauss, const floa
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
                    const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
     if (P <= 0) return;
-    if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 or 8 tokens per prompt");
+    if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 to 15 tokens per prompt");
     if (P > decoder_max_prompts(T) || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
     const size_t n4 = (size_t)NTOK_IMG * DIM / 4;
     const size_t total = n4 * P;
@@ -904,7 +935,7 @@ void decoder_start(const DecoderPrompts& prompts, const float* gauss, const floa
         a.first.rows = P * T;
         for (int i = 0; i < n_first; ++i) a.first.op[i] = first[i];
         a.lin_cols = cols > 0 ? cols : 1;
-        a.lin_blocks = cols * ((P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE);
+        a.lin_blocks = cols * ((P + TL_PROMPT_SLICE<TOK> - 1) / TL_PROMPT_SLICE<TOK>);
         a.no_mask = no_mask; a.keys = keys; a.keys_h = keys_h; a.n4_per_prompt = n4; a.P = P;
         hipLaunchKernelGGL(decoder_start_kernel<TOK>, dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);)
 }
@@ -913,7 +944,7 @@ size_t token_to_image_scratch_floats(int P, int T) { return (size_t)P * HEADS * 
 
 void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t s) {
     if (count <= 0 || rows <= 0) return;
-    if (!decoder_tokens_supported(T) || rows % T) throw_error("token_linears: whole prompts of 7 or 8 token rows");
+    if (!decoder_tokens_supported(T) || rows % T) throw_error("token_linears: whole prompts of 7 to 15 token rows");
     if (count > TL_MAX_OPS || rows > TL_MAX_ROWS) throw_error("token_linears: too many layers or rows for one launch");
     LinJob job;
     job.count = count;
@@ -927,7 +958,7 @@ void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream
         job.op[i] = ops[i];
         blocks += ops[i].N / 4;
     }
-    const int row_slice = TL_PROMPT_SLICE * T;
+    const int row_slice = decoder_prompt_slice(T) * T;
     const int slices = (rows + row_slice - 1) / row_slice;
     if (count == 1 && ops[0].K > DIM && ops[0].K % 256 == 0 && ops[0].K <= TLD_MAX_K && !ops[0].in.ln_w && !ops[0].in.add) {
         const size_t lds = (size_t)std::min(rows, row_slice) * ops[0].K * 4;
@@ -945,9 +976,11 @@ void token_self_attention_out(const float* q, const float* kx, const float* v, c
     if (P <= 0) return;
     if (!decoder_tokens_supported(T) || P * T > TL_MAX_ROWS || out.K != DIM || out.N % 4)
         throw_error("token_self_attention_out: unsupported shape");
-    static_assert(SA_TOKEN_LDS<7> <= 64 * 1024 && SA_TOKEN_LDS<8> <= 64 * 1024, "below the default dynamic-LDS limit: no opt-in needed");
+    static_assert(SA_TOKEN_LDS<7> <= 64 * 1024 && SA_TOKEN_LDS<8> <= 64 * 1024 && SA_TOKEN_LDS<kDecoderMaxTokens> <= 64 * 1024,
+                  "below the default dynamic-LDS limit: no opt-in needed");
+    const int slice = decoder_prompt_slice(T);
     DLIMG_FOR_TOKENS(T, "token_self_attention_out",
-        hipLaunchKernelGGL(token_self_attn_out_kernel<TOK>, dim3(out.N / 4, (P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE), dim3(256),
+        hipLaunchKernelGGL(token_self_attn_out_kernel<TOK>, dim3(out.N / 4, (P + slice - 1) / slice), dim3(256),
                            SA_TOKEN_LDS<TOK>, s, q, kx, v, out, P);)
 }
 
@@ -962,7 +995,8 @@ bool token_self_attention_out_with_gemm(const float* q, const float* kx, const f
                        g.N % SAG_BN == 0 && g.K % 64 == 0 && !(g.resid && g.resid_mod % SAG_BM != 0);
     if (!plain) return false;
     const int tiles = (g.M / SAG_BM) * (g.N / SAG_BN);
-    const int bx = out.N / 4, by = (P + TL_PROMPT_SLICE - 1) / TL_PROMPT_SLICE;
+    const int slice = decoder_prompt_slice(T);
+    const int bx = out.N / 4, by = (P + slice - 1) / slice;
     // the tiles sit behind the self-attention's workgroups and find their XCD by their own index (xcd_remap): that is the
     // XCD the hardware gave them only if a multiple of 8 workgroups stands in front
     if ((bx * by) % 8) return false;

@@ -29,7 +29,7 @@ DLIMG_DEVICE float sum_over_groups(float v) {
 
 // ---------------------------------------------------------------------------------------------
 // keys <- LayerNorm(keys + attention(image -> tokens) Wo + bo), with the f16 copy the next projection reads.
-//   attention: an image position attends to the TOK (7 or 8) tokens of its prompt, 8 heads x 16 (q: f16 [rows][ldq],
+//   attention: an image position attends to the TOK (7 .. 15) tokens of its prompt, 8 heads x 16 (q: f16 [rows][ldq],
 //              token k / v: fp32 [P][TOK][128]); lane (row m = lane % 16, group g = lane / 16) does heads 2g and 2g + 1 of its row, so its
 //              32 outputs ARE the A fragments of the projection for k = 32 g + 8 kk .. + 7, kk = 0 .. 3
 //   projection: 128 -> 256 on v_mfma_f32_16x16x32_f16, Wo (f16 [256][128]) in LDS for the workgroup's 64 rows
@@ -40,6 +40,10 @@ DLIMG_DEVICE float sum_over_groups(float v) {
 constexpr int IU_ROWS = 64;
 constexpr int IU_WSTRIDE = INNER + 8;        // halves per row of Wo in LDS: 272 B, so the 16 rows of a fragment read spread over the banks
 template <int TOK> constexpr size_t IU_LDS = (size_t)DIM * IU_WSTRIDE * 2 + 2 * TOK * INNER * 4 + 3 * DIM * 4;
+// 68 KB of Wo + 1 KB per token row + 3 KB: 79 KB at 7 token rows, 86 KB at 15, of the CU's 160 KB.  What limits the kernel
+// to one workgroup per CU is not LDS but registers: 259 (7 rows) to 288 (15 rows) VGPRs + AGPRs per lane (Wo in flight, the
+// residual, the accumulators) leave one wave per SIMD at every count, so the larger counts lose no occupancy.
+static_assert(IU_LDS<k::kDecoderMaxTokens> <= 160 * 1024, "the CU's LDS");
 
 struct ImageUpdate {
     const half_t* q; int ldq;
@@ -51,7 +55,9 @@ struct ImageUpdate {
 
 template <int TOK>
 __global__ __launch_bounds__(256) void image_update_kernel(ImageUpdate a) {
-    static_assert(TOK * INNER / 4 <= 256, "a thread stages one float4 of the prompt's token k and v");
+    // a thread stages one float4 of the prompt's token k and v up to 8 token rows, two from 9 on
+    constexpr int KV4 = TOK * INNER / 4, KV_TRIPS = (KV4 + 255) / 256;
+    static_assert(KV_TRIPS <= 2, "token k / v staging");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     half_t* w_lds = reinterpret_cast<half_t*>(smem);                                   // [256][IU_WSTRIDE]
     float* sk = reinterpret_cast<float*>(smem + (size_t)DIM * IU_WSTRIDE * 2);         // [TOK][128]
@@ -75,6 +81,13 @@ __global__ __launch_bounds__(256) void image_update_kernel(ImageUpdate a) {
         kvreg[0] = reinterpret_cast<const float4_t*>(a.tk + (size_t)p * TOK * INNER)[tid];
         kvreg[1] = reinterpret_cast<const float4_t*>(a.tv + (size_t)p * TOK * INNER)[tid];
     }
+    float4_t kvmore[2];                              // rows 8 .. TOK - 1: requested with everything else
+    if constexpr (KV_TRIPS > 1) {
+        if (tid + 256 < KV4) {
+            kvmore[0] = reinterpret_cast<const float4_t*>(a.tk + (size_t)p * TOK * INNER)[tid + 256];
+            kvmore[1] = reinterpret_cast<const float4_t*>(a.tv + (size_t)p * TOK * INNER)[tid + 256];
+        }
+    }
     const float c0 = a.bias[tid], c1 = a.ln_w[tid], c2 = a.ln_b[tid];
     const half_t* qr = a.q + row * a.ldq + 32 * g;
     half8_t q8[4];
@@ -92,6 +105,12 @@ __global__ __launch_bounds__(256) void image_update_kernel(ImageUpdate a) {
     if (tid < TOK * INNER / 4) {
         reinterpret_cast<float4_t*>(sk)[tid] = kvreg[0];
         reinterpret_cast<float4_t*>(sv)[tid] = kvreg[1];
+    }
+    if constexpr (KV_TRIPS > 1) {
+        if (tid + 256 < KV4) {
+            reinterpret_cast<float4_t*>(sk)[tid + 256] = kvmore[0];
+            reinterpret_cast<float4_t*>(sv)[tid + 256] = kvmore[1];
+        }
     }
     cb[tid] = c0;
     cb[DIM + tid] = c1;
@@ -410,9 +429,19 @@ void image_update(const half_t* q, int ldq, const float* tk, const float* tv, co
         opt_in.ensure((const void*)image_update_kernel<TOK>, IU_LDS<TOK>, "image_update: the device refuses the kernel's LDS size");
         hipLaunchKernelGGL(image_update_kernel<TOK>, dim3(P * NTOK_IMG / IU_ROWS), dim3(256), IU_LDS<TOK>, s, a);
     };
-    if (T == 7) launch(std::integral_constant<int, 7>{});
-    else if (T == 8) launch(std::integral_constant<int, 8>{});
-    else throw_error("image_update: 7 or 8 tokens per prompt");
+    switch (T) {
+        case 7: launch(std::integral_constant<int, 7>{}); break;
+        case 8: launch(std::integral_constant<int, 8>{}); break;
+        case 9: launch(std::integral_constant<int, 9>{}); break;
+        case 10: launch(std::integral_constant<int, 10>{}); break;
+        case 11: launch(std::integral_constant<int, 11>{}); break;
+        case 12: launch(std::integral_constant<int, 12>{}); break;
+        case 13: launch(std::integral_constant<int, 13>{}); break;
+        case 14: launch(std::integral_constant<int, 14>{}); break;
+        case 15: launch(std::integral_constant<int, 15>{}); break;
+        default: throw_error("image_update: 7 to 15 tokens per prompt");
+    }
+    static_assert(kDecoderMaxTokens == 15, "every supported count is named above");
 }
 
 

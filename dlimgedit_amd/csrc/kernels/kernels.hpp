@@ -149,11 +149,16 @@ void attention_global(const half_t* qkv, const half_t* rel_h, const half_t* rel_
 
 // ---- mask decoder (token side is tiny: fp32 VALU kernels) ------------------------------------
 // Every launcher of the token side takes T, the token rows per prompt: 5 output tokens (iou + 4 mask tokens) + the prompt's
-// points, 7 (a point and its pad token, or a box) or 8 (a point and a box).  A launch never mixes counts, and one launch
-// holds at most 112 token rows: decoder_max_prompts(T) prompts.
+// points, 7 (a point and its pad token, or a box), 8 (a point and a box), up to 15 (8 clicks and a box).  Every count has
+// its own instantiation of every kernel, a launch never mixes counts, and one launch holds at most 112 token rows:
+// decoder_max_prompts(T) prompts.
 constexpr int kDecoderMaxRows = 112;
-constexpr bool decoder_tokens_supported(int T) { return T == 7 || T == 8; }
+constexpr int kDecoderMaxPoints = 10;                       // 8 clicks + the two corners of a box
+constexpr int kDecoderMaxTokens = 5 + kDecoderMaxPoints;
+constexpr bool decoder_tokens_supported(int T) { return T >= 7 && T <= kDecoderMaxTokens; }
 constexpr int decoder_max_prompts(int T) { return kDecoderMaxRows / T; }
+// prompts per workgroup of the token-side kernels that take whole prompts (their slice of rows is at most 16)
+constexpr int decoder_prompt_slice(int T) { return T <= 8 ? 2 : 1; }
 // floats of workspace for the per-key-group partial results of token_to_image_partials
 size_t token_to_image_scratch_floats(int P, int T);
 // A [rows][256] fp32 token matrix as a consumer sees it: optionally LayerNorm'ed (over the 256 columns) and with another
@@ -178,10 +183,9 @@ struct TokenLinear {
     int relu = 0;
 };
 // The prompts of one decode (at most 16 per launch); the part a launch uses travels in the first kernel's arguments.  With
-// n = T - 5 points per prompt (2 or 3): coords [P][n][2] in the 1024-pixel frame, labels [P][n], both tightly packed, and per prompt the DEVICE address
+// n = T - 5 points per prompt (2 .. 10): coords [P][n][2] in the 1024-pixel frame, labels [P][n], both tightly packed, and per prompt the DEVICE address
 // of its image embedding ([4096][256] fp32).
 constexpr int kDecoderMaxPrompts = 16;
-constexpr int kDecoderMaxPoints = 3;
 struct DecoderPrompts {
     float coords[kDecoderMaxPrompts * kDecoderMaxPoints * 2];
     float labels[kDecoderMaxPrompts * kDecoderMaxPoints];

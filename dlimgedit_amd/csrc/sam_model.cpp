@@ -547,7 +547,7 @@ void SamModel::decode(float const* const* emb, float const* coords, float const*
     static_assert(5 + k::kDecoderMaxPoints == kDecMaxTokens && k::decoder_tokens_supported(kDecTokens) &&
                   k::decoder_tokens_supported(kDecMaxTokens), "the kernels are built for these token counts");
     reserve_decoder(count);
-    // the token-side kernels take at most 112 token rows per launch (16 prompts of 7 rows, 14 of 8): larger requests run
+    // the token-side kernels take at most 112 token rows per launch (16 prompts of 7 rows, 14 of 8, ... 7 of 15): larger requests run
     // in chunks that share the workspaces (stream order) and write their own part of logits() / iou()
     const int chunk = k::decoder_max_prompts(5 + points);
     for (int c0 = 0; c0 < count; c0 += chunk)

@@ -31,7 +31,7 @@ constexpr int kEmbedDim = 256;      // channels of the image embedding
 constexpr int kPatchK = 768;        // 3 * 16 * 16
 constexpr int kImageSize = 1024;    // /root/reference/src/segmentation.cpp:17
 constexpr int kDecTokens = 7;       // token rows of a two-point prompt (a point and its pad token, or a box): 5 + 2
-constexpr int kDecMaxTokens = 8;    // ... of a three-point prompt (a point and a box): the workspaces are sized by it
+constexpr int kDecMaxTokens = 15;   // ... of the largest prompt (8 clicks and a box, 10 points): the workspaces are sized by it
 constexpr int kLowRes = 256;
 
 struct LinearH {                    // f16 weight for MFMA GEMMs, fp32 bias
@@ -149,7 +149,7 @@ class SamModel {
     void encode(int batch, float* const* emb_dst = nullptr);
     float const* embeddings() const { return emb_.get(); }
 
-    // Decoder for `count` prompts of `points` points each (2 or 3: every prompt of a call has the same number, 5 + points
+    // Decoder for `count` prompts of `points` points each (2 .. 10: every prompt of a call has the same number, 5 + points
     // token rows). emb[i]: device embedding of prompt i's image; coords [count][points][2], labels [count][points] host
     // arrays. Results stay on device: logits() [count][4][256][256], iou() [count][4].
     void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2);

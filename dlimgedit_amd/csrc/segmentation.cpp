@@ -1,5 +1,6 @@
 #include "segmentation.hpp"
 
+#include "prompt_plan.hpp"
 #include "roctx.hpp"
 
 #include <algorithm>
@@ -49,13 +50,68 @@ int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* r
 }
 
 namespace {
-// prompt i of a batch call: points [count][2], regions [count][4], either or both
-void pack_batch_prompt(ResizeLongestSide const& rs, int const* points, int const* regions, int i, float* coords, float* labels) {
+// One prompt of a batch call (prompt_plan.hpp) from the call's arrays, points [count][2] and regions [count][4]: up to one
+// click it is pack_prompt's prompt; with more, the clicks in the order given with their labels, then the corners of the
+// box, or the padding point when there is none (SamOnnxModel._embed_points).  coords [points()][2], labels [points()].
+void pack_batch_prompt(ResizeLongestSide const& rs, PromptSpec const& spec, int const* points, int const* regions, float* coords,
+                       float* labels) {
+    const int i = spec.head;
     Point p;
     Region r;
-    if (points) p = Point{points[i * 2], points[i * 2 + 1]};
-    if (regions) r = Region{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
-    pack_prompt(rs, points ? &p : nullptr, regions ? &r : nullptr, coords, labels);
+    if (spec.clicks) p = Point{points[i * 2], points[i * 2 + 1]};
+    if (spec.box) r = Region{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
+    if (spec.clicks <= 1) {
+        pack_prompt(rs, spec.clicks ? &p : nullptr, spec.box ? &r : nullptr, coords, labels);
+        return;
+    }
+    auto set = [&](int index, Point q, int label) {
+        Point t = rs.transform(q);
+        coords[index * 2 + 0] = float(t.x);
+        coords[index * 2 + 1] = float(t.y);
+        labels[index] = float(label);
+    };
+    for (int c = 0; c < spec.clicks; ++c)
+        set(c, Point{points[(i + c) * 2], points[(i + c) * 2 + 1]}, click_label(spec, c, regions));
+    if (spec.box) {
+        set(spec.clicks, r.top_left, 2);
+        set(spec.clicks + 1, r.bottom_right, 3);
+    } else {
+        set(spec.clicks, Point{0, 0}, -1);
+    }
+}
+
+// The prompts of a batch call, packed: prompt j's points start at point at[j] of coords / labels.
+struct BatchPrompts {
+    std::vector<PromptSpec> prompts;
+    std::vector<size_t> at;
+    std::vector<float> coords, labels;
+};
+BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions) {
+    std::vector<char> has_handle(count);
+    for (int i = 0; i < count; ++i) has_handle[i] = segs[i] != nullptr;
+    BatchPrompts b;
+    b.prompts = plan_prompts(has_handle, points != nullptr, regions);
+    size_t total = 0;
+    for (PromptSpec const& p : b.prompts) {
+        b.at.push_back(total);
+        total += p.points();
+    }
+    b.coords.resize(total * 2);
+    b.labels.resize(total);
+    for (size_t j = 0; j < b.prompts.size(); ++j)
+        pack_batch_prompt(segs[b.prompts[j].head]->geometry(), b.prompts[j], points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
+    return b;
+}
+// the prompts of one chunk, tightly packed for SamModel::decode
+void gather_chunk(BatchPrompts const& b, PromptChunk const& chunk, std::vector<float>& cc, std::vector<float>& ll) {
+    const int npts = chunk.points;
+    cc.resize(chunk.prompts.size() * npts * 2);
+    ll.resize(chunk.prompts.size() * npts);
+    for (size_t j = 0; j < chunk.prompts.size(); ++j) {
+        const size_t at = b.at[chunk.prompts[j]];
+        std::copy_n(&b.coords[at * 2], npts * 2, &cc[j * npts * 2]);
+        std::copy_n(&b.labels[at], npts, &ll[j * npts]);
+    }
 }
 }  // namespace
 
@@ -456,29 +512,30 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
         for (int i = 0; i < 3; ++i) out_accuracy[i] = iou[i + 1];
 }
 
-// Prompts are grouped by the replica that holds their image's embedding; on each GPU they are cut into chunks of at most
-// kPromptChunk, each chunk decoded as one batch on the next lane, its masks copied out while the next chunk runs.
+// Prompts are grouped by the replica that holds their image's embedding; on each GPU they are grouped by their number of
+// points (a decoder launch holds one count) and cut into chunks of at most kPromptChunk prompts (prompt_plan.hpp), each chunk
+// decoded as one batch on the next lane, its masks copied out while the next chunk runs.
 void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                           int const* regions, uint8_t* const* out_masks) {
     if (count <= 0) return;
     DLIMG_ASSERT(points != nullptr || regions != nullptr);
-    const int npts = points && regions ? 3 : 2;          // points per prompt, the same for every entry of the call
     constexpr int kPromptChunk = 8;
-    EnvironmentImpl& env = segs[0]->env_;
-    std::vector<float> coords((size_t)count * npts * 2), labels((size_t)count * npts);
+    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
+    std::vector<PromptSpec> const& prompts = batch.prompts;
+    EnvironmentImpl& env = segs[prompts[0].head]->env_;
     std::vector<int> used;
-    for (int i = 0; i < count; ++i) {
-        DLIMG_ASSERT(&segs[i]->env_ == &env);
-        DLIMG_ASSERT(segs[i]->embedding_ != nullptr && out_masks[i] != nullptr);
-        segs[i]->settle();                       // prompts of a batch go to any lane: the embeddings are complete first
-        pack_batch_prompt(segs[i]->image_size_, points, regions, i, &coords[(size_t)i * npts * 2], &labels[(size_t)i * npts]);
-        if (std::find(used.begin(), used.end(), segs[i]->replica_) == used.end()) used.push_back(segs[i]->replica_);
+    for (PromptSpec const& p : prompts) {
+        SegmentationImpl const* seg = segs[p.head];
+        DLIMG_ASSERT(&seg->env_ == &env);
+        DLIMG_ASSERT(seg->embedding_ != nullptr && out_masks[p.head] != nullptr);
+        seg->settle();                           // prompts of a batch go to any lane: the embeddings are complete first
+        if (std::find(used.begin(), used.end(), seg->replica_) == used.end()) used.push_back(seg->replica_);
     }
     for_each_replica(env, used, [&](int replica) {
         HIP_CHECK(hipSetDevice(env.device_of(replica)));
         std::vector<int> mine;
-        for (int i = 0; i < count; ++i)
-            if (segs[i]->replica_ == replica) mine.push_back(i);
+        for (int j = 0; j < (int)prompts.size(); ++j)
+            if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
         struct Chunk { SamModel* model; SamModel::MaskSlot* slot; std::vector<k::PostJob> jobs; };
         std::vector<Chunk> chunks;
         auto finish = [&](Chunk& c) {
@@ -494,16 +551,12 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
             c.model->release_mask_slot(*slot);
         };
         try {
-            for (size_t base = 0; base < mine.size(); base += kPromptChunk) {
-                const int n = (int)std::min<size_t>(kPromptChunk, mine.size() - base);
+            std::vector<float> cc, ll;
+            for (PromptChunk const& part : plan_prompt_chunks(prompts, mine, kPromptChunk)) {
+                const int n = (int)part.prompts.size(), npts = part.points;
                 std::vector<float const*> emb(n);
-                std::vector<float> cc((size_t)n * npts * 2), ll((size_t)n * npts);
-                for (int j = 0; j < n; ++j) {
-                    const int i = mine[base + j];
-                    emb[j] = segs[i]->embedding_;
-                    std::copy_n(&coords[(size_t)i * npts * 2], npts * 2, &cc[(size_t)j * npts * 2]);
-                    std::copy_n(&labels[(size_t)i * npts], npts, &ll[(size_t)j * npts]);
-                }
+                for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
+                gather_chunk(batch, part, cc, ll);
                 SamModel& model = env.next_lane(replica);
                 // masks of a chunk are copied to the caller while the two chunks behind it are on the GPU
                 if (chunks.size() >= 3) finish(chunks[chunks.size() - 3]);
@@ -514,7 +567,7 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
                 std::lock_guard<std::mutex> lock(model.mutex());
                 model.decode(emb.data(), cc.data(), ll.data(), n, npts);
                 for (int j = 0; j < n; ++j) {
-                    const int i = mine[base + j];
+                    const int i = prompts[part.prompts[j]].head;
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
                     cur.jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
                                                   out_masks[i], o, r);
@@ -545,31 +598,33 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
     if (count <= 0) return;
     DLIMG_ASSERT(points != nullptr || regions != nullptr);
     DLIMG_ASSERT(dev_out != nullptr);
-    const int npts = points && regions ? 3 : 2;
     if (root_device < 0 || root_device >= EnvironmentImpl::device_count())
         throw Exception("root device " + std::to_string(root_device) + " is out of range: " +
                         std::to_string(EnvironmentImpl::device_count()) + " device(s) visible");
     constexpr int kPromptChunk = 8;
-    EnvironmentImpl& env = segs[0]->env_;
-    std::vector<float> coords((size_t)count * npts * 2), labels((size_t)count * npts);
+    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
+    std::vector<PromptSpec> const& prompts = batch.prompts;
+    EnvironmentImpl& env = segs[prompts[0].head]->env_;
+    // one mask and one offset per prompt, in head order; the continuation entries of a prompt repeat its offset
     std::vector<size_t> offsets(count);
     std::vector<int> used;
     size_t total = 0;
-    for (int i = 0; i < count; ++i) {
-        DLIMG_ASSERT(&segs[i]->env_ == &env);
-        DLIMG_ASSERT(segs[i]->embedding_ != nullptr);
-        segs[i]->settle();
-        pack_batch_prompt(segs[i]->image_size_, points, regions, i, &coords[(size_t)i * npts * 2], &labels[(size_t)i * npts]);
-        offsets[i] = total;
-        total += (size_t)segs[i]->image_size_.original.width * segs[i]->image_size_.original.height;
-        if (std::find(used.begin(), used.end(), segs[i]->replica_) == used.end()) used.push_back(segs[i]->replica_);
+    for (size_t j = 0; j < prompts.size(); ++j) {
+        SegmentationImpl const* seg = segs[prompts[j].head];
+        DLIMG_ASSERT(&seg->env_ == &env);
+        DLIMG_ASSERT(seg->embedding_ != nullptr);
+        seg->settle();
+        const int end = j + 1 < prompts.size() ? prompts[j + 1].head : count;
+        for (int i = prompts[j].head; i < end; ++i) offsets[i] = total;
+        total += (size_t)seg->image_size_.original.width * seg->image_size_.original.height;
+        if (std::find(used.begin(), used.end(), seg->replica_) == used.end()) used.push_back(seg->replica_);
     }
     if (out_offsets) std::copy(offsets.begin(), offsets.end(), out_offsets);
     for_each_replica(env, used, [&](int replica) {
         HIP_CHECK(hipSetDevice(env.device_of(replica)));
         std::vector<int> mine;
-        for (int i = 0; i < count; ++i)
-            if (segs[i]->replica_ == replica) mine.push_back(i);
+        for (int j = 0; j < (int)prompts.size(); ++j)
+            if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
         struct Chunk { SamModel* model; SamModel::MaskSlot* slot; };
         std::vector<Chunk> chunks;
         auto settle = [&](bool drain) {          // wait for every chunk, hand the slots back; first error wins
@@ -588,24 +643,20 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
             if (first) std::rethrow_exception(first);
         };
         try {
-            for (size_t base = 0; base < mine.size(); base += kPromptChunk) {
-                const int n = (int)std::min<size_t>(kPromptChunk, mine.size() - base);
+            std::vector<float> cc, ll;
+            for (PromptChunk const& part : plan_prompt_chunks(prompts, mine, kPromptChunk)) {
+                const int n = (int)part.prompts.size(), npts = part.points;
                 std::vector<float const*> emb(n);
-                std::vector<float> cc((size_t)n * npts * 2), ll((size_t)n * npts);
                 std::vector<k::PostJob> jobs(n);
-                for (int j = 0; j < n; ++j) {
-                    const int i = mine[base + j];
-                    emb[j] = segs[i]->embedding_;
-                    std::copy_n(&coords[(size_t)i * npts * 2], npts * 2, &cc[(size_t)j * npts * 2]);
-                    std::copy_n(&labels[(size_t)i * npts], npts, &ll[(size_t)j * npts]);
-                }
+                for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
+                gather_chunk(batch, part, cc, ll);
                 SamModel& model = env.next_lane(replica);
                 chunks.push_back(Chunk{&model, &model.acquire_mask_slot()});
                 roctx::Range range("dlimg.compute_masks_device");
                 std::lock_guard<std::mutex> lock(model.mutex());
                 model.decode(emb.data(), cc.data(), ll.data(), n, npts);
                 for (int j = 0; j < n; ++j) {
-                    const int i = mine[base + j];
+                    const int i = prompts[part.prompts[j]].head;
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
                     jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
                                               dev_out + offsets[i], o, r);

@@ -56,13 +56,16 @@ class SegmentationImpl {
     void compute_mask(Point const* point, Region const* region, uint8_t* const out_masks[3],
                       float out_accuracy[3]) const;
     // points XOR regions: entry i is a point or a box query.  Both: entry i is the box regions[i] refined by the foreground
-    // point points[i], one three-point prompt (pack_prompt); every entry of a call has the same number of points.
+    // point points[i], one three-point prompt (pack_prompt).  An entry whose segs[i] is null adds one more click to the prompt
+    // in front of it (prompt_plan.hpp: up to 8 clicks, foreground or background, with or without the box); its out_masks
+    // entry is not read.  Prompts of different sizes may share a call.
     static void compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                    int const* regions, uint8_t* const* out_masks);
 
     // Device-output form of compute_mask_batch: mask i is produced on the GPU that holds segs[i]'s embedding
     // and lands at dev_out + offset_i in the memory of HIP device `root_device` (offset_i = sum of width*height of the
-    // entries before it; also returned in out_offsets when given).  Returns when every mask is in place.
+    // prompts before it; also returned in out_offsets when given, a continuation entry repeating its prompt's).  Returns when
+    // every mask is in place.
     static void compute_mask_batch_device(SegmentationImpl const* const* segs, int count, int const* points,
                                           int const* regions, int root_device, uint8_t* dev_out, size_t* out_offsets);
 

@@ -117,7 +117,14 @@ typedef struct dlimg_Api {
      * foreground point points[i] -- SAM's combined prompt (point, top-left, bottom-right; labels 1, 2, 3; no
      * padding point), whose single mask is the decoder's output 0.  [get_segmentation_mask keeps the
      * reference's rule: given both, the point wins and the region is ignored.]  The same handle may
-     * appear several times (several prompts on one cached embedding). out_masks[i]: width*height bytes. */
+     * appear several times (several prompts on one cached embedding). out_masks[i]: width*height bytes.
+     * Several clicks per prompt: an entry whose segs[i] is NULL is a continuation entry -- points[i] is one more
+     * click of the prompt opened by the nearest entry with a handle in front of it, its label regions[4 i] (1
+     * foreground, 0 background; the other three ints 0), foreground when regions is NULL.  The head entry is read
+     * as above and its own click is a foreground click; in a call with continuation entries a head whose region
+     * is empty (x1 < x0) has no box.  A prompt has at most 8 clicks and gets ONE mask, out_masks of its head (the
+     * continuation entries' out_masks are not read and may be NULL).  Prompts of different sizes may share a call.
+     * Refused: more than 8 clicks, a continuation entry in front, a label other than 0 / 1. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;

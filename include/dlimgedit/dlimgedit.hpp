@@ -8,7 +8,7 @@
 // header need no rebuild at all because the C table underneath is layout-identical.
 //
 // Additions: Segmentation::process_batch and Segmentation::compute_mask_batch (batched entry
-// points of this build).  Requires C++17.  Define DLIMGEDIT_LOAD_DYNAMIC before including to bind
+// points of this build), Click and the compute_mask / compute_mask_batch forms that take several clicks per prompt.  Requires C++17.  Define DLIMGEDIT_LOAD_DYNAMIC before including to bind
 // the library at run time: dlsym "dlimg_init" yourself and pass the result to dlimg::initialize().
 #pragma once
 
@@ -18,6 +18,7 @@
 #include <cstddef>
 #include <exception>
 #include <memory>
+#include <optional>
 #include <string>
 #include <utility>
 #include <vector>
@@ -201,6 +202,12 @@ struct Region {
 constexpr bool operator==(Region a, Region b) { return a.top_left == b.top_left && a.bottom_right == b.bottom_right; }
 constexpr bool operator!=(Region a, Region b) { return !(a == b); }
 
+// One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
+struct Click {
+    Point point;
+    bool foreground = true;
+};
+
 // An encoded image (embedding resident in HBM) that answers mask queries cheaply.
 class Segmentation {
   public:
@@ -275,6 +282,54 @@ class Segmentation {
         static_assert(sizeof(Point) == 2 * sizeof(int) && sizeof(Region) == 4 * sizeof(int), "packed as the C table reads them");
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), points.empty() ? nullptr : &points.data()->x,
                                                    regions.empty() ? nullptr : &regions.data()->top_left.x, ptrs.data()));
+        return out;
+    }
+
+    // Click-to-refine (addition of this build): one mask from 1 .. 8 clicks -- the first one a foreground click -- and an
+    // optional box, as one prompt: the clicks in the order given, then the box.
+    Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt) const {
+        return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region})[0]);
+    }
+
+    // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
+    // optional box per prompt.
+    static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
+                                                 std::vector<std::vector<Click>> const& clicks,
+                                                 std::vector<std::optional<Region>> const& regions = {}) {
+        if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()))
+            throw Exception("compute_mask_batch: one list of clicks and at most one region per segmentation");
+        std::vector<Image> out;
+        bool refined = false;
+        for (size_t j = 0; j < segs.size(); ++j) {
+            if (clicks[j].empty() || clicks[j].size() > 8) throw Exception("compute_mask_batch: a prompt takes 1 to 8 clicks");
+            if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
+            refined = refined || clicks[j].size() > 1;
+            out.emplace_back(segs[j]->extent(), Channels::mask);
+        }
+        // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
+        // empty region, x1 < x0: none); every further click is an entry without a handle whose region holds its label.
+        // Without any further click the entries are plain point and box + point entries, where an empty region means nothing
+        // special: then the prompts without a box go in a call without regions, the others in one with both arrays.
+        for (int pass = 0; pass < (refined ? 1 : 2); ++pass) {
+            std::vector<dlimg_Segmentation> hs;
+            std::vector<Point> pts;
+            std::vector<Region> regs;
+            std::vector<uint8_t*> ptrs;
+            for (size_t j = 0; j < segs.size(); ++j) {
+                const bool box = !regions.empty() && regions[j].has_value();
+                if (!refined && box != (pass == 1)) continue;
+                for (size_t c = 0; c < clicks[j].size(); ++c) {
+                    hs.push_back(c == 0 ? segs[j]->handle_.get() : nullptr);
+                    pts.push_back(clicks[j][c].point);
+                    ptrs.push_back(c == 0 ? out[j].pixels() : nullptr);
+                    if (c == 0) regs.push_back(box ? *regions[j] : Region(Point{0, 0}, Point{-1, -1}));
+                    else regs.push_back(Region(Point{clicks[j][c].foreground ? 1 : 0, 0}, Point{0, 0}));
+                }
+            }
+            if (hs.empty()) continue;
+            detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), &pts.data()->x,
+                                                       (refined || pass == 1) ? &regs.data()->top_left.x : nullptr, ptrs.data()));
+        }
         return out;
     }
 
