@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import enum
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from pathlib import Path
 from typing import Optional, Sequence, Tuple
 
@@ -305,6 +305,7 @@ class Mask:
 MAX_CLICKS = 8               # clicks of one prompt (csrc/prompt_plan.hpp: kMaxClicks)
 TOKEN_ROWS_MAX = 112         # token rows of one decoder launch (csrc/kernels/kernels.hpp: kDecoderMaxRows)
 EMPTY_REGION = (0, 0, -1, -1)    # x1 < x0: "no box" for the head of a multi-click prompt
+REFINE_MARK = 4              # regions[4 i] of a refinement mark (dlimgedit.h: DLIMG_REFINE_MARK; csrc/prompt_plan.hpp: kRefineMark)
 
 
 @dataclass
@@ -314,20 +315,32 @@ class ClickEntries:
     four ints regions[i] -- the box of a head (EMPTY_REGION: none), (label, 0, 0, 0) of a continuation entry.
     prompt_heads[j] is the entry that opened prompt j, token_rows[j] its token rows in the decoder (6 + clicks, 7 + clicks with
     a box), and launches the decoder launches of one GPU: [(token rows, [prompt indices])], prompts grouped by their token
-    rows in order of first appearance and cut at the 112 rows a launch holds."""
+    rows in order of first appearance and cut at the 112 rows a launch holds.
+    A refinement mark is a continuation entry (REFINE_MARK, 0, 0, 0) whose point is not read.  stage_clicks[j]: the clicks each
+    stage of prompt j takes (one stage without marks; token_rows[j] are the last stage's).  A prompt with marks is decoded
+    behind the others, one launch per stage."""
     heads: list
     points: list
     regions: list
     prompt_heads: list
     token_rows: list
+    stage_clicks: list = field(default_factory=list)
+
+    def _staged(self, j) -> bool:
+        return j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1
 
     @property
     def launches(self) -> list:
         out = []
-        for t in dict.fromkeys(self.token_rows):
-            group = [j for j, tj in enumerate(self.token_rows) if tj == t]
+        plain = [j for j in range(len(self.token_rows)) if not self._staged(j)]
+        for t in dict.fromkeys(self.token_rows[j] for j in plain):
+            group = [j for j in plain if self.token_rows[j] == t]
             cut = TOKEN_ROWS_MAX // t
             out += [(t, group[k:k + cut]) for k in range(0, len(group), cut)]
+        for j in range(len(self.token_rows)):
+            if self._staged(j):
+                box_rows = self.token_rows[j] - self.stage_clicks[j][-1]
+                out += [(box_rows + k, [j]) for k in self.stage_clicks[j]]
         return out
 
 
@@ -363,21 +376,47 @@ def _checked_clicks(clicks, labels):
     return clicks, labels
 
 
-def click_entries(clicks, labels=None, regions=None) -> ClickEntries:
+def _checked_marks(n_clicks: int, refine_after) -> list:
+    """`refine_after` of one prompt -> the click counts behind which a refinement mark goes: None: none; "each": one behind
+    every click but the last (SAM's interactive loop); else click counts k, strictly increasing, 1 <= k < the prompt's clicks."""
+    if refine_after is None:
+        return []
+    if isinstance(refine_after, str):
+        if refine_after != "each":
+            raise Error('refine_after is a sequence of click counts or "each"')
+        return list(range(1, n_clicks))
+    ks = [int(k) for k in refine_after]
+    if any(k < 1 or k >= n_clicks for k in ks):
+        raise Error(f"refine_after: a mark goes behind the first k clicks, 1 <= k < {n_clicks} (every stage adds at least one click)")
+    if any(b <= a for a, b in zip(ks, ks[1:])):
+        raise Error("refine_after: the click counts are strictly increasing (no mark directly after another)")
+    return ks
+
+
+def click_entries(clicks, labels=None, regions=None, refine_after=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
-    labels[j] their labels (None: all foreground), regions[j] its box or None.  Pure host code."""
+    labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
+    prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
+    decoded in stages, each taking the low-res logits of the one before it as SAM's mask input.  Pure host code."""
     n = len(clicks)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
-    if len(labels) != n or len(regions) != n:
-        raise Error("one list of labels and one region (or None) per prompt")
+    refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
+    if len(labels) != n or len(regions) != n or len(refine_after) != n:
+        raise Error("one list of labels, one region (or None) and one refine_after (or None) per prompt")
     out = ClickEntries([], [], [], [], [])
     for j in range(n):
         cs, ls = _checked_clicks(clicks[j], labels[j])
+        marks = _checked_marks(len(cs), refine_after[j])
         r = regions[j]
         out.prompt_heads.append(len(out.heads))
         out.token_rows.append(5 + len(cs) + (2 if r is not None else 1))
+        out.stage_clicks.append(marks + [len(cs)])
         for k, (c, lab) in enumerate(zip(cs, ls)):
+            if k in marks:               # a mark behind the first k clicks: in front of click k (0-based)
+                out.heads.append(None)
+                out.points.append((0, 0))
+                out.regions.append((REFINE_MARK, 0, 0, 0))
             out.heads.append(j if k == 0 else None)
             out.points.append((c.x, c.y))
             if k:
@@ -466,21 +505,29 @@ class Segmentation:
         return [Mask(m, a) for m, a in zip(masks, acc)]
 
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
-                            region: Optional[Region] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+                            region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
-        an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0."""
+        an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
+        refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
+        them: the first k clicks give a mask whose low-res logits are the mask input of the next stage (on the GPU), and so on;
+        the mask of the last stage is returned.  Needs a model with the mask branch (pe.mask.*)."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
-                                               out=None if out is None else [out])[0]
+                                               out=None if out is None else [out],
+                                               refine_after=None if refine_after is None else [refine_after])[0]
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
-                           clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None) -> list:
+                           clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
         `clicks` instead of `points`: prompt i is the clicks clicks[i] (1 .. 8) with labels[i] (1 / 0; None: foreground) and
-        the box regions[i] (None: no box); prompts of different sizes may share the call (click_entries builds the lists)."""
+        the box regions[i] (None: no box); prompts of different sizes may share the call (click_entries builds the lists).
+        refine_after (with `clicks`): per prompt None, "each" or click counts, or one "each" for all -- refinement marks, see
+        compute_mask_clicks."""
+        if refine_after is not None and clicks is None:
+            raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
             if points is not None:
                 raise Error("compute_mask_batch: `points` or `clicks`, not both")
@@ -488,7 +535,7 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
-            entries = click_entries(clicks, labels, regions)
+            entries = click_entries(clicks, labels, regions, refine_after)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
@@ -802,16 +849,18 @@ class ext:
 
     @classmethod
     def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0, clicks=None,
-                                  labels=None) -> list:
+                                  labels=None, refine_after=None) -> list:
         """Device-output form of Segmentation.compute_mask_batch (points, regions or both, or clicks / labels / regions, as
         there): masks land tightly packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their
-        embeddings live; returns the byte offset of every mask."""
+        embeddings live; returns the byte offset of every mask.  refine_after: as there."""
+        if refine_after is not None and clicks is None:
+            raise Error("compute_mask_batch_device: refine_after goes with `clicks`")
         if clicks is not None:
             if points is not None:
                 raise Error("compute_mask_batch_device: `points` or `clicks`, not both")
             if len(clicks) != len(segs):
                 raise Error("compute_mask_batch_device: one list of clicks per segmentation")
-            entries = click_entries(clicks, labels, regions)
+            entries = click_entries(clicks, labels, regions, refine_after)
             calls = _entry_calls(entries)
             if len(calls) > 1:      # one-click prompts with and without a box: a call each, so that the masks stay in order
                 calls = [([i], entries.regions[i] != EMPTY_REGION) for i in range(len(entries.heads))]

@@ -850,8 +850,28 @@ static_assert(sizeof(DecoderStart<7>) <= 2048 && sizeof(DecoderStart<8>) <= 2048
               sizeof(DecoderStart<10>) <= 2048 && sizeof(DecoderStart<11>) <= 2048 && sizeof(DecoderStart<12>) <= 2048 &&
               sizeof(DecoderStart<13>) <= 2048 && sizeof(DecoderStart<14>) <= 2048 && sizeof(DecoderStart<15>) <= 2048,
               "the prompts travel as kernel arguments");
+// A masked launch (SAM's mask_input: the previous step's low-res logits through the prompt encoder's mask branch,
+// mask_embed_kernel below) initialises the keys as  emb + proj.b + h[token] . proj.w  instead of  emb + no_mask : the dense
+// embedding SAM adds to the image embedding is the last 1x1 convolution of the branch (16 -> 256), applied here to the 16
+// values of the token, so it never exists as a [4096][256] tensor.  Same single f16 rounding of the sum as the unmasked
+// form.  MASKED is a template parameter: the unmasked instantiations take DecoderStart<TOK> and keep their code; a launch
+// never mixes masked and unmasked prompts.
+constexpr int MASK_HID = k::kMaskHidden;
 template <int TOK>
-__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart<TOK> a) {
+struct DecoderStartMasked : DecoderStart<TOK> {
+    const float* h[StartPrompts<TOK>::MAXP];     // per prompt: [4096][16] fp32
+    const float* proj_w;                         // [256][16]
+    const float* proj_b;                         // [256]
+};
+static_assert(sizeof(DecoderStartMasked<7>) <= 2560 && sizeof(DecoderStartMasked<8>) <= 2560 && sizeof(DecoderStartMasked<9>) <= 2560 &&
+              sizeof(DecoderStartMasked<10>) <= 2560 && sizeof(DecoderStartMasked<11>) <= 2560 && sizeof(DecoderStartMasked<12>) <= 2560 &&
+              sizeof(DecoderStartMasked<13>) <= 2560 && sizeof(DecoderStartMasked<14>) <= 2560 && sizeof(DecoderStartMasked<15>) <= 2560,
+              "the prompts travel as kernel arguments");
+template <int TOK, bool MASKED>
+using DecoderStartArgs = std::conditional_t<MASKED, DecoderStartMasked<TOK>, DecoderStart<TOK>>;
+
+template <int TOK, bool MASKED = false>
+__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStartArgs<TOK, MASKED> a) {
     __shared__ __attribute__((aligned(16))) float rows[TL_ROW_SLICE<TOK> * DIM];
     const int c = threadIdx.x;
     if ((int)blockIdx.x < a.P) {
@@ -885,12 +905,135 @@ __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStart<TOK> a)
     const int P = a.P, skip = a.P + a.lin_blocks;
     const size_t total = n4_per_prompt * P;
     const size_t nblk = gridDim.x - skip;
+    if constexpr (MASKED) {
+        // element i is columns 4 (i % 64) .. + 3 of token (i / 64) % 4096; the stride of the loop and n4_per_prompt are
+        // multiples of 64, so a thread keeps its four columns -- and their 4 x 16 weights -- for all of its elements
+        const int c4 = threadIdx.x & (DIM / 4 - 1);
+        float4_t w[4][MASK_HID / 4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int q = 0; q < MASK_HID / 4; ++q)
+                w[e][q] = reinterpret_cast<const float4_t*>(a.proj_w)[(c4 * 4 + e) * (MASK_HID / 4) + q];
+        const float4_t bias = reinterpret_cast<const float4_t*>(a.proj_b)[c4];
+        for (size_t i = (blockIdx.x - skip) * (size_t)blockDim.x + threadIdx.x; i < total; i += nblk * blockDim.x) {
+            const size_t p = i / n4_per_prompt, j = i % n4_per_prompt;
+            const float4_t* __restrict__ hrow = reinterpret_cast<const float4_t*>(a.h[p]) + (j / (DIM / 4)) * (MASK_HID / 4);
+            float4_t d = bias;
+#pragma unroll
+            for (int q = 0; q < MASK_HID / 4; ++q) {
+                const float4_t hv = hrow[q];
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    d[e] = fmaf(hv[0], w[e][q][0], fmaf(hv[1], w[e][q][1], fmaf(hv[2], w[e][q][2], fmaf(hv[3], w[e][q][3], d[e]))));
+            }
+            const float4_t v = reinterpret_cast<const float4_t*>(a.prompts.emb[p])[j] + d;
+            reinterpret_cast<float4_t*>(keys)[i] = v;
+            reinterpret_cast<half4_t*>(keys_h)[i] = half4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+        }
+        return;
+    }
     for (size_t i = (blockIdx.x - skip) * (size_t)blockDim.x + threadIdx.x; i < total; i += nblk * blockDim.x) {
         const size_t p = i / n4_per_prompt, j = i % n4_per_prompt;
         float4_t v = reinterpret_cast<const float4_t*>(a.prompts.emb[p])[j];
         v += reinterpret_cast<const float4_t*>(no_mask)[j % (DIM / 4)];
         reinterpret_cast<float4_t*>(keys)[i] = v;
         reinterpret_cast<half4_t*>(keys_h)[i] = half4_t{(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The prompt encoder's mask branch up to its last convolution (SAM: mask_downscaling[0..5]): low-res logits [256][256] ->
+// conv 2x2 / 2 (1 -> 4) -> LayerNorm2d -> GELU -> conv 2x2 / 2 (4 -> 16) -> LayerNorm2d -> GELU, one value set h[token][16]
+// per token of the 64 x 64 grid.  The last convolution (1x1, 16 -> 256) is applied by the masked decoder_start_kernel.
+// One thread per token, 16 workgroups of 256 per prompt: a token's receptive field is its own 4 x 4 block of logits, read as
+// four aligned 16-byte loads; the 332 weights go through LDS (broadcast reads); everything else lives in registers.  The
+// plane is chosen here from the IoU predictions with post-processing's rule (postprocess.hip), so the logits are read
+// where the decode left them.  fp32 throughout, exact (erf) GELU.
+struct MaskEmbedArgs {
+    k::MaskSource src[k::kDecoderMaxPrompts];
+    k::MaskBranch w;
+    float* h;                                    // [P][4096][16]
+};
+constexpr int ME_W1 = 0, ME_B1 = 16, ME_G1 = 20, ME_H1 = 24, ME_W2 = 28, ME_B2 = ME_W2 + 256, ME_G2 = ME_B2 + 16, ME_H2 = ME_G2 + 16,
+              ME_WEIGHTS = ME_H2 + 16;
+__global__ __launch_bounds__(256) void mask_embed_kernel(MaskEmbedArgs a) {
+    __shared__ __attribute__((aligned(16))) float w[ME_WEIGHTS];
+    {
+        const int t = threadIdx.x;
+        w[ME_W2 + t] = a.w.w2[t];
+        if (t < 16) {
+            w[ME_W1 + t] = a.w.w1[t];
+            w[ME_B2 + t] = a.w.b2[t];
+            w[ME_G2 + t] = a.w.ln2_w[t];
+            w[ME_H2 + t] = a.w.ln2_b[t];
+        }
+        if (t < 4) {
+            w[ME_B1 + t] = a.w.b1[t];
+            w[ME_G1 + t] = a.w.ln1_w[t];
+            w[ME_H1 + t] = a.w.ln1_b[t];
+        }
+    }
+    const int p = blockIdx.y;
+    const k::MaskSource src = a.src[p];
+    const float* low = src.logits4;
+    if (src.iou4) {
+        // SamOnnxModel.select_masks with two prompt points, as postprocess_kernel chooses
+        float best = __fadd_rn(src.iou4[0], __fmul_rn(-0.5f, 1000.0f));
+        int bi = 0;
+#pragma unroll
+        for (int i = 1; i < 4; ++i)
+            if (src.iou4[i] > best) { best = src.iou4[i]; bi = i; }
+        low += (size_t)bi * 256 * 256;
+    }
+    const int token = blockIdx.x * 256 + threadIdx.x;            // 16 x 256 = 4096: no tail
+    const int ty = token >> 6, tx = token & 63;
+    float4_t rows[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rows[r] = *reinterpret_cast<const float4_t*>(low + (size_t)(4 * ty + r) * 256 + 4 * tx);
+    __syncthreads();
+    float acc[MASK_HID];
+#pragma unroll
+    for (int o = 0; o < MASK_HID; ++o) acc[o] = w[ME_B2 + o];
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            // first convolution at (2 ty + dy, 2 tx + dx): the 2 x 2 logits at rows 2 dy, 2 dy + 1, columns 2 dx, 2 dx + 1
+            const float x00 = rows[2 * dy][2 * dx], x01 = rows[2 * dy][2 * dx + 1], x10 = rows[2 * dy + 1][2 * dx],
+                        x11 = rows[2 * dy + 1][2 * dx + 1];
+            float y[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                y[c] = fmaf(x00, w[ME_W1 + 4 * c], fmaf(x01, w[ME_W1 + 4 * c + 1], fmaf(x10, w[ME_W1 + 4 * c + 2],
+                       fmaf(x11, w[ME_W1 + 4 * c + 3], w[ME_B1 + c]))));
+            const float mean = ((y[0] + y[1]) + (y[2] + y[3])) * 0.25f;
+            float var = 0.f;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { y[c] -= mean; var = fmaf(y[c], y[c], var); }
+            const float rstd = 1.0f / sqrtf(var * 0.25f + 1e-6f);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const float g = gelu_erf(fmaf(y[c] * rstd, w[ME_G1 + c], w[ME_H1 + c]));
+#pragma unroll
+                for (int o = 0; o < MASK_HID; ++o) acc[o] = fmaf(g, w[ME_W2 + ((o * 4 + c) * 2 + dy) * 2 + dx], acc[o]);
+            }
+        }
+    float mean = 0.f;
+#pragma unroll
+    for (int o = 0; o < MASK_HID; ++o) mean += acc[o];
+    mean *= 1.0f / MASK_HID;
+    float var = 0.f;
+#pragma unroll
+    for (int o = 0; o < MASK_HID; ++o) { acc[o] -= mean; var = fmaf(acc[o], acc[o], var); }
+    const float rstd = 1.0f / sqrtf(var * (1.0f / MASK_HID) + 1e-6f);
+    float4_t* dst = reinterpret_cast<float4_t*>(a.h + ((size_t)p * NTOK_IMG + token) * MASK_HID);
+#pragma unroll
+    for (int q = 0; q < MASK_HID / 4; ++q) {
+        float4_t v;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_erf(fmaf(acc[4 * q + e] * rstd, w[ME_G2 + 4 * q + e], w[ME_H2 + 4 * q + e]));
+        dst[q] = v;
     }
 }
 
@@ -908,12 +1051,20 @@ static_assert(k::kDecoderMaxTokens == 15, "DLIMG_FOR_TOKENS names every supporte
 
 namespace k {
 
-void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                   const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+namespace {
+// mask: null for the unmasked launch; else the per-prompt h rows and the branch's last convolution
+struct StartMask { const float* const* h; const float* proj_w; const float* proj_b; };
+void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
+                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
+                          const float* no_mask, const StartMask* mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
     if (P <= 0) return;
     if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 to 15 tokens per prompt");
     if (P > decoder_max_prompts(T) || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
+    if (mask) {
+        if (!mask->h || !mask->proj_w || !mask->proj_b) throw_error("decoder_start: a masked launch needs the mask branch's rows and weights");
+        for (int i = 0; i < P; ++i)
+            if (!mask->h[i]) throw_error("decoder_start: a launch never mixes masked and unmasked prompts");
+    }
     const size_t n4 = (size_t)NTOK_IMG * DIM / 4;
     const size_t total = n4 * P;
     const int key_blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
@@ -923,9 +1074,9 @@ void decoder_start(const DecoderPrompts& prompts, const float* gauss, const floa
             throw_error("decoder_start: the first linears take the plain 256-wide token rows");
         cols += first[i].N / 4;
     }
-    DLIMG_FOR_TOKENS(T, "decoder_start",
-        DecoderStart<TOK> a{};
-        constexpr int NPTS = StartPrompts<TOK>::NPTS;
+    auto fill = [&](auto& a) {
+        using Args = std::remove_reference_t<decltype(a)>;
+        constexpr int NPTS = decltype(Args::prompts)::NPTS;
         std::memcpy(a.prompts.coords, prompts.coords, (size_t)P * NPTS * 2 * sizeof(float));
         std::memcpy(a.prompts.labels, prompts.labels, (size_t)P * NPTS * sizeof(float));
         for (int i = 0; i < P; ++i) a.prompts.emb[i] = prompts.emb[i];
@@ -935,9 +1086,53 @@ void decoder_start(const DecoderPrompts& prompts, const float* gauss, const floa
         a.first.rows = P * T;
         for (int i = 0; i < n_first; ++i) a.first.op[i] = first[i];
         a.lin_cols = cols > 0 ? cols : 1;
-        a.lin_blocks = cols * ((P + TL_PROMPT_SLICE<TOK> - 1) / TL_PROMPT_SLICE<TOK>);
+        a.lin_blocks = cols * ((P + decoder_prompt_slice(T) - 1) / decoder_prompt_slice(T));
         a.no_mask = no_mask; a.keys = keys; a.keys_h = keys_h; a.n4_per_prompt = n4; a.P = P;
-        hipLaunchKernelGGL(decoder_start_kernel<TOK>, dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);)
+    };
+    DLIMG_FOR_TOKENS(T, "decoder_start",
+        static_assert(TL_PROMPT_SLICE<TOK> == decoder_prompt_slice(TOK), "fill() cuts the first linears as the kernel does");
+        if (mask) {
+            DecoderStartMasked<TOK> a{};
+            fill(a);
+            for (int i = 0; i < P; ++i) a.h[i] = mask->h[i];
+            a.proj_w = mask->proj_w; a.proj_b = mask->proj_b;
+            hipLaunchKernelGGL((decoder_start_kernel<TOK, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
+        } else {
+            DecoderStart<TOK> a{};
+            fill(a);
+            hipLaunchKernelGGL((decoder_start_kernel<TOK, false>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
+        })
+}
+}  // namespace
+
+void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
+                   const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
+                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+    launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, no_mask, nullptr, keys,
+                         keys_h, P, T, s);
+}
+
+void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
+                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
+                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+    const StartMask mask{h, branch.proj_w, branch.proj_b};
+    launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, nullptr, &mask, keys,
+                         keys_h, P, T, s);
+}
+
+void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h, int P, hipStream_t s) {
+    if (P <= 0) return;
+    if (P > kDecoderMaxPrompts) throw_error("mask_embed: too many prompts for one launch");
+    if (!h || !branch.w1 || !branch.b1 || !branch.ln1_w || !branch.ln1_b || !branch.w2 || !branch.b2 || !branch.ln2_w || !branch.ln2_b)
+        throw_error("mask_embed: the model has no mask branch (pe.mask.*)");
+    MaskEmbedArgs a{};
+    for (int i = 0; i < P; ++i) {
+        if (!src[i].logits4 || ((uintptr_t)src[i].logits4 & 15)) throw_error("mask_embed: every prompt needs 16-byte aligned logits");
+        a.src[i] = src[i];
+    }
+    a.w = branch;
+    a.h = h;
+    hipLaunchKernelGGL(mask_embed_kernel, dim3(NTOK_IMG / 256, P), dim3(256), 0, s, a);
 }
 
 size_t token_to_image_scratch_floats(int P, int T) { return (size_t)P * HEADS * T * T2I_PARTS * 18; }

@@ -197,6 +197,27 @@ struct DecoderPrompts {
 void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
                    const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s);
+// Mask input (SAM's click-to-refine loop: the low-res logits of the previous step through the prompt encoder's mask branch).
+// MaskBranch: the branch's tensors as the model file holds them, fp32 -- conv 2x2 / 2 w1 [4][1][2][2], b1 [4]; LayerNorm2d
+// ln1 [4]; conv 2x2 / 2 w2 [16][4][2][2], b2 [16]; LayerNorm2d ln2 [16]; 1x1 conv proj_w [256][16], proj_b [256].
+// MaskSource: where one prompt's mask input lies -- the four planes [4][256][256] a decode left and, when the plane is the
+// best of 1..3 by the IoU predictions (the single-mask rule of a two-point prompt, chosen on the device), those four
+// predictions; iou4 == nullptr: plane 0.
+constexpr int kMaskHidden = 16;
+struct MaskBranch {
+    const float* w1 = nullptr; const float* b1 = nullptr; const float* ln1_w = nullptr; const float* ln1_b = nullptr;
+    const float* w2 = nullptr; const float* b2 = nullptr; const float* ln2_w = nullptr; const float* ln2_b = nullptr;
+    const float* proj_w = nullptr; const float* proj_b = nullptr;
+};
+struct MaskSource { const float* logits4; const float* iou4; };
+// h[p][token][16] = GELU(LN2d(conv2(GELU(LN2d(conv1(plane of src[p])))))) for P prompts (src: host array): everything of the
+// branch but its last convolution.  One launch, 16 workgroups per prompt.
+void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h /*[P][4096][16]*/, int P, hipStream_t);
+// decoder_start for prompts that all have a mask input: keys = emb[p] + proj_b + h[p][token] . proj_w (fp32 + f16) instead
+// of emb[p] + no_mask, which SAM's dense embedding replaces.  h: host array of P device pointers ([4096][16] each).
+void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
+                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
+                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s);
 // up to 5 layers over the same rows (<= 112, whole prompts of T rows) in one launch
 void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t);
 // self-attention among the T tokens of each prompt + its output projection `out` (K = 256) in one launch

@@ -14,6 +14,14 @@
 // count (groups in the order their first prompt appears, prompts in the caller's order inside a group) and every group is
 // cut into chunks of `chunk` prompts, each chunk one decode on the next lane.  Prompts, never entries, are counted, so a
 // prompt is never cut; a call whose prompts all have one count is cut as it always was.
+//
+// Marks -> stages (plan_staged_prompts).  A continuation entry whose four ints are {kRefineMark, 0, 0, 0} is a refinement
+// mark, not a click: its point is not read and it does not count towards the 8 clicks.  A prompt with m marks is decoded in
+// m + 1 stages: stage j takes the clicks in front of mark j (the head's included), the last stage all of them, every stage
+// the prompt's box (or the padding point), packed exactly as an unmarked prompt of those clicks; from the second stage on a
+// stage takes the low-res logits of the stage before it as SAM's mask input.  Every stage adds at least one click: a mark
+// directly after a mark, and a mark as the last entry of a prompt, are refused.  plan_prompts itself knows no marks: the
+// value 4 is one more label it refuses.
 #pragma once
 
 #include <stdexcept>
@@ -23,6 +31,7 @@
 namespace dlimg {
 
 constexpr int kMaxClicks = 8;
+constexpr int kRefineMark = 4;       // regions[4 i] of a mark: the first value SAM's labels (-1 pad, 0 / 1 clicks, 2 / 3 corners) leave free
 
 struct PromptSpec {
     int head = 0;            // entry that opened the prompt (its handle, its out_masks, its region)
@@ -75,6 +84,99 @@ struct PromptChunk {
     int points = 0;                  // packed points of every prompt of the chunk
     std::vector<int> prompts;        // indices into the call's prompt list, caller's order
 };
+
+// The stages of one prompt of a call that may hold marks.  click_entry[c]: the entry click c travels in (the head for c = 0;
+// marks skipped, so the clicks of a marked prompt are not consecutive entries); stage_clicks[j]: the clicks stage j takes,
+// strictly increasing, the last one == PromptSpec::clicks.  A prompt without marks has one stage.
+struct PromptStages {
+    std::vector<int> click_entry;
+    std::vector<int> stage_clicks;
+    bool staged() const { return stage_clicks.size() > 1; }
+};
+struct StagedPrompts {
+    std::vector<PromptSpec> prompts;
+    std::vector<PromptStages> stages;        // [prompt]
+};
+
+inline bool is_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kRefineMark; }
+
+// plan_prompts for a call that may hold marks; without one it is plan_prompts (same prompts, same refusals).  mask_branch: the
+// model has the prompt encoder's mask branch (pe.mask.*), without which no stage can take a mask input.
+inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
+    const int count = (int)has_handle.size();
+    bool any_mark = false;
+    for (int i = 0; i < count; ++i) any_mark |= !has_handle[i] && is_mark_entry(regions, i);
+    StagedPrompts out;
+    if (!any_mark) {
+        out.prompts = plan_prompts(has_handle, points_given, regions);
+        for (PromptSpec const& p : out.prompts) {
+            PromptStages s;
+            for (int c = 0; c < p.clicks; ++c) s.click_entry.push_back(p.head + c);
+            s.stage_clicks.push_back(p.clicks);
+            out.stages.push_back(s);
+        }
+        return out;
+    }
+    // the call without its marks is an ordinary call, which plan_prompts reads (a marked prompt has two clicks or more, so
+    // the call keeps a continuation entry and with it the reading of an empty region as "no box")
+    std::vector<char> handles;
+    std::vector<int> ints, entry_of;
+    bool last_was_mark = false;
+    for (int i = 0; i < count; ++i) {
+        const bool mark = !has_handle[i] && is_mark_entry(regions, i);
+        if (mark) {
+            const int* r = regions + 4 * i;
+            const std::string who = "mask batch: entry " + std::to_string(i) + ": a refinement mark ";
+            if (r[1] != 0 || r[2] != 0 || r[3] != 0) throw std::invalid_argument(who + "is {4, 0, 0, 0} in regions[4 i ..]: the other three ints are 0");
+            if (!mask_branch)
+                throw std::invalid_argument(who + "needs the prompt encoder's mask branch, and the model file has no pe.mask.* tensors");
+            if (handles.empty()) throw std::invalid_argument(who + "needs a prompt in front of it");
+            if (last_was_mark) throw std::invalid_argument(who + "directly follows another mark: every stage adds at least one click");
+            if (i + 1 == count || has_handle[i + 1])
+                throw std::invalid_argument(who + "is the last entry of its prompt: every stage adds at least one click");
+        } else {
+            handles.push_back(has_handle[i]);
+            ints.insert(ints.end(), regions + 4 * i, regions + 4 * i + 4);
+            entry_of.push_back(i);
+        }
+        last_was_mark = mark;
+    }
+    std::vector<PromptSpec> packed;
+    try {
+        packed = plan_prompts(handles, points_given, ints.data());
+    } catch (std::invalid_argument const& e) {
+        // plan_prompts numbers the entries of the list without marks: name the caller's entry instead
+        std::string msg = e.what();
+        const std::string key = "entry ";
+        const size_t at = msg.find(key);
+        if (at != std::string::npos) {
+            size_t end = at + key.size();
+            while (end < msg.size() && msg[end] >= '0' && msg[end] <= '9') ++end;
+            if (end > at + key.size()) {
+                const size_t n = std::stoul(msg.substr(at + key.size(), end - at - key.size()));
+                if (n < entry_of.size()) msg = msg.substr(0, at + key.size()) + std::to_string(entry_of[n]) + msg.substr(end);
+            }
+        }
+        throw std::invalid_argument(msg);
+    }
+    for (PromptSpec p : packed) {
+        PromptStages s;
+        for (int c = 0; c < p.clicks; ++c) s.click_entry.push_back(entry_of[p.head + c]);
+        p.head = entry_of[p.head];
+        // the marks of this prompt: the entries between its clicks
+        for (int c = 1; c < p.clicks; ++c)
+            if (s.click_entry[c] != s.click_entry[c - 1] + 1) s.stage_clicks.push_back(c);
+        s.stage_clicks.push_back(p.clicks);
+        out.prompts.push_back(p);
+        out.stages.push_back(s);
+    }
+    return out;
+}
+
+// label of click c of a prompt that may hold marks
+inline int staged_click_label(PromptStages const& s, int c, int const* regions) {
+    return (c == 0 || !regions) ? 1 : regions[4 * s.click_entry[c]];
+}
 
 // `mine`: the prompts (indices) one GPU decodes, in the caller's order
 inline std::vector<PromptChunk> plan_prompt_chunks(std::vector<PromptSpec> const& prompts, std::vector<int> const& mine, int chunk) {

@@ -541,8 +541,10 @@ void SamModel::reserve_decoder(int count) {
     dec_count_ = count;
 }
 
-void SamModel::decode(float const* const* emb, float const* coords, float const* labels, int count, int points) {
+void SamModel::decode(float const* const* emb, float const* coords, float const* labels, int count, int points,
+                      k::MaskSource const* mask_input) {
     DLIMG_ASSERT(count > 0);
+    if (mask_input && !has_mask_branch()) throw Exception("a mask input needs the prompt encoder's mask branch: the model file has no pe.mask.* tensors");
     DLIMG_ASSERT(points >= 2 && points <= k::kDecoderMaxPoints);
     static_assert(5 + k::kDecoderMaxPoints == kDecMaxTokens && k::decoder_tokens_supported(kDecTokens) &&
                   k::decoder_tokens_supported(kDecMaxTokens), "the kernels are built for these token counts");
@@ -550,14 +552,23 @@ void SamModel::decode(float const* const* emb, float const* coords, float const*
     // the token-side kernels take at most 112 token rows per launch (16 prompts of 7 rows, 14 of 8, ... 7 of 15): larger requests run
     // in chunks that share the workspaces (stream order) and write their own part of logits() / iou()
     const int chunk = k::decoder_max_prompts(5 + points);
+    if (mask_input) {
+        // a later chunk's mask input must not be this call's own output of an earlier chunk
+        DLIMG_ASSERT(count <= chunk);
+        const size_t need = (size_t)count * kTokens * k::kMaskHidden;    // 256 KB per prompt of the launch
+        if (need > mask_h_.capacity()) {
+            HIP_CHECK(hipStreamSynchronize(stream_));                    // an earlier masked decode may still read the old one
+            mask_h_.reserve(need);
+        }
+    }
     for (int c0 = 0; c0 < count; c0 += chunk)
         decode_chunk(emb + c0, coords + (size_t)c0 * points * 2, labels + (size_t)c0 * points, std::min(chunk, count - c0), c0,
-                     points);
+                     points, mask_input ? mask_input + c0 : nullptr);
     mark_activity();
 }
 
 void SamModel::decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first,
-                            int points) {
+                            int points, k::MaskSource const* mask_input) {
     SamWeights const& W = *weights_;
     const int TOK = 5 + points;                      // token rows per prompt
     const int P = count, M = P * kTokens, T = P * TOK;
@@ -605,6 +616,16 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             DecoderLayer const& L = W.dec_[0];
             k::TokenLinear qkv[3] = {lin({}, 256, L.self_attn.q, {}, sq_.get(), 0), lin({}, 256, L.self_attn.k, {}, sk_.get(), 0),
                                      lin({}, 256, L.self_attn.v, {}, sv_.get(), 0)};
+            if (mask_input) {
+                // SAM's mask input: the branch's two strided convolutions on the logits, its last (1x1) one inside the keys'
+                // initialisation, where the dense embedding takes the place of no_mask_embed
+                const k::MaskBranch branch = W.mask_branch();
+                k::mask_embed(mask_input, branch, mask_h_.get(), P, s);
+                float const* h[k::kDecoderMaxPrompts];
+                for (int i = 0; i < P; ++i) h[i] = mask_h_.get() + (size_t)i * kTokens * k::kMaskHidden;
+                k::decoder_start_masked(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
+                                        W.mask_tokens_.get(), tokens_.get(), qkv, 3, h, branch, keys_.get(), keys_h_.get(), P, TOK, s);
+            } else
             k::decoder_start(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
                              W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, TOK, s);
         }

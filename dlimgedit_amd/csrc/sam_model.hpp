@@ -86,6 +86,17 @@ struct SamWeights {
     LinearH neck1_, neck2_;               // 1x1 conv [256, D]; 3x3 conv as [256, 9*256] (tap-major columns)
     NormW neck_ln1_, neck_ln2_;
     DeviceBuffer<float> pe_gauss_, pe_point_, pe_not_a_point_, pe_no_mask_;
+    // the prompt encoder's mask branch (pe.mask.*), optional in the file: without it no prompt can take a mask input
+    bool has_mask_branch_ = false;
+    DeviceBuffer<float> mask_w1_, mask_b1_, mask_w2_, mask_b2_, mask_proj_w_, mask_proj_b_;
+    NormW mask_ln1_, mask_ln2_;
+    k::MaskBranch mask_branch() const {
+        k::MaskBranch b;
+        b.w1 = mask_w1_.get(); b.b1 = mask_b1_.get(); b.ln1_w = mask_ln1_.w.get(); b.ln1_b = mask_ln1_.b.get();
+        b.w2 = mask_w2_.get(); b.b2 = mask_b2_.get(); b.ln2_w = mask_ln2_.w.get(); b.ln2_b = mask_ln2_.b.get();
+        b.proj_w = mask_proj_w_.get(); b.proj_b = mask_proj_b_.get();
+        return b;
+    }
     DeviceBuffer<float> iou_token_, mask_tokens_;
     std::array<DecoderLayer, 2> dec_;
     LinearF final_q_, final_o_;
@@ -152,7 +163,12 @@ class SamModel {
     // Decoder for `count` prompts of `points` points each (2 .. 10: every prompt of a call has the same number, 5 + points
     // token rows). emb[i]: device embedding of prompt i's image; coords [count][points][2], labels [count][points] host
     // arrays. Results stay on device: logits() [count][4][256][256], iou() [count][4].
-    void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2);
+    // mask_input (optional, [count]): every prompt's mask input, SAM's click-to-refine loop -- device logits some decode left
+    // (this lane's own logits() / iou() are fine: they are read before this decode writes them, in stream order).  All
+    // prompts of a call have one or none; needs a model with the mask branch (has_mask_branch()).
+    void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2,
+                k::MaskSource const* mask_input = nullptr);
+    bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
     float const* logits() const { return logits_.get(); }
     // Diagnostic: the token-side workspaces as the last decode of ONE prompt left them (after synchronize()), one after
     // the other; names/sizes in decoder_state_layout().  What a parity or race hunt compares stage by stage.
@@ -215,7 +231,8 @@ class SamModel {
   private:
     void reserve_encoder(int batch);
     void reserve_decoder(int count);
-    void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points);
+    void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points,
+                      k::MaskSource const* mask_input);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
 
     int device_ = 0;
@@ -287,6 +304,7 @@ class SamModel {
     // ---- decoder workspace (sized for dec_count_ prompts)
     int dec_count_ = 0;
     DeviceBuffer<float> keys_, logits_, iou_, hyper_;
+    DeviceBuffer<float> mask_h_;         // [launch's prompts][4096][16]: the mask branch in front of its last convolution (first masked decode)
     DeviceBuffer<half_t> keys_h_, kqv_h_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
 

@@ -231,6 +231,30 @@ SamWeights::SamWeights(std::string const& weight_path, int device_index) : devic
     ld.f32("pe.point", {4, 256}, pe_point_);
     ld.f32("pe.not_a_point", {256}, pe_not_a_point_);
     ld.f32("pe.no_mask", {256}, pe_no_mask_);
+    {   // the mask branch (mask input of click-to-refine) is optional, all or nothing: a file without it serves everything but marks
+        static const char* const names[] = {"pe.mask.down1.w", "pe.mask.down1.b", "pe.mask.ln1.w", "pe.mask.ln1.b", "pe.mask.down2.w",
+                                            "pe.mask.down2.b", "pe.mask.ln2.w",   "pe.mask.ln2.b", "pe.mask.proj.w", "pe.mask.proj.b"};
+        int present = 0;
+        const char* absent = nullptr;
+        for (const char* n : names) {
+            if (file.has(n)) ++present;
+            else absent = n;
+        }
+        if (present != 0 && absent)
+            throw Exception("'" + file.path() + "': the mask branch pe.mask.* is all or nothing: " + std::to_string(present) +
+                            " of its 10 tensors are there, '" + absent + "' is not");
+        has_mask_branch_ = present != 0;
+        if (has_mask_branch_) {
+            ld.f32("pe.mask.down1.w", {4, 1, 2, 2}, mask_w1_);
+            ld.f32("pe.mask.down1.b", {4}, mask_b1_);
+            ld.norm("pe.mask.ln1", 4, mask_ln1_);
+            ld.f32("pe.mask.down2.w", {16, 4, 2, 2}, mask_w2_);
+            ld.f32("pe.mask.down2.b", {16}, mask_b2_);
+            ld.norm("pe.mask.ln2", 16, mask_ln2_);
+            ld.f32("pe.mask.proj.w", {256, 16}, mask_proj_w_);
+            ld.f32("pe.mask.proj.b", {256}, mask_proj_b_);
+        }
+    }
     {   // dense positional encoding of the 64x64 grid (PositionEmbeddingRandom.forward), constant
         HostTensor const& g = file.get("pe.gauss", {2, 128});
         std::vector<float> pe((size_t)kTokens * 256);

@@ -80,17 +80,58 @@ void pack_batch_prompt(ResizeLongestSide const& rs, PromptSpec const& spec, int 
     }
 }
 
-// The prompts of a batch call, packed: prompt j's points start at point at[j] of coords / labels.
+// Stage `n_clicks` of a prompt that holds refinement marks (prompt_plan.hpp): its first n_clicks clicks -- which do not lie in
+// consecutive entries -- then the box or the padding point, packed exactly as an unmarked prompt of those clicks is.
+void pack_stage(ResizeLongestSide const& rs, PromptSpec const& spec, PromptStages const& stages, int n_clicks, int const* points,
+                int const* regions, float* coords, float* labels) {
+    PromptSpec part = spec;
+    part.clicks = n_clicks;
+    if (n_clicks <= 1) {
+        pack_batch_prompt(rs, part, points, regions, coords, labels);
+        return;
+    }
+    const int i = spec.head;
+    auto set = [&](int index, Point q, int label) {
+        Point t = rs.transform(q);
+        coords[index * 2 + 0] = float(t.x);
+        coords[index * 2 + 1] = float(t.y);
+        labels[index] = float(label);
+    };
+    for (int c = 0; c < n_clicks; ++c) {
+        const int e = stages.click_entry[c];
+        set(c, Point{points[e * 2], points[e * 2 + 1]}, staged_click_label(stages, c, regions));
+    }
+    if (spec.box) {
+        set(n_clicks, Point{regions[i * 4], regions[i * 4 + 1]}, 2);
+        set(n_clicks + 1, Point{regions[i * 4 + 2], regions[i * 4 + 3]}, 3);
+    } else {
+        set(n_clicks, Point{0, 0}, -1);
+    }
+}
+
+// The prompts of a batch call, packed: prompt j's points start at point at[j] of coords / labels.  A staged prompt (stages[j]
+// has more than one stage) is packed as its last stage, all of its clicks.
 struct BatchPrompts {
     std::vector<PromptSpec> prompts;
+    std::vector<PromptStages> stages;
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
 BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions) {
     std::vector<char> has_handle(count);
-    for (int i = 0; i < count; ++i) has_handle[i] = segs[i] != nullptr;
+    SegmentationImpl const* any = nullptr;
+    for (int i = 0; i < count; ++i) {
+        has_handle[i] = segs[i] != nullptr;
+        if (!any) any = segs[i];
+    }
     BatchPrompts b;
-    b.prompts = plan_prompts(has_handle, points != nullptr, regions);
+    {
+        // a mark needs the mask branch of the model; the environment's replicas share one model file
+        const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
+        StagedPrompts plan = plan_staged_prompts(has_handle, points != nullptr, regions, mask_branch);
+        b.prompts = std::move(plan.prompts);
+        b.stages = std::move(plan.stages);
+    }
     size_t total = 0;
     for (PromptSpec const& p : b.prompts) {
         b.at.push_back(total);
@@ -98,9 +139,45 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     }
     b.coords.resize(total * 2);
     b.labels.resize(total);
-    for (size_t j = 0; j < b.prompts.size(); ++j)
-        pack_batch_prompt(segs[b.prompts[j].head]->geometry(), b.prompts[j], points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
+    for (size_t j = 0; j < b.prompts.size(); ++j) {
+        ResizeLongestSide const& rs = segs[b.prompts[j].head]->geometry();
+        if (b.stages[j].staged())
+            pack_stage(rs, b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
+        else
+            pack_batch_prompt(rs, b.prompts[j], points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
+    }
     return b;
+}
+// What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
+// of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).
+struct BatchWork { PromptChunk part; bool staged; };
+std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
+    std::vector<int> plain;
+    for (int j : mine)
+        if (!b.stages[j].staged()) plain.push_back(j);
+    std::vector<BatchWork> work;
+    for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
+    for (int j : mine)
+        if (b.stages[j].staged()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+    return work;
+}
+// The stages of staged prompt j in front of its last one, decoded on `model` (mutex held) one after the other; returns the
+// mask input of the last stage: the plane the stage before it would deliver, where that decode left it.
+k::MaskSource run_early_stages(SamModel& model, BatchPrompts const& b, int j, float const* emb, ResizeLongestSide const& rs,
+                               int const* points, int const* regions) {
+    PromptSpec const& spec = b.prompts[j];
+    PromptStages const& st = b.stages[j];
+    float coords[2 * k::kDecoderMaxPoints], labels[k::kDecoderMaxPoints];
+    k::MaskSource src{nullptr, nullptr};
+    for (size_t s = 0; s + 1 < st.stage_clicks.size(); ++s) {
+        PromptSpec part = spec;
+        part.clicks = st.stage_clicks[s];
+        pack_stage(rs, spec, st, part.clicks, points, regions, coords, labels);
+        model.decode(&emb, coords, labels, 1, part.points(), s ? &src : nullptr);
+        // single_mask_job's rule: the best of planes 1..3 for a two-point stage, plane 0 otherwise
+        src = k::MaskSource{model.logits(), part.points() > 2 ? nullptr : model.iou()};
+    }
+    return src;
 }
 // the prompts of one chunk, tightly packed for SamModel::decode
 void gather_chunk(BatchPrompts const& b, PromptChunk const& chunk, std::vector<float>& cc, std::vector<float>& ll) {
@@ -514,7 +591,9 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
 
 // Prompts are grouped by the replica that holds their image's embedding; on each GPU they are grouped by their number of
 // points (a decoder launch holds one count) and cut into chunks of at most kPromptChunk prompts (prompt_plan.hpp), each chunk
-// decoded as one batch on the next lane, its masks copied out while the next chunk runs.
+// decoded as one batch on the next lane, its masks copied out while the next chunk runs.  A prompt with refinement marks is a
+// chunk of its own behind them: its stages run in order on one lane's stream, each taking the logits of the one before it as
+// its mask input, and only the last one is post-processed.
 void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                           int const* regions, uint8_t* const* out_masks) {
     if (count <= 0) return;
@@ -552,7 +631,8 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
         };
         try {
             std::vector<float> cc, ll;
-            for (PromptChunk const& part : plan_prompt_chunks(prompts, mine, kPromptChunk)) {
+            for (BatchWork const& work : plan_batch_work(batch, mine, kPromptChunk)) {
+                PromptChunk const& part = work.part;
                 const int n = (int)part.prompts.size(), npts = part.points;
                 std::vector<float const*> emb(n);
                 for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
@@ -565,7 +645,12 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
                 Chunk& cur = chunks.back();
                 roctx::Range range("dlimg.compute_masks");
                 std::lock_guard<std::mutex> lock(model.mutex());
-                model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                if (work.staged) {
+                    const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
+                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src);
+                } else {
+                    model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                }
                 for (int j = 0; j < n; ++j) {
                     const int i = prompts[part.prompts[j]].head;
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
@@ -644,7 +729,8 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
         };
         try {
             std::vector<float> cc, ll;
-            for (PromptChunk const& part : plan_prompt_chunks(prompts, mine, kPromptChunk)) {
+            for (BatchWork const& work : plan_batch_work(batch, mine, kPromptChunk)) {
+                PromptChunk const& part = work.part;
                 const int n = (int)part.prompts.size(), npts = part.points;
                 std::vector<float const*> emb(n);
                 std::vector<k::PostJob> jobs(n);
@@ -654,7 +740,12 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
                 chunks.push_back(Chunk{&model, &model.acquire_mask_slot()});
                 roctx::Range range("dlimg.compute_masks_device");
                 std::lock_guard<std::mutex> lock(model.mutex());
-                model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                if (work.staged) {
+                    const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
+                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src);
+                } else {
+                    model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                }
                 for (int j = 0; j < n; ++j) {
                     const int i = prompts[part.prompts[j]].head;
                     const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;

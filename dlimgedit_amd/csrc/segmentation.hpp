@@ -58,7 +58,8 @@ class SegmentationImpl {
     // points XOR regions: entry i is a point or a box query.  Both: entry i is the box regions[i] refined by the foreground
     // point points[i], one three-point prompt (pack_prompt).  An entry whose segs[i] is null adds one more click to the prompt
     // in front of it (prompt_plan.hpp: up to 8 clicks, foreground or background, with or without the box); its out_masks
-    // entry is not read.  Prompts of different sizes may share a call.
+    // entry is not read.  Prompts of different sizes may share a call.  A continuation entry {4, 0, 0, 0} is a refinement mark:
+    // the prompt is decoded in stages, each taking the logits of the one before it as mask input (prompt_plan.hpp).
     static void compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                    int const* regions, uint8_t* const* out_masks);
 

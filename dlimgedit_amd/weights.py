@@ -50,7 +50,36 @@ def _ln_specs(prefix: str, dim: int) -> List[Spec]:
     return [(f"{prefix}.w", (dim,), ("ln_w",)), (f"{prefix}.b", (dim,), ("u", 0.1))]
 
 
-def param_specs(cfg: SamConfig) -> List[Spec]:
+def mask_branch_specs() -> List[Spec]:
+    """The prompt encoder's mask branch (SAM's mask_downscaling: the mask input of click-to-refine): conv 2x2 / 2 (1 -> 4),
+    LayerNorm2d, GELU, conv 2x2 / 2 (4 -> 16), LayerNorm2d, GELU, conv 1x1 (16 -> 256).  The names avoid "conv": the branch
+    stays fp32 (f16_operand).  The set is optional in a model file, all or nothing: a model without it serves everything but
+    refinement marks."""
+    c1, c2 = MASK_IN_CHANS // 4, MASK_IN_CHANS
+    s: List[Spec] = [("pe.mask.down1.w", (c1, 1, 2, 2), ("lin", 4)), ("pe.mask.down1.b", (c1,), ("u", 0.05))]
+    s += _ln_specs("pe.mask.ln1", c1)
+    s += [("pe.mask.down2.w", (c2, c1, 2, 2), ("lin", c1 * 4)), ("pe.mask.down2.b", (c2,), ("u", 0.05))]
+    s += _ln_specs("pe.mask.ln2", c2)
+    s += [("pe.mask.proj.w", (DEC_DIM, c2), ("lin", c2)), ("pe.mask.proj.b", (DEC_DIM,), ("u", 0.05))]
+    return s
+
+
+MASK_IN_CHANS = 16
+MASK_BRANCH = tuple(n for n, _, _ in mask_branch_specs())
+
+
+def has_mask_branch(params) -> bool:
+    """True when `params` holds the whole mask branch, False when it holds none of it; a partial set is refused."""
+    present = [n for n in MASK_BRANCH if n in params]
+    if present and len(present) != len(MASK_BRANCH):
+        missing = [n for n in MASK_BRANCH if n not in params]
+        raise ValueError(f"partial mask branch: pe.mask.* is all or nothing, {len(present)} of {len(MASK_BRANCH)} tensors given, "
+                         f"e.g. {missing[0]} is missing")
+    return bool(present)
+
+
+def param_specs(cfg: SamConfig, mask_branch: bool = False) -> List[Spec]:
+    """The tensors of one model.  mask_branch: with the optional mask branch (mask_branch_specs), listed behind pe.no_mask."""
     d, hd, g, w = cfg.embed_dim, cfg.head_dim, cfg.grid, cfg.window_size
     k_patch = 3 * cfg.patch_size ** 2
     s: List[Spec] = [
@@ -74,12 +103,14 @@ def param_specs(cfg: SamConfig) -> List[Spec]:
     s += [("enc.neck.conv2.w", (oc, oc, 3, 3), ("lin", oc * 9))]
     s += _ln_specs("enc.neck.ln2", oc)
 
-    # prompt encoder (mask-input branch is never taken: has_mask_input == 0,
-    # /root/reference/src/segmentation.cpp:43-45)
+    # prompt encoder (the reference never takes the mask-input branch: has_mask_input == 0,
+    # /root/reference/src/segmentation.cpp:43-45; here refinement marks do, when the model has it)
     s += [("pe.gauss", (2, DEC_DIM // 2), ("u", 1.7)),
           ("pe.point", (4, DEC_DIM), ("u", 0.5)),
           ("pe.not_a_point", (DEC_DIM,), ("u", 0.5)),
           ("pe.no_mask", (DEC_DIM,), ("u", 0.5))]
+    if mask_branch:
+        s += mask_branch_specs()
 
     # mask decoder
     s += [("dec.iou_token", (DEC_DIM,), ("u", 0.5)),
@@ -137,9 +168,10 @@ def counter_uniform(seed: int, name: str, n: int) -> np.ndarray:
     return (u24 * (2.0 / 16777216.0) - 1.0).astype(np.float32)
 
 
-def synthetic_weights(cfg: SamConfig, seed: int = 0) -> Dict[str, np.ndarray]:
+def synthetic_weights(cfg: SamConfig, seed: int = 0, mask_branch: bool = False) -> Dict[str, np.ndarray]:
+    """Seeded weights; every tensor is a function of (seed, its name) alone, so the mask branch changes no other tensor."""
     out: Dict[str, np.ndarray] = {}
-    for name, shape, init in param_specs(cfg):
+    for name, shape, init in param_specs(cfg, mask_branch):
         n = int(np.prod(shape))
         u = counter_uniform(seed, name, n)
         if init[0] == "lin":
@@ -227,10 +259,10 @@ def check_f16_range(params: Dict[str, np.ndarray], allow_out_of_range: bool = Fa
 
 
 def save_weights(path, cfg: SamConfig, params: Dict[str, np.ndarray], allow_out_of_range: bool = False) -> Path:
-    """Write `params` (must cover param_specs(cfg) exactly) to `path` in DLW v1."""
+    """Write `params` (must cover param_specs(cfg) exactly; the mask branch as a whole or not at all) to `path` in DLW v1."""
     path = Path(path)
-    check_f16_range({s[0]: params[s[0]] for s in param_specs(cfg) if s[0] in params}, allow_out_of_range)
-    specs = param_specs(cfg)
+    specs = param_specs(cfg, has_mask_branch(params))
+    check_f16_range({s[0]: params[s[0]] for s in specs if s[0] in params}, allow_out_of_range)
     names = [s[0] for s in specs]
     missing = [n for n in names if n not in params]
     if missing:
@@ -287,9 +319,9 @@ def load_weights(path) -> Tuple[Dict[str, int], Dict[str, np.ndarray]]:
     return meta, out
 
 
-def write_synthetic_model_dir(model_dir, cfg: SamConfig, seed: int = 0) -> Dict[str, np.ndarray]:
+def write_synthetic_model_dir(model_dir, cfg: SamConfig, seed: int = 0, mask_branch: bool = False) -> Dict[str, np.ndarray]:
     """Create `<model_dir>/segmentation/sam_<variant>.dlw` with seeded weights; returns them."""
-    params = synthetic_weights(cfg, seed)
+    params = synthetic_weights(cfg, seed, mask_branch)
     save_weights(Path(model_dir) / "segmentation" / weight_file_name(cfg), cfg, params)
     return params
 
@@ -351,10 +383,39 @@ def hf_name_map(cfg: SamConfig) -> List[Tuple[str, str]]:
     return m
 
 
+_HF_MASK = ("conv1", "layer_norm1", "conv2", "layer_norm2", "conv3")
+_META_MASK = ("0", "1", "3", "4", "6")
+_OUR_MASK = ("down1", "ln1", "down2", "ln2", "proj")
+
+
+def _mask_name_map(prefix: str, theirs) -> List[Tuple[str, str]]:
+    """(our name, their key) of the mask branch; the 1x1 convolution's weight is [256, 16] here and [256, 16, 1, 1] there."""
+    return [(f"pe.mask.{o}.{a}", f"{prefix}.{t}.{b}") for o, t in zip(_OUR_MASK, theirs) for a, b in (("w", "weight"), ("b", "bias"))]
+
+
+def _mask_to(params, names) -> Dict[str, np.ndarray]:
+    if not has_mask_branch(params):
+        return {}
+    sd = {theirs: params[ours] for ours, theirs in names}
+    key = dict(names)["pe.mask.proj.w"]
+    sd[key] = sd[key].reshape(DEC_DIM, MASK_IN_CHANS, 1, 1)
+    return sd
+
+
+def _mask_from(sd, names, a) -> Dict[str, np.ndarray]:
+    """The branch when the state dict holds all of it; a part of it alone (a stripped checkpoint) is ignored."""
+    if not all(theirs in sd for _, theirs in names):
+        return {}
+    p = {ours: a(sd[theirs]) for ours, theirs in names}
+    p["pe.mask.proj.w"] = p["pe.mask.proj.w"].reshape(DEC_DIM, MASK_IN_CHANS)
+    return p
+
+
 def to_hf_state_dict(cfg: SamConfig, params: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Our tensors laid out under HF `SamModel` keys (for cross-checking the oracle)."""
+    """Our tensors laid out under HF `SamModel` keys (for cross-checking the oracle); the mask branch when `params` has it."""
     d, g = cfg.embed_dim, cfg.grid
     sd = {hf: params[ours] for ours, hf in hf_name_map(cfg)}
+    sd.update(_mask_to(params, _mask_name_map("prompt_encoder.mask_embed", _HF_MASK)))
     sd["vision_encoder.patch_embed.projection.weight"] = params["enc.patch.w"].reshape(d, 3, cfg.patch_size, cfg.patch_size)
     sd["vision_encoder.pos_embed"] = params["enc.pos"].reshape(1, g, g, d)
     sd["vision_encoder.neck.conv1.weight"] = params["enc.neck.conv1.w"].reshape(cfg.out_chans, d, 1, 1)
@@ -382,7 +443,8 @@ def from_hf_state_dict(cfg: SamConfig, sd) -> Dict[str, np.ndarray]:
     p["pe.point"] = np.concatenate([a(sd[f"prompt_encoder.point_embed.{i}.weight"]) for i in range(4)], 0)
     for k in ("pe.not_a_point", "pe.no_mask", "dec.iou_token"):
         p[k] = p[k].reshape(-1)
-    want = {n: s for n, s, _ in param_specs(cfg)}
+    p.update(_mask_from(sd, _mask_name_map("prompt_encoder.mask_embed", _HF_MASK), a))
+    want = {n: s for n, s, _ in param_specs(cfg, has_mask_branch(p))}
     for n, s in want.items():
         if tuple(p[n].shape) != tuple(s):
             raise ValueError(f"{n}: checkpoint shape {p[n].shape} != {s}")
@@ -447,6 +509,7 @@ def meta_name_map(cfg: SamConfig) -> List[Tuple[str, str]]:
 def to_meta_state_dict(cfg: SamConfig, params: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
     d, g = cfg.embed_dim, cfg.grid
     sd = {theirs: params[ours] for ours, theirs in meta_name_map(cfg)}
+    sd.update(_mask_to(params, _mask_name_map("prompt_encoder.mask_downscaling", _META_MASK)))
     sd["image_encoder.patch_embed.proj.weight"] = params["enc.patch.w"].reshape(d, 3, cfg.patch_size, cfg.patch_size)
     sd["image_encoder.pos_embed"] = params["enc.pos"].reshape(1, g, g, d)
     sd["image_encoder.neck.0.weight"] = params["enc.neck.conv1.w"].reshape(cfg.out_chans, d, 1, 1)
@@ -459,8 +522,8 @@ def to_meta_state_dict(cfg: SamConfig, params: Dict[str, np.ndarray]) -> Dict[st
 
 
 def from_meta_state_dict(cfg: SamConfig, sd) -> Dict[str, np.ndarray]:
-    """Meta checkpoint (`torch.load('sam_vit_b_01ec64.pth')`) -> our tensors.  Unused tensors of the
-    checkpoint (mask_downscaling.*: the mask-input branch, never taken here) are ignored."""
+    """Meta checkpoint (`torch.load('sam_vit_b_01ec64.pth')`) -> our tensors, with the mask branch (mask_downscaling.*) when
+    the checkpoint holds all of it; a part of it alone is ignored."""
     def a(x):
         return np.ascontiguousarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x, dtype=np.float32)
     d = cfg.embed_dim
@@ -475,7 +538,8 @@ def from_meta_state_dict(cfg: SamConfig, sd) -> Dict[str, np.ndarray]:
     p["pe.not_a_point"] = a(sd["prompt_encoder.not_a_point_embed.weight"]).reshape(-1)
     p["pe.no_mask"] = a(sd["prompt_encoder.no_mask_embed.weight"]).reshape(-1)
     p["dec.iou_token"] = a(sd["mask_decoder.iou_token.weight"]).reshape(-1)
-    for n, s, _ in param_specs(cfg):
+    p.update(_mask_from(sd, _mask_name_map("prompt_encoder.mask_downscaling", _META_MASK), a))
+    for n, s, _ in param_specs(cfg, has_mask_branch(p)):
         if tuple(p[n].shape) != tuple(s):
             raise ValueError(f"{n}: checkpoint shape {p[n].shape} != {s} (wrong variant?)")
     return p

@@ -124,10 +124,22 @@ typedef struct dlimg_Api {
      * as above and its own click is a foreground click; in a call with continuation entries a head whose region
      * is empty (x1 < x0) has no box.  A prompt has at most 8 clicks and gets ONE mask, out_masks of its head (the
      * continuation entries' out_masks are not read and may be NULL).  Prompts of different sizes may share a call.
-     * Refused: more than 8 clicks, a continuation entry in front, a label other than 0 / 1. */
+     * Refused: more than 8 clicks, a continuation entry in front, a label other than 0 / 1.
+     * Refinement marks (SAM's mask input): a continuation entry whose four ints are {DLIMG_REFINE_MARK, 0, 0, 0} is a
+     * mark, not a click -- points[i] is not read and it does not count towards the 8 clicks.  A prompt with m marks
+     * is decoded in m + 1 stages on the GPU that holds the embedding: stage j takes the clicks in front of mark j
+     * (the head's included), the last stage all clicks, every stage the prompt's box if it has one; from the second
+     * stage on a stage takes the low-res logits of the stage before it as its mask input, the way SAM's interactive
+     * predictor feeds them back.  The mask of the last stage is delivered.  Refused (the message names the mark): a
+     * mark directly after a mark, a mark as the last entry of a prompt, a mark with non-zero trailing ints, a mark
+     * for a model whose file has no mask branch (pe.mask.*).  A call without marks is read as it always was. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
+
+/* regions[4 i] of a refinement mark in get_segmentation_masks (slot 14): the first value SAM's label space leaves
+ * free (-1 padding point, 0 / 1 clicks, 2 / 3 box corners). */
+#define DLIMG_REFINE_MARK 4
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

@@ -14,6 +14,7 @@
 
 #include "dlimgedit.h"
 
+#include <algorithm>
 #include <array>
 #include <cstddef>
 #include <exception>
@@ -287,17 +288,33 @@ class Segmentation {
 
     // Click-to-refine (addition of this build): one mask from 1 .. 8 clicks -- the first one a foreground click -- and an
     // optional box, as one prompt: the clicks in the order given, then the box.
-    Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt) const {
-        return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region})[0]);
+    // refine_after: click counts k, strictly increasing, 1 <= k < clicks.size() -- "a refinement mark after the first k
+    // clicks": the clicks are replayed in stages the way SAM's interactive predictor takes them, each stage with the low-res
+    // logits of the one before it as its mask input (on the GPU); the mask of the last stage is returned.  refine_each(n):
+    // a mark after every click but the last.  Needs a model with the mask branch.
+    Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
+                       std::vector<int> const& refine_after = {}) const {
+        return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after})[0]);
+    }
+    static std::vector<int> refine_each(size_t clicks) {
+        std::vector<int> after;
+        for (size_t k = 1; k < clicks; ++k) after.push_back(int(k));
+        return after;
     }
 
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
-    // optional box per prompt.
+    // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none).
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
-                                                 std::vector<std::optional<Region>> const& regions = {}) {
-        if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()))
-            throw Exception("compute_mask_batch: one list of clicks and at most one region per segmentation");
+                                                 std::vector<std::optional<Region>> const& regions = {},
+                                                 std::vector<std::vector<int>> const& refine_after = {}) {
+        if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
+            (!refine_after.empty() && refine_after.size() != segs.size()))
+            throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
+        for (size_t j = 0; j < refine_after.size(); ++j)
+            for (size_t m = 0; m < refine_after[j].size(); ++m)
+                if (refine_after[j][m] < 1 || refine_after[j][m] >= int(clicks[j].size()) || (m && refine_after[j][m] <= refine_after[j][m - 1]))
+                    throw Exception("compute_mask_batch: refine_after holds click counts k, strictly increasing, 1 <= k < the prompt's clicks");
         std::vector<Image> out;
         bool refined = false;
         for (size_t j = 0; j < segs.size(); ++j) {
@@ -319,6 +336,12 @@ class Segmentation {
                 const bool box = !regions.empty() && regions[j].has_value();
                 if (!refined && box != (pass == 1)) continue;
                 for (size_t c = 0; c < clicks[j].size(); ++c) {
+                    if (!refine_after.empty() && std::find(refine_after[j].begin(), refine_after[j].end(), int(c)) != refine_after[j].end()) {
+                        hs.push_back(nullptr);           // a mark after the first c clicks: its point is not read
+                        pts.push_back(Point{0, 0});
+                        ptrs.push_back(nullptr);
+                        regs.push_back(Region(Point{DLIMG_REFINE_MARK, 0}, Point{0, 0}));
+                    }
                     hs.push_back(c == 0 ? segs[j]->handle_.get() : nullptr);
                     pts.push_back(clicks[j][c].point);
                     ptrs.push_back(c == 0 ? out[j].pixels() : nullptr);
