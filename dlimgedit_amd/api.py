@@ -651,6 +651,7 @@ class ext:
                 "dlimg_amd_test_attention": ([ci, vp, vp, vp, vp, ci, ci, ci, vp], ci),
                 "dlimg_amd_test_resize": ([vp, ci, ci, ci, ci, ci, ci, vp], ci),
                 "dlimg_amd_test_decode": ([vp, ci, vp, ci, vp, vp, vp, vp, vp], ci),
+                "dlimg_amd_test_decode_prompts": ([vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.c_char_p, ci], ci),
                 "dlimg_amd_bench_attention": ([ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_prepost": ([ci, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_gemm": ([ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
@@ -676,7 +677,8 @@ class ext:
                "dlimg_amd_test_postprocess", "dlimg_amd_test_postprocess_batch", "dlimg_amd_test_force_gemm_tile",
                "dlimg_amd_test_force_gemm_consumer_tile", "dlimg_amd_test_gemm", "dlimg_amd_test_gemm_ln",
                "dlimg_amd_test_lane_worker", "dlimg_amd_test_gemm_stream", "dlimg_amd_test_layernorm",
-               "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_bench_attention",
+               "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_test_decode_prompts",
+               "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps")
 
@@ -1036,6 +1038,39 @@ class ext:
         _check_hook(cls._h().dlimg_amd_test_decode(env.handle(), emb.shape[0], emb.ctypes.data, count, idx.ctypes.data,
                                                    c.ctypes.data, l.ctypes.data, logits.ctypes.data, iou.ctypes.data))
         return logits, iou
+
+    @classmethod
+    def test_decode_prompts(cls, env: Environment, embeddings: np.ndarray, emb_index, coords, labels, mask_planes=None,
+                            mask_iou=None, want_state: bool = False):
+        """The whole of SamModel::decode (one call for all prompts) on given embeddings [n][4096][256]: prompt i decodes
+        embeddings[emb_index[i]] with coords[i] ([points][2], resized-image pixels) and labels[i] ([points]), 2 .. 10 points,
+        the same number for every prompt.  mask_planes [count][4][256][256]: every prompt's mask input; mask_iou [count][4]:
+        the predictions its plane is chosen by on the device (None: plane 0).  Returns (logits [count][4][256][256], iou
+        [count][4]) and, with want_state (one prompt), {name: array} of the token-side workspaces, "mask_h" after a masked
+        call."""
+        emb = np.ascontiguousarray(embeddings, dtype=np.float32).reshape(-1, 4096, 256)
+        idx = np.ascontiguousarray(emb_index, dtype=np.int32).reshape(-1)
+        count = idx.size
+        l = np.ascontiguousarray(labels, dtype=np.float32).reshape(count, -1)
+        points = l.shape[1]
+        c = np.ascontiguousarray(coords, dtype=np.float32).reshape(count, points, 2)
+        planes = None if mask_planes is None else np.ascontiguousarray(mask_planes, dtype=np.float32).reshape(count, 4, 256, 256)
+        iou4 = None if mask_iou is None else np.ascontiguousarray(mask_iou, dtype=np.float32).reshape(count, 4)
+        logits = np.empty((count, 4, 256, 256), dtype=np.float32)
+        iou = np.empty((count, 4), dtype=np.float32)
+        state = np.empty(1 << 18, dtype=np.float32) if want_state else None      # 15 rows and mask_h need 131 k floats
+        layout = C.create_string_buffer(1024)
+        _check_hook(cls._h().dlimg_amd_test_decode_prompts(
+            env.handle(), emb.shape[0], emb.ctypes.data, count, idx.ctypes.data, points, c.ctypes.data, l.ctypes.data,
+            cls._ptr(planes), cls._ptr(iou4), logits.ctypes.data, iou.ctypes.data, cls._ptr(state),
+            0 if state is None else state.size, layout, 1024))
+        if not want_state:
+            return logits, iou
+        res, off = {}, 0
+        for n, cnt in ((n, int(cnt)) for n, cnt in (item.split(":") for item in layout.value.decode().strip(",").split(","))):
+            res[n] = state[off:off + cnt].copy()
+            off += cnt
+        return logits, iou, res
 
     @classmethod
     def test_resize(cls, pixels: np.ndarray, channels: Channels, out_w: int, out_h: int) -> np.ndarray:

@@ -691,18 +691,27 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
     HIP_CHECK(hipGetLastError());
 }
 
-std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() {
-    const size_t T = kDecTokens;
-    return {{"tokens", T * 256}, {"final_q", T * 128}, {"self_k", T * 256}, {"self_v", T * 256}, {"self_out", T * 256},
-            {"t2i_out", T * 256}, {"mlp_hidden", T * 2048}, {"queries", T * 256}, {"i2t_k", T * 128}, {"i2t_v", T * 128},
-            {"final_partials", k::token_to_image_scratch_floats(1, kDecTokens)}, {"hyper", 4 * 32}, {"iou", 4}, {"keys_head", 4096}};
+std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }
+
+std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout(int tokens, bool with_mask_h) {
+    DLIMG_ASSERT(k::decoder_tokens_supported(tokens));
+    const size_t T = (size_t)tokens;
+    std::vector<std::pair<const char*, size_t>> parts = {
+        {"tokens", T * 256}, {"final_q", T * 128}, {"self_k", T * 256}, {"self_v", T * 256}, {"self_out", T * 256},
+        {"t2i_out", T * 256}, {"mlp_hidden", T * 2048}, {"queries", T * 256}, {"i2t_k", T * 128}, {"i2t_v", T * 128},
+        {"final_partials", k::token_to_image_scratch_floats(1, tokens)}, {"hyper", 4 * 32}, {"iou", 4}, {"keys_head", 4096}};
+    if (with_mask_h) parts.push_back({"mask_h", (size_t)kTokens * k::kMaskHidden});
+    return parts;
 }
 
-void SamModel::decoder_state(float* out) const {
+void SamModel::decoder_state(float* out) const { decoder_state(out, kDecTokens); }
+
+void SamModel::decoder_state(float* out, int tokens, bool with_mask_h) const {
     float const* src[] = {tokens_.get(), sq_.get(), sk_.get(), sv_.get(), tsa_.get(), tt2i_.get(), tmlp_.get(), queries_.get(),
-                          tk_.get(), tv_.get(), t2i_part_.get(), hyper_.get(), iou_.get(), keys_.get()};
+                          tk_.get(), tv_.get(), t2i_part_.get(), hyper_.get(), iou_.get(), keys_.get(), mask_h_.get()};
+    if (with_mask_h) DLIMG_ASSERT(mask_h_.capacity() >= (size_t)kTokens * k::kMaskHidden);
     size_t off = 0, i = 0;
-    for (auto const& part : decoder_state_layout()) {
+    for (auto const& part : decoder_state_layout(tokens, with_mask_h)) {
         HIP_CHECK(hipMemcpy(out + off, src[i++], part.second * sizeof(float), hipMemcpyDeviceToHost));
         off += part.second;
     }

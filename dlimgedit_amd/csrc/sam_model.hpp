@@ -174,6 +174,10 @@ class SamModel {
     // the other; names/sizes in decoder_state_layout().  What a parity or race hunt compares stage by stage.
     static std::vector<std::pair<const char*, size_t>> decoder_state_layout();
     void decoder_state(float* out) const;
+    // The same for a prompt of `tokens` token rows (7 .. 15: 5 + its points); with_mask_h adds "mask_h" [4096][16], the mask
+    // branch in front of its last convolution as the last MASKED decode of one prompt left it.
+    static std::vector<std::pair<const char*, size_t>> decoder_state_layout(int tokens, bool with_mask_h = false);
+    void decoder_state(float* out, int tokens, bool with_mask_h = false) const;
     float const* iou() const { return iou_.get(); }
 
     // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):

@@ -14,7 +14,9 @@
 #include <chrono>
 #include <thread>
 #include <cstdlib>
+#include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 namespace dlimg {
@@ -406,6 +408,57 @@ DLIMG_API int dlimg_amd_test_decode(dlimg_Environment env, int n_emb, float cons
         m.synchronize();
         download(out_logits, m.logits(), (size_t)count * 4 * kLowRes * kLowRes);
         download(out_iou, m.iou(), (size_t)count * 4);
+    });
+}
+
+DLIMG_API int dlimg_amd_test_decode_prompts(dlimg_Environment env, int n_emb, float const* emb, int count, int const* emb_index,
+                                            int points, float const* coords, float const* labels, float const* mask_planes,
+                                            float const* mask_iou, float* out_logits, float* out_iou, float* out_state,
+                                            int state_capacity, char* out_layout, int layout_capacity) {
+    return guarded([&] {
+        // every refusal is a host check in front of the first launch (SamModel::decode asserts some of them itself)
+        if (n_emb < 1 || count < 1) throw Exception("test_decode_prompts: n_emb and count must be at least 1");
+        if (points < 2 || points > k::kDecoderMaxPoints) throw Exception("test_decode_prompts: 2 to 10 points per prompt");
+        if (!emb || !emb_index || !coords || !labels || !out_logits || !out_iou) throw Exception("test_decode_prompts: null pointer");
+        if (mask_iou && !mask_planes) throw Exception("test_decode_prompts: IoU predictions without the planes they choose from");
+        for (int i = 0; i < count; ++i)
+            if (emb_index[i] < 0 || emb_index[i] >= n_emb) throw Exception("test_decode_prompts: embedding index out of range");
+        const int tokens = 5 + points;
+        const bool masked = mask_planes != nullptr;
+        if (out_state && count != 1) throw Exception("test_decode_prompts: the state is that of a one-prompt call");
+        SamModel& m = impl(env).next_lane(0);
+        if (masked && !m.has_mask_branch())
+            throw Exception("test_decode_prompts: a mask input needs the prompt encoder's mask branch: the model file has no pe.mask.* tensors");
+        if (masked && count > k::decoder_max_prompts(tokens))
+            throw Exception("test_decode_prompts: a masked call takes at most the prompts of one launch");
+        size_t state_floats = 0;
+        std::string layout;
+        for (auto const& part : SamModel::decoder_state_layout(tokens, masked)) {
+            layout += std::string(part.first) + ":" + std::to_string(part.second) + ",";
+            state_floats += part.second;
+        }
+        if (out_layout && layout_capacity > 0) std::snprintf(out_layout, (size_t)layout_capacity, "%s", layout.c_str());
+        if (out_state && (state_capacity < 0 || (size_t)state_capacity < state_floats))
+            throw Exception("test_decode_prompts: the state buffer is too small");
+        // the product's decoder on a lane of replica 0: ONE decode() call for all `count` prompts, cut into launches of
+        // decoder_max_prompts(tokens) prompts by decode() itself
+        std::lock_guard<std::mutex> lock(m.mutex());
+        HIP_CHECK(hipSetDevice(m.device()));
+        const size_t per = (size_t)kTokens * kEmbedDim, planes = (size_t)4 * kLowRes * kLowRes;
+        Upload<float> dev(emb, (size_t)n_emb * per);
+        Upload<float> dev_planes(mask_planes, masked ? (size_t)count * planes : 0);
+        Upload<float> dev_iou(mask_iou, mask_iou ? (size_t)count * 4 : 0);
+        std::vector<float const*> ptrs(count);
+        std::vector<k::MaskSource> sources(count);
+        for (int i = 0; i < count; ++i) {
+            ptrs[i] = dev.get() + (size_t)emb_index[i] * per;
+            if (masked) sources[i] = k::MaskSource{dev_planes.get() + i * planes, mask_iou ? dev_iou.get() + (size_t)i * 4 : nullptr};
+        }
+        m.decode(ptrs.data(), coords, labels, count, points, masked ? sources.data() : nullptr);
+        m.synchronize();
+        download(out_logits, m.logits(), (size_t)count * planes);
+        download(out_iou, m.iou(), (size_t)count * 4);
+        if (out_state) m.decoder_state(out_state, tokens, masked);
     });
 }
 

@@ -85,6 +85,18 @@ DLIMG_API int dlimg_amd_test_attention(int global, uint16_t const* qkv, float co
  * pointers are errors. */
 DLIMG_API int dlimg_amd_test_decode(dlimg_Environment env, int n_emb, float const* emb, int count, int const* emb_index,
                                     float const* coords, float const* labels, float* out_logits, float* out_iou);
+/* The same decoder call with everything SamModel::decode takes: `points` points per prompt (2 .. 10, 5 + points token rows;
+ * coords [count][points][2], labels [count][points]: clicks 1 / 0 in the caller's order, then the box corners 2 / 3 or the
+ * padding point -1) and, optionally, a mask input per prompt: mask_planes [count][4][256][256] (host) and mask_iou [count][4],
+ * the predictions the plane is chosen by on the device (NULL: plane 0).  A call of any size without mask input is cut into
+ * launches by decode(); a masked call takes at most one launch's prompts (112 / (5 + points)).  out_state (optional, count == 1):
+ * the token-side workspaces of that prompt, names and sizes in out_layout ("name:floats,..."), "mask_h" [4096][16] last after a
+ * masked call.  Refused before anything is launched: points out of range, null pointers, an index out of range, a mask input
+ * for a model without pe.mask.*, a masked call above the limit, a state for more than one prompt or a buffer too small. */
+DLIMG_API int dlimg_amd_test_decode_prompts(dlimg_Environment env, int n_emb, float const* emb, int count, int const* emb_index,
+                                            int points, float const* coords, float const* labels, float const* mask_planes,
+                                            float const* mask_iou, float* out_logits, float* out_iou, float* out_state,
+                                            int state_capacity, char* out_layout, int layout_capacity);
 /* K17: the stb_image_resize-equivalent longest-side resampler (default filter, sRGB, clamp):
  * pixels [height][stride] -> out_pixels [out_h][out_w * bytes_per_pixel] packed. */
 DLIMG_API int dlimg_amd_test_resize(uint8_t const* pixels, int width, int height, int stride, int channels, int out_w,

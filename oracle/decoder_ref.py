@@ -26,9 +26,10 @@ Rounding points (F16_POINTS), read off csrc/sam_model.cpp and csrc/kernels/decod
   attn_h   the image -> token attention output, cast to f16 as the A operand of the Wo MFMA (image_update_kernel).
   gelu_h   GELU(LayerNorm2d(ConvT1)) cast to f16 as the A operand of the ConvT2 MFMA (upscale_logits_kernel).
 
-Taps (names of `dlimg_amd_decoder_state`, one prompt):
-  tokens     [7,256]  iou token, 4 mask tokens, the 2 prompt tokens (tokens_)
-  queries    [7,256]  the last two-way block's token rows after the MLP residual, before norm3 (queries_)
+Taps (names of `dlimg_amd_decoder_state` and of the state of `dlimg_amd_test_decode_prompts`, one prompt of n points,
+T = 5 + n token rows: 7 for the two-point prompts, up to 15):
+  tokens     [T,256]  iou token, 4 mask tokens, the n prompt tokens in the order of the packed prompt (tokens_)
+  queries    [T,256]  the last two-way block's token rows after the MLP residual, before norm3 (queries_)
   keys_head  [16,256] the first 16 rows of the final fp32 keys (keys_), after the last block's norm4
   hyper      [4,32]   the hyper-network outputs (hyper_)
   iou        [4]      the IoU predictions (iou_)
@@ -89,7 +90,8 @@ def image_pe(gauss) -> np.ndarray:
 
 
 def embed_prompt(coords, labels, p) -> np.ndarray:
-    """SamOnnxModel._embed_points in float64: coords [2,2] in resized-image pixels, labels [2] -> [2,256]."""
+    """SamOnnxModel._embed_points in float64: coords [n,2] in resized-image pixels, labels [n] (0 / 1: a background / foreground
+    click, 2 / 3: box corners, -1: the padding point) -> [n,256]."""
     c = (np.asarray(coords, f64).reshape(-1, 2) + 0.5) / IMAGE_SIZE
     e = _pe_encoding(c, p["pe.gauss"])
     lab = np.asarray(labels, f64).reshape(-1)[:, None]
@@ -120,7 +122,7 @@ def _token_attention(q_in, k_in, v_in, p, pre):
 
 
 def decode(emb, coords, labels, params, round_at: Iterable[str] = (), taps: Optional[dict] = None):
-    """Embedding [4096,256] + packed prompt (coords [2,2], labels [2]) -> (logits [4,256,256], iou [4]), float64, with
+    """Embedding [4096,256] + packed prompt (coords [n,2], labels [n], any n) -> (logits [4,256,256], iou [4]), float64, with
     f16 rounding at the points named in `round_at` (a subset of F16_POINTS)."""
     round_at = frozenset(round_at)
     unknown = round_at - set(F16_POINTS)

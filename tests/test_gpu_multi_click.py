@@ -11,7 +11,8 @@ without a box, 7 .. 15 token rows in the decoder, plane 0 out from two clicks on
 * one click through the new form has the bits of today's point call, one click and a box those of today's box + point call;
 * a call that mixes prompts of 7, 8, 9, 12 and 15 token rows over both images, 1 .. 20 prompts (the 8 prompts of a lane's
   chunk, and the per-launch cut of 7 prompts at 15 rows: the 20-prompt call has eight of them; a lane never gets more than
-  8 prompts, so the cuts of 12 prompts at 9 rows and 9 at 12 are reached by the planner's CPU tests only), gives every prompt
+  8 prompts, so through this route the cuts of 12 prompts at 9 rows and 9 at 12 are reached by the planner's CPU tests only;
+  on the GPU every cut runs in test_gpu_decoder_prompts.py, through the decoder's test hook), gives every prompt
   the bits of a call of its own; the device-output form gives the host form's bits, offsets tightly packed, also under two
   replicas; a two-token call in between leaves nothing behind;
 * 9 clicks, a continuation entry in front and a label other than 0 / 1 are refused, and the handle works afterwards.
