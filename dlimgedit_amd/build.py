@@ -44,6 +44,7 @@ SOURCES = [
     "kernels/attention_global.hip",
     "kernels/decoder.hip",
     "kernels/decoder_image.hip",
+    "kernels/decoder_hq.hip",
     "kernels/postprocess.hip",
     "kernels/resize.hip",
     "kernels/objects.hip",

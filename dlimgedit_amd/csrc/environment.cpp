@@ -368,9 +368,12 @@ SamModel& EnvironmentImpl::next_lane(int replica) {
     return *l.lanes[replicas_[replica]->next_lane.fetch_add(1) % l.lanes.size()];
 }
 
-float* EmbeddingPool::take() {
+float* EmbeddingPool::take(size_t floats) {
+    if (floats == 0) floats = (size_t)kTokens * kEmbedDim;
     {
         std::lock_guard<std::mutex> lock(mutex_);
+        if (floats_ == 0) floats_ = floats;
+        DLIMG_ASSERT(floats_ == floats);         // one model per environment: every buffer of a pool has its size
         if (!free_.empty()) {
             float* p = free_.back();
             free_.pop_back();
@@ -379,7 +382,7 @@ float* EmbeddingPool::take() {
     }
     HIP_CHECK(hipSetDevice(device_));
     float* p = nullptr;
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), (size_t)kTokens * kEmbedDim * sizeof(float)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), floats * sizeof(float)));
     return p;
 }
 

@@ -38,13 +38,16 @@ class EmbeddingPool {
     ~EmbeddingPool();
     EmbeddingPool(EmbeddingPool const&) = delete;
     EmbeddingPool& operator=(EmbeddingPool const&) = delete;
-    float* take();
+    // floats: the size of a buffer, the same for every buffer of the pool (handle_floats(): a SAM-HQ model's handles keep
+    // the image's HQ features behind the embedding); 0: the embedding alone
+    float* take(size_t floats = 0);
     void give(float* buffer) noexcept;
 
   private:
     int device_;
     std::mutex mutex_;
     std::vector<float*> free_;
+    size_t floats_ = 0;                  // set by the first take()
 };
 
 class EnvironmentImpl {

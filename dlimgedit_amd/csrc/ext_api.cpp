@@ -98,7 +98,7 @@ DLIMG_API int dlimg_amd_get_logits(dlimg_Segmentation seg, int const* point, int
         std::lock_guard<std::mutex> lock(m.mutex());
         HIP_CHECK(hipSetDevice(m.device()));
         float const* emb = s.embedding();
-        m.decode(&emb, coords, labels, 1);
+        m.decode(&emb, coords, labels, 1, 2, nullptr, /*handles*/ true);
         m.synchronize();
         download(out_logits, m.logits(), (size_t)4 * kLowRes * kLowRes);
         download(out_iou, m.iou(), 4);
@@ -112,9 +112,18 @@ DLIMG_API int dlimg_amd_decoder_state(dlimg_Segmentation seg, int const* point, 
         DLIMG_ASSERT(s.embedding() != nullptr && point != nullptr);
         std::string layout;
         size_t total = 0;
-        for (auto const& part : SamModel::decoder_state_layout()) {
+        // a SAM-HQ model: the prompt has 8 token rows (the HQ token last), and the layout grows at its end by "hyper_hq"
+        // and the image's "hq_features" [256][256][32]
+        const bool hq = s.environment().lane(s.replica(), 0).has_hq();
+        const auto parts = hq ? SamModel::decoder_state_layout(kDecTokens + 1, false, true) : SamModel::decoder_state_layout();
+        for (auto const& part : parts) {
             layout += std::string(part.first) + ":" + std::to_string(part.second) + ",";
             total += part.second;
+        }
+        const size_t state_floats = total;
+        if (hq) {
+            layout += "hq_features:" + std::to_string(kHqFeatureFloats) + ",";
+            total += kHqFeatureFloats;
         }
         if (out_layout && layout_capacity > 0) {
             std::snprintf(out_layout, (size_t)layout_capacity, "%s", layout.c_str());
@@ -128,8 +137,12 @@ DLIMG_API int dlimg_amd_decoder_state(dlimg_Segmentation seg, int const* point, 
         std::lock_guard<std::mutex> lock(m.mutex());
         HIP_CHECK(hipSetDevice(m.device()));
         float const* emb = s.embedding();
-        m.decode(&emb, coords, labels, 1);
+        m.decode(&emb, coords, labels, 1, 2, nullptr, /*handles*/ true);
         m.synchronize();
+        if (hq) {
+            m.decoder_state(out, kDecTokens + 1, false, true);
+            download(out + state_floats, emb + kEmbeddingFloats, kHqFeatureFloats);
+        } else
         m.decoder_state(out);
     });
 }
@@ -352,6 +365,11 @@ DLIMG_API int dlimg_amd_encode_and_mask(dlimg_Environment env, dlimg_ImageView c
     return guarded([&] {
         DLIMG_ASSERT(dev_images != nullptr && points != nullptr && dev_masks != nullptr && count > 0);
         EnvironmentImpl& e = impl(env);
+        // the asynchronous path decodes from the lane's own embeddings, which carry no handle and so no HQ features
+        if (e.lane(0, 0).has_hq())
+            throw Exception("dlimg_amd_encode_and_mask does not serve a SAM-HQ model (dec.hq.* in the model file): the asynchronous "
+                            "path keeps no Segmentation handle, and the HQ features of an image live in its handle -- use "
+                            "process / compute_mask or the batch calls");
         for (int i = 0; i < count; ++i) {
             check_device_image(dev_images[i]);       // refused here, not when its pass is enqueued
             DLIMG_ASSERT(dev_masks[i] != nullptr);

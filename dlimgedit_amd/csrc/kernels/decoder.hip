@@ -32,11 +32,13 @@ constexpr int NTOK_IMG = 4096;
 // (segmentation.cpp:135-152 packs two; labels 1/-1 for a point, 2/3 for a box; SAM's PromptEncoder.forward puts the point
 // in front of the box corners and sends no pad token with a box: labels 1, 2, 3).
 // Column c of the TOK token rows of prompt p: iou token, 4 mask tokens, the prompt points.
-template <int TOK, typename Prompts>
+// HQ (SAM-HQ models): the last packed point is the pseudo-point of the HQ token (kernels.hpp, kDecoderHqLabel): its row is
+// hq_token[c] alone.
+template <int TOK, bool HQ = false, typename Prompts>
 DLIMG_DEVICE void prompt_token_column(const Prompts& pr, int p, int c, const float* __restrict__ gauss,
                                       const float* __restrict__ point_embed, const float* __restrict__ not_a_point,
                                       const float* __restrict__ iou_token, const float* __restrict__ mask_tokens,
-                                      float (&out)[TOK]) {
+                                      float (&out)[TOK], const float* __restrict__ hq_token = nullptr) {
     constexpr int NPTS = TOK - OUT_TOK;
     out[0] = iou_token[c];
 #pragma unroll
@@ -44,6 +46,12 @@ DLIMG_DEVICE void prompt_token_column(const Prompts& pr, int p, int c, const flo
     const int kf = c & 127;
 #pragma unroll
     for (int i = 0; i < NPTS; ++i) {
+        if constexpr (HQ) {
+            if (i == NPTS - 1) {
+                out[OUT_TOK + i] = hq_token[c];
+                continue;
+            }
+        }
         const float x = (pr.coords[(p * NPTS + i) * 2 + 0] + 0.5f) / 1024.0f;
         const float y = (pr.coords[(p * NPTS + i) * 2 + 1] + 0.5f) / 1024.0f;
         float v = __fadd_rn(__fmul_rn(2.0f * x - 1.0f, gauss[kf]), __fmul_rn(2.0f * y - 1.0f, gauss[128 + kf]));
@@ -757,16 +765,18 @@ DLIMG_DEVICE void head_layer(const float* x /*LDS*/, const float* __restrict__ w
 
 // The workgroup first finishes the final token-to-image attention for ITS token (merge of the partials, output projection,
 // residual: see merge_partials) and applies norm_final_attn to it.
-template <int TOK /*rows per prompt*/>
+// HQ (SAM-HQ models): grid row 5 does the same for the HQ token, row TOK - 1, with SAM-HQ's MLP, and writes hyper_hq [P][32].
+struct HeadWeightsHq : k::HeadWeights { k::HqHead hq; };
+template <int TOK /*rows per prompt*/, bool HQ = false>
 __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float* __restrict__ part, k::TokenLinear out,
                                                                     const float* __restrict__ out_wt, k::TokenRows norm,
-                                                                    k::HeadWeights hw, float* __restrict__ hyper,
-                                                                    float* __restrict__ iou) {
+                                                                    std::conditional_t<HQ, HeadWeightsHq, k::HeadWeights> hw,
+                                                                    float* __restrict__ hyper, float* __restrict__ iou) {
     __shared__ __attribute__((aligned(16))) float x0[DIM], x1[DIM], x2[DIM], att[INNER];
     __shared__ float opart[4][DIM];
     __shared__ float2_t stat[1], stat_res[1];
     const int p = blockIdx.x, mi = blockIdx.y;
-    const int tok = mi < 4 ? 1 + mi : 0;
+    const int tok = mi < 4 ? 1 + mi : (HQ && mi == 5 ? TOK - 1 : 0);
     const int row = p * TOK + tok;
     // one round trip: this thread's 32 weights of the output projection (column c, k quarter kq), the partials, the residual
     const int c = threadIdx.x & (DIM - 1), kq = threadIdx.x >> 8;
@@ -808,6 +818,16 @@ __global__ __launch_bounds__(HEAD_THREADS) void output_heads_kernel(const float*
     if (threadIdx.x < DIM)
         x0[threadIdx.x] = (x1[threadIdx.x] - stat[0][0]) * stat[0][1] * norm.ln_w[threadIdx.x] + norm.ln_b[threadIdx.x];
     __syncthreads();
+    if constexpr (HQ) {
+        if (mi == 5) {
+            head_layer<DIM>(x0, hw.hq.w[0], hw.hq.b[0], DIM, true, x1);
+            __syncthreads();
+            head_layer<DIM>(x1, hw.hq.w[1], hw.hq.b[1], DIM, true, x2);
+            __syncthreads();
+            head_layer<32>(x2, hw.hq.w[2], hw.hq.b[2], 32, false, hw.hq.hyper_hq + (size_t)p * 32);
+            return;
+        }
+    }
     head_layer<DIM>(x0, hw.w[mi][0], hw.b[mi][0], DIM, true, x1);
     __syncthreads();
     head_layer<DIM>(x1, hw.w[mi][1], hw.b[mi][1], DIM, true, x2);
@@ -867,15 +887,24 @@ static_assert(sizeof(DecoderStartMasked<7>) <= 2560 && sizeof(DecoderStartMasked
               sizeof(DecoderStartMasked<10>) <= 2560 && sizeof(DecoderStartMasked<11>) <= 2560 && sizeof(DecoderStartMasked<12>) <= 2560 &&
               sizeof(DecoderStartMasked<13>) <= 2560 && sizeof(DecoderStartMasked<14>) <= 2560 && sizeof(DecoderStartMasked<15>) <= 2560,
               "the prompts travel as kernel arguments");
-template <int TOK, bool MASKED>
-using DecoderStartArgs = std::conditional_t<MASKED, DecoderStartMasked<TOK>, DecoderStart<TOK>>;
+// HQ (SAM-HQ models) is a template parameter like MASKED: the other instantiations keep their arguments and their code.
+template <typename Base> struct WithHqToken : Base { const float* hq_token; };
+template <int TOK, bool MASKED, bool HQ = false>
+using DecoderStartArgs = std::conditional_t<HQ, WithHqToken<std::conditional_t<MASKED, DecoderStartMasked<TOK>, DecoderStart<TOK>>>,
+                                            std::conditional_t<MASKED, DecoderStartMasked<TOK>, DecoderStart<TOK>>>;
+static_assert(sizeof(WithHqToken<DecoderStartMasked<15>>) <= 2568 && sizeof(WithHqToken<DecoderStartMasked<8>>) <= 2568,
+              "the prompts travel as kernel arguments");
 
-template <int TOK, bool MASKED = false>
-__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStartArgs<TOK, MASKED> a) {
+template <int TOK, bool MASKED = false, bool HQ = false>
+__global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStartArgs<TOK, MASKED, HQ> a) {
     __shared__ __attribute__((aligned(16))) float rows[TL_ROW_SLICE<TOK> * DIM];
     const int c = threadIdx.x;
     if ((int)blockIdx.x < a.P) {
         float v[TOK];
+        if constexpr (HQ)
+            prompt_token_column<TOK, true>(a.prompts, blockIdx.x, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v,
+                                           a.hq_token);
+        else
         prompt_token_column<TOK>(a.prompts, blockIdx.x, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
 #pragma unroll
         for (int t = 0; t < TOK; ++t) a.tokens[((size_t)blockIdx.x * TOK + t) * DIM + c] = v[t];
@@ -890,6 +919,10 @@ __global__ __launch_bounds__(256) void decoder_start_kernel(DecoderStartArgs<TOK
         const TokenColumn w_first = token_column_prefetch(op, first, row0, row1);
         for (int p = row0 / TOK; p * TOK < row1; ++p) {
             float v[TOK];
+            if constexpr (HQ)
+                prompt_token_column<TOK, true>(a.prompts, p, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v,
+                                               a.hq_token);
+            else
             prompt_token_column<TOK>(a.prompts, p, c, a.gauss, a.point_embed, a.not_a_point, a.iou_token, a.mask_tokens, v);
 #pragma unroll
             for (int t = 0; t < TOK; ++t) rows[(p * TOK + t - row0) * DIM + c] = v[t];
@@ -1056,9 +1089,16 @@ namespace {
 struct StartMask { const float* const* h; const float* proj_w; const float* proj_b; };
 void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                           const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* no_mask, const StartMask* mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+                          const float* no_mask, const StartMask* mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
+                          const float* hq_token) {
     if (P <= 0) return;
     if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 to 15 tokens per prompt");
+    if (hq_token) {
+        if (T < 8) throw_error("decoder_start: a SAM-HQ prompt has at least 8 token rows (the HQ token travels as the last one)");
+        for (int i = 0; i < P && i < decoder_max_prompts(T); ++i)
+            if (prompts.labels[(size_t)i * (T - 5) + (T - 6)] != kDecoderHqLabel)
+                throw_error("decoder_start: the last point of a SAM-HQ prompt is the HQ token's pseudo-point");
+    }
     if (P > decoder_max_prompts(T) || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
     if (mask) {
         if (!mask->h || !mask->proj_w || !mask->proj_b) throw_error("decoder_start: a masked launch needs the mask branch's rows and weights");
@@ -1091,6 +1131,23 @@ void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, con
     };
     DLIMG_FOR_TOKENS(T, "decoder_start",
         static_assert(TL_PROMPT_SLICE<TOK> == decoder_prompt_slice(TOK), "fill() cuts the first linears as the kernel does");
+        if constexpr (TOK >= 8) {
+            if (hq_token && mask) {
+                WithHqToken<DecoderStartMasked<TOK>> a{};
+                fill(a);
+                for (int i = 0; i < P; ++i) a.h[i] = mask->h[i];
+                a.proj_w = mask->proj_w; a.proj_b = mask->proj_b; a.hq_token = hq_token;
+                hipLaunchKernelGGL((decoder_start_kernel<TOK, true, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
+                return;
+            }
+            if (hq_token) {
+                WithHqToken<DecoderStart<TOK>> a{};
+                fill(a);
+                a.hq_token = hq_token;
+                hipLaunchKernelGGL((decoder_start_kernel<TOK, false, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
+                return;
+            }
+        }
         if (mask) {
             DecoderStartMasked<TOK> a{};
             fill(a);
@@ -1107,17 +1164,18 @@ void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, con
 
 void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s, const float* hq_token) {
     launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, no_mask, nullptr, keys,
-                         keys_h, P, T, s);
+                         keys_h, P, T, s, hq_token);
 }
 
 void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                           const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s) {
+                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
+                          const float* hq_token) {
     const StartMask mask{h, branch.proj_w, branch.proj_b};
     launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, nullptr, &mask, keys,
-                         keys_h, P, T, s);
+                         keys_h, P, T, s, hq_token);
 }
 
 void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h, int P, hipStream_t s) {
@@ -1241,9 +1299,20 @@ void token_to_image_partials(const float* q, const TokenLinear* q_proj, const ha
 }
 
 void output_heads(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenRows& norm,
-                  const HeadWeights& hw, float* hyper, float* iou, int P, int T, hipStream_t s) {
+                  const HeadWeights& hw, float* hyper, float* iou, int P, int T, hipStream_t s, const HqHead* hq) {
     if (P <= 0) return;
     if (out.K != INNER || out.N != DIM || !norm.ln_w) throw_error("output_heads: unsupported shape");
+    if (hq) {
+        if (T < 8 || !hq->hyper_hq || !hq->w[0] || !hq->w[1] || !hq->w[2] || !hq->b[0] || !hq->b[1] || !hq->b[2] ||
+            (((uintptr_t)hq->w[0] | (uintptr_t)hq->w[1] | (uintptr_t)hq->w[2]) & 15))
+            throw_error("output_heads: the SAM-HQ head needs its MLP, its output and a prompt of at least 8 token rows");
+        HeadWeightsHq hwq;
+        static_cast<HeadWeights&>(hwq) = hw;
+        hwq.hq = *hq;
+        DLIMG_FOR_TOKENS(T, "output_heads",
+            hipLaunchKernelGGL((output_heads_kernel<TOK, true>), dim3(P, 6), dim3(HEAD_THREADS), 0, s, scratch, out, out_wt, norm, hwq, hyper, iou);)
+        return;
+    }
     DLIMG_FOR_TOKENS(T, "output_heads",
         hipLaunchKernelGGL(output_heads_kernel<TOK>, dim3(P, 5), dim3(HEAD_THREADS), 0, s, scratch, out, out_wt, norm, hw, hyper, iou);)
 }

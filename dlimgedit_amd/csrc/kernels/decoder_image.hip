@@ -242,7 +242,11 @@ struct Upscale {
     int rows_per_block;
 };
 
-__global__ __launch_bounds__(256) void upscale_logits_kernel(Upscale a) {
+// STORE_U (SAM-HQ models): the up-scaled embedding itself is stored as well, [P][256][256][32] f16 in raster order, for the HQ
+// mask path (decoder_hq.hip); the other instantiation keeps its arguments and its code.
+struct UpscaleStore : Upscale { half_t* u_out; };
+template <bool STORE_U>
+__global__ __launch_bounds__(256) void upscale_logits_kernel(std::conditional_t<STORE_U, UpscaleStore, Upscale> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     half_t* w1 = reinterpret_cast<half_t*>(smem);
     half_t* w2 = w1 + (size_t)UP_W1ROWS * UP_W1STRIDE;
@@ -408,6 +412,12 @@ __global__ __launch_bounds__(256) void upscale_logits_kernel(Upscale a) {
             const float total = (odd ? k1 : k0) + __shfl_xor(odd ? k0 : k1, 16, 64);
             const int Y = 4 * ty + 2 * (s1 >> 1) + (s2 >> 1), X = 4 * tx + 2 * (s1 & 1) + (s2 & 1);
             out[Y * 256 + X] = total;
+            if constexpr (STORE_U) {
+                half_t* ud = a.u_out + (((size_t)p * 256 + Y) * 256 + X) * 32 + 4 * g;
+#pragma unroll
+                for (int jl = 0; jl < 2; ++jl)
+                    *reinterpret_cast<half4_t*>(ud + 16 * jl) = half4_t{(half_t)u[jl][0], (half_t)u[jl][1], (half_t)u[jl][2], (half_t)u[jl][3]};
+            }
         }
     }
     }
@@ -446,16 +456,25 @@ void image_update(const half_t* q, int ldq, const float* tk, const float* tv, co
 
 
 void upscale_logits(const half_t* keys_h, const half_t* W1, const float* b1, const float* ln_w, const float* ln_b, float eps,
-                    const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t s) {
+                    const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t s, half_t* u_out) {
     if (P <= 0) return;
-    if (((uintptr_t)keys_h | (uintptr_t)W1 | (uintptr_t)W2) & 15) throw_error("upscale_logits: operands must be 16-byte aligned");
-    static k::LdsOptIn opt_in;
-    opt_in.ensure((const void*)upscale_logits_kernel, UP_LDS, "upscale_logits: the device refuses the kernel's LDS size");
+    if (((uintptr_t)keys_h | (uintptr_t)W1 | (uintptr_t)W2 | (uintptr_t)u_out) & 15) throw_error("upscale_logits: operands must be 16-byte aligned");
+    static k::LdsOptIn opt_in, opt_in_store;
+    if (u_out) opt_in_store.ensure((const void*)upscale_logits_kernel<true>, UP_LDS, "upscale_logits: the device refuses the kernel's LDS size");
+    else
+    opt_in.ensure((const void*)upscale_logits_kernel<false>, UP_LDS, "upscale_logits: the device refuses the kernel's LDS size");
     // two workgroups per group of rows (one per pair of first-stage sub-pixels), one workgroup per CU (89 KB of LDS): the
     // smallest row groups that still fit the chip in one round
     const int rows_per_block = 2 * P * (NTOK_IMG / 64) <= 256 ? 64 : (2 * P * (NTOK_IMG / 128) <= 256 ? 128 : 256);
     Upscale a{keys_h, W1, b1, ln_w, ln_b, eps, W2, b2, hyper, logits, rows_per_block};
-    hipLaunchKernelGGL(upscale_logits_kernel, dim3(2 * P * NTOK_IMG / rows_per_block), dim3(256), UP_LDS, s, a);
+    if (u_out) {
+        UpscaleStore au;
+        static_cast<Upscale&>(au) = a;
+        au.u_out = u_out;
+        hipLaunchKernelGGL(upscale_logits_kernel<true>, dim3(2 * P * NTOK_IMG / rows_per_block), dim3(256), UP_LDS, s, au);
+        return;
+    }
+    hipLaunchKernelGGL(upscale_logits_kernel<false>, dim3(2 * P * NTOK_IMG / rows_per_block), dim3(256), UP_LDS, s, a);
 }
 
 }  // namespace k

@@ -194,9 +194,14 @@ struct DecoderPrompts {
 // First launch of a decode.  tokens [P,T,256]: iou token, 4 mask tokens, T - 5 prompt tokens (the positional part later steps
 // add); `first` (n_first <= 5 layers, K = 256, no LayerNorm / residual; their `in` is ignored) are applied to those same
 // rows in this launch.  Image side: keys = emb[p] + no_mask (fp32 + f16) for all prompts.
+// hq_token (optional, [256]): the prompts of a SAM-HQ model.  Their LAST point is a pseudo-point that carries SAM-HQ's output
+// token: its label is kDecoderHqLabel, a value no caller's label can be, and its token row (row T - 1) is hq_token and nothing
+// else -- no Fourier term, no point embedding.  The two-way transformer does not care where a row stands, so the HQ token
+// travels as one more trailing row through every token-side kernel unchanged; output_heads reads it back from row T - 1.
+constexpr float kDecoderHqLabel = -1024.0f;
 void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                    const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s);
+                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s, const float* hq_token = nullptr);
 // Mask input (SAM's click-to-refine loop: the low-res logits of the previous step through the prompt encoder's mask branch).
 // MaskBranch: the branch's tensors as the model file holds them, fp32 -- conv 2x2 / 2 w1 [4][1][2][2], b1 [4]; LayerNorm2d
 // ln1 [4]; conv 2x2 / 2 w2 [16][4][2][2], b2 [16]; LayerNorm2d ln2 [16]; 1x1 conv proj_w [256][16], proj_b [256].
@@ -217,7 +222,8 @@ void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h /*[P][
 // of emb[p] + no_mask, which SAM's dense embedding replaces.  h: host array of P device pointers ([4096][16] each).
 void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
                           const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s);
+                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
+                          const float* hq_token = nullptr);
 // up to 5 layers over the same rows (<= 112, whole prompts of T rows) in one launch
 void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t);
 // self-attention among the T tokens of each prompt + its output projection `out` (K = 256) in one launch
@@ -245,14 +251,34 @@ void image_update(const half_t* q, int ldq, const float* tk, const float* tv, co
 // Up-scaling path + mask product in one launch (kernels/decoder_image.hip): logits [P,4,256,256] from the f16 keys, the two
 // transposed convolutions as GEMM weights (W1 [256][256], rows = sub-pixel * 64 + channel; W2 [128][64], rows = sub-pixel * 32
 // + channel), the LayerNorm2d between them and the hyper vectors [P,4,32].
+// u_out (optional, SAM-HQ models): the up-scaled embedding itself, [P][256][256][32] f16 in raster order -- the values the
+// mask product is taken with -- for hq_mask_path.
 void upscale_logits(const half_t* keys_h, const half_t* W1, const float* b1, const float* ln_w, const float* ln_b, float eps,
-                    const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t);
+                    const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t, half_t* u_out = nullptr);
 // hyper-network MLPs (4 x 256->256->256->32) and IoU head (256->256->256->4) on the output tokens: the launch finishes the
 // final token-to-image attention (scratch, out, out_wt as above) for the five tokens it needs (rows 0..4 of each prompt's
 // T) and applies `norm` to them
 struct HeadWeights { const float* w[5][3]; const float* b[5][3]; };
+// hq (optional, SAM-HQ models): one more workgroup per prompt does the same for row T - 1, the HQ token, runs SAM-HQ's MLP
+// (256->256->256->32) on it and writes hyper_hq [P,32].
+struct HqHead { const float* w[3]; const float* b[3]; float* hyper_hq; };
 void output_heads(const float* scratch, const TokenLinear& out, const float* out_wt, const TokenRows& norm /*ln_w, ln_b, eps*/,
-                  const HeadWeights& hw, float* hyper /*[P,4,32]*/, float* iou /*[P,4]*/, int P, int T, hipStream_t);
+                  const HeadWeights& hw, float* hyper /*[P,4,32]*/, float* iou /*[P,4]*/, int P, int T, hipStream_t,
+                  const HqHead* hq = nullptr);
+
+// ---- SAM-HQ (kernels/decoder_hq.hip) ---------------------------------------------------------
+// Per image: hq_features [256][256][32] fp32 in raster order = the two branches' second transposed convolutions (GEMM results
+// [4096 * 4][128], row = token * 4 + first sub-pixel, column = second sub-pixel * 32 + channel, without bias) + both biases.
+void hq_features_finish(const float* vit, const float* emb, const float* b_vit, const float* b_emb, float* out, hipStream_t);
+// Per prompt: logits[p][m] += hyper_hq[p] . (conv2_3x3(GELU(LN2d(conv1_3x3(U[p])))) + features[p]) for the four planes m.
+// U: [P][256][256][32] f16 (upscale_logits' u_out); H: workspace [P][256][256][64] f16; features: host array of P device
+// pointers; conv1_w [9][64][32] and conv2_w [9][32][64] f16, tap-major (tap = ky * 3 + kx), then output, then input channel.
+struct HqMaskWeights {
+    const half_t* conv1_w = nullptr; const float* conv1_b = nullptr; const float* ln_w = nullptr; const float* ln_b = nullptr;
+    const half_t* conv2_w = nullptr; const float* conv2_b = nullptr;
+};
+void hq_mask_path(const half_t* U, const HqMaskWeights& w, float eps, half_t* H, const float* const* features,
+                  const float* hyper_hq, float* logits, int P, hipStream_t);
 
 // ---- mask post-processing (K16) --------------------------------------------------------------
 // For each of `count` jobs: logits plane job.src (256x256 f32, device) -> two-stage bilinear

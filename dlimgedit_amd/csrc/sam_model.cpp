@@ -130,6 +130,14 @@ void SamModel::reserve_encoder(int batch) {
     hid_.reserve(M * wide);
     neck_f32_.reserve(M * kEmbedDim);
     emb_.reserve(M * kEmbedDim);
+    if (W.has_hq()) {
+        hq_a_.reserve(M * 4 * kEmbedDim);
+        hq_h_.reserve(M * 4 * kEmbedDim);
+        hq_vit_.reserve(M * 4 * 128);
+        hq_embf_.reserve(M * 4 * 128);
+        emb_h_.reserve(M * kEmbedDim);
+        hq_feat_.reserve((size_t)batch * kHqFeatureFloats);
+    }
     enc_batch_ = batch;
 }
 
@@ -429,6 +437,9 @@ void SamModel::encode(int batch, float* const* emb_dst) {
     writes_stream(g);
     gemm(g, ST_GEMM_PATCH);
 
+    int layer_index = 0, first_global = -1;
+    for (int gi : W.geom_.global_attn_indexes)
+        if (first_global < 0 || gi < first_global) first_global = gi;
     for (EncoderLayer const& L : W.layers_) {
         g = k::GemmArgs{};
         reads_stream(g, L.qkv, L.ln1);
@@ -460,6 +471,16 @@ void SamModel::encode(int batch, float* const* emb_dst) {
         stream_residual(g);
         writes_stream(g);
         gemm(g, ST_GEMM_FC2);
+        // SAM-HQ: the early ViT feature is the output of the FIRST global-attention block; xn_ holds its f16 copy right here
+        if (W.has_hq() && layer_index == first_global) {
+            if (!fused) {
+                clock_.timed(ST_ENC_OTHER, (double)M * D * 6, [&] {
+                    k::add_cast(x_.get(), nullptr, 0, (size_t)M * D, nullptr, xn_.get(), stream_);
+                });
+            }
+            hq_gemm_pair(xn_.get(), D, W.hq_vit1_, W.hq_vit_ln_, W.hq_vit2_, M, hq_vit_.get());
+        }
+        ++layer_index;
     }
 
     // neck: 1x1 conv -> LayerNorm2d -> 3x3 conv (pad 1) -> LayerNorm2d, all channel-last
@@ -501,8 +522,20 @@ void SamModel::encode(int batch, float* const* emb_dst) {
     *pass_flag_ = 0;
     clock_.timed(ST_LAYERNORM, (double)M * kEmbedDim * 8, [&] {
         k::layernorm(neck_f32_.get(), W.neck_ln2_.w.get(), W.neck_ln2_.b.get(), kLnEps, M, kEmbedDim, k::ACT_NONE,
-                     direct ? direct : emb_.get(), nullptr, stream_, pass_flag_);
+                     direct ? direct : emb_.get(), W.has_hq() ? emb_h_.get() : nullptr, stream_, pass_flag_);
     });
+    if (W.has_hq()) {
+        // the embedding branch of the HQ features, then per image: both branches and their biases, in raster order, behind
+        // the embedding in the handle's buffer (or in the lane's workspace when the pass has no handle)
+        hq_gemm_pair(emb_h_.get(), kEmbedDim, W.hq_emb1_, W.hq_emb_ln_, W.hq_emb2_, M, hq_embf_.get());
+        clock_.timed(ST_ENC_OTHER, (double)batch * kHqFeatureFloats * 12, [&] {
+            for (int i = 0; i < batch; ++i) {
+                float* dst = (emb_dst && emb_dst[i]) ? emb_dst[i] + kEmbeddingFloats : hq_feat_.get() + (size_t)i * kHqFeatureFloats;
+                const size_t off = (size_t)i * kTokens * 4 * 128;
+                k::hq_features_finish(hq_vit_.get() + off, hq_embf_.get() + off, W.hq_vit2_.b.get(), W.hq_emb2_.b.get(), dst, stream_);
+            }
+        });
+    }
     if (emb_dst && !direct) {
         const size_t n = (size_t)kTokens * kEmbedDim;
         for (int i = 0; i < batch; ++i)
@@ -511,6 +544,25 @@ void SamModel::encode(int batch, float* const* emb_dst) {
     }
     HIP_CHECK(hipGetLastError());     // a refused launch (bad grid, LDS size) is reported here, not at a later sync
     mark_activity();                  // behind the last kernel of the pass
+}
+
+// One branch of SAM-HQ's per-image features: two transposed convolutions (kernel 2, stride 2) as GEMMs over the image
+// positions with a LayerNorm2d + GELU between them, which is a ROW LayerNorm once the first result [M][4 * C] is read as
+// [4 M][C].  a: f16 [M][K]; out: fp32 [4 M][128], row = token * 4 + first sub-pixel, column = second sub-pixel * 32 + channel,
+// without the second convolution's bias (hq_features_finish adds it).
+void SamModel::hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out) {
+    const int C = conv1.out / 4;                 // channels between the two convolutions: 256 (ViT branch) or 64 (embedding branch)
+    k::GemmArgs g;
+    g.A = a; g.lda = K; g.W = conv1.w.get(); g.ldw = K; g.bias = conv1.b.get();
+    g.out_f32 = hq_a_.get(); g.ldc32 = conv1.out; g.M = M; g.N = conv1.out; g.K = K;
+    gemm(g);
+    clock_.timed(ST_LAYERNORM, (double)M * conv1.out * 6, [&] {
+        k::layernorm(hq_a_.get(), ln.w.get(), ln.b.get(), kLnEps, 4 * M, C, k::ACT_GELU, nullptr, hq_h_.get(), stream_);
+    });
+    g = k::GemmArgs{};
+    g.A = hq_h_.get(); g.lda = C; g.W = conv2.w.get(); g.ldw = C;
+    g.out_f32 = out; g.ldc32 = conv2.out; g.M = 4 * M; g.N = conv2.out; g.K = C;
+    gemm(g);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -538,14 +590,48 @@ void SamModel::reserve_decoder(int count) {
     tt2i_.reserve(T * 256);
     t2i_part_.reserve(k::token_to_image_scratch_floats((int)P, kDecMaxTokens));
     tmlp_.reserve(T * 2048);
+    if (weights_->has_hq()) {
+        // the 3x3 path's workspaces are needed for the prompts of ONE launch (at most 14: 8 token rows)
+        const size_t L = std::min<size_t>(P, k::decoder_max_prompts(8));
+        hyper_hq_.reserve(P * 32);
+        hq_u_.reserve(L * kLowRes * kLowRes * 32);          // 4 MB per prompt
+        hq_mid_.reserve(L * kLowRes * kLowRes * 64);        // 8 MB per prompt
+    }
     dec_count_ = count;
 }
 
+std::string SamModel::hq_refusal(int points) const {
+    if (!has_hq() || points <= kHqMaxPoints) return {};
+    return "a prompt of " + std::to_string(points) + " packed points (8 clicks and a box) is more than a SAM-HQ model takes: at most " +
+           std::to_string(kHqMaxPoints) + " points, because the HQ token of the model file's dec.hq.* group travels as the 15th and last "
+           "token row of the decoder";
+}
+
 void SamModel::decode(float const* const* emb, float const* coords, float const* labels, int count, int points,
-                      k::MaskSource const* mask_input) {
+                      k::MaskSource const* mask_input, bool handles) {
     DLIMG_ASSERT(count > 0);
     if (mask_input && !has_mask_branch()) throw Exception("a mask input needs the prompt encoder's mask branch: the model file has no pe.mask.* tensors");
     DLIMG_ASSERT(points >= 2 && points <= k::kDecoderMaxPoints);
+    std::vector<float> hq_coords, hq_labels;
+    if (has_hq()) {
+        if (!handles)
+            throw Exception("a SAM-HQ model (dec.hq.* in the model file) does not decode bare embeddings: the HQ features of the "
+                            "image are part of the decode, and only a Segmentation handle holds them");
+        const std::string why = hq_refusal(points);
+        if (!why.empty()) throw Exception(why);
+        // the HQ token as one more trailing pseudo-point of every prompt (kernels.hpp, kDecoderHqLabel): from here on the
+        // prompts are those of a plain model with one point more
+        const int np = points + 1;
+        hq_coords.assign((size_t)count * np * 2, 0.f);
+        hq_labels.assign((size_t)count * np, k::kDecoderHqLabel);
+        for (int i = 0; i < count; ++i) {
+            std::copy_n(coords + (size_t)i * points * 2, points * 2, hq_coords.data() + (size_t)i * np * 2);
+            std::copy_n(labels + (size_t)i * points, points, hq_labels.data() + (size_t)i * np);
+        }
+        coords = hq_coords.data();
+        labels = hq_labels.data();
+        points = np;
+    }
     static_assert(5 + k::kDecoderMaxPoints == kDecMaxTokens && k::decoder_tokens_supported(kDecTokens) &&
                   k::decoder_tokens_supported(kDecMaxTokens), "the kernels are built for these token counts");
     reserve_decoder(count);
@@ -571,12 +657,15 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
                             int points, k::MaskSource const* mask_input) {
     SamWeights const& W = *weights_;
     const int TOK = 5 + points;                      // token rows per prompt
+    const bool hq = W.has_hq();
     const int P = count, M = P * kTokens, T = P * TOK;
     hipStream_t s = stream_;
     float* logits_out = logits_.get() + (size_t)first * 4 * kLowRes * kLowRes;
     float* iou_out = iou_.get() + (size_t)first * 4;
 
     auto body = [&] {
+        // a SAM-HQ model: the last point of every prompt is the HQ token's pseudo-point (decode() appended it)
+        float const* hq_token = hq ? W.hq_token_.get() : nullptr;
         // prompts travel as kernel arguments of the first launch
         k::DecoderPrompts prompts{};
         std::memcpy(prompts.coords, coords, (size_t)P * points * 2 * sizeof(float));
@@ -624,10 +713,12 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
                 float const* h[k::kDecoderMaxPrompts];
                 for (int i = 0; i < P; ++i) h[i] = mask_h_.get() + (size_t)i * kTokens * k::kMaskHidden;
                 k::decoder_start_masked(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
-                                        W.mask_tokens_.get(), tokens_.get(), qkv, 3, h, branch, keys_.get(), keys_h_.get(), P, TOK, s);
+                                        W.mask_tokens_.get(), tokens_.get(), qkv, 3, h, branch, keys_.get(), keys_h_.get(), P, TOK, s,
+                                        hq_token);
             } else
             k::decoder_start(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
-                             W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, TOK, s);
+                             W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, TOK, s,
+                             hq_token);
         }
         for (int i = 0; i < 2; ++i) {
             DecoderLayer const& L = W.dec_[i];
@@ -681,19 +772,34 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
                 hw.w[m][j] = W.heads_[m][j].w.get();
                 hw.b[m][j] = W.heads_[m][j].b.get();
             }
+        k::HqHead hq_head{};
+        if (hq) {
+            for (int j = 0; j < 3; ++j) {
+                hq_head.w[j] = W.hq_mlp_[j].w.get();
+                hq_head.b[j] = W.hq_mlp_[j].b.get();
+            }
+            hq_head.hyper_hq = hyper_hq_.get();
+        }
         k::output_heads(t2i_part_.get(), lin({}, 128, W.final_o_, cur, nullptr, 0), W.final_o_t_.get(), normed(nullptr, W.ln_final_),
-                        hw, hyper_.get(), iou_out, P, TOK, s);
+                        hw, hyper_.get(), iou_out, P, TOK, s, hq ? &hq_head : nullptr);
         // upscaling ConvT(256->64) -> LN2d -> GELU -> ConvT(64->32) -> GELU and the product with the hyper vectors
         k::upscale_logits(keys_h_.get(), W.up1_.w.get(), W.up1_.b.get(), W.up_ln_.w.get(), W.up_ln_.b.get(), kLnEps,
-                          W.up2_.w.get(), W.up2_.b.get(), hyper_.get(), logits_out, P, s);
+                          W.up2_.w.get(), W.up2_.b.get(), hyper_.get(), logits_out, P, s, hq ? hq_u_.get() : nullptr);
+        if (hq) {
+            // SAM-HQ: the 3x3 path on the up-scaled embedding + the image's HQ features (behind the embedding in the handle's
+            // buffer), times hyper_hq, added to all four planes: everything downstream sees masks_sam + masks_hq
+            float const* feat[k::kDecoderMaxPrompts];
+            for (int i = 0; i < P; ++i) feat[i] = emb[i] + kEmbeddingFloats;
+            k::hq_mask_path(hq_u_.get(), W.hq_mask_weights(), kLnEps, hq_mid_.get(), feat, hyper_hq_.get(), logits_out, P, s);
+        }
     };
-    clock_.timed(ST_DECODER, 3.62e9 * P, body);
+    clock_.timed(ST_DECODER, (hq ? 3.62e9 + 4.83e9 : 3.62e9) * P, body);
     HIP_CHECK(hipGetLastError());
 }
 
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }
 
-std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout(int tokens, bool with_mask_h) {
+std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout(int tokens, bool with_mask_h, bool with_hq) {
     DLIMG_ASSERT(k::decoder_tokens_supported(tokens));
     const size_t T = (size_t)tokens;
     std::vector<std::pair<const char*, size_t>> parts = {
@@ -701,17 +807,25 @@ std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout(int t
         {"t2i_out", T * 256}, {"mlp_hidden", T * 2048}, {"queries", T * 256}, {"i2t_k", T * 128}, {"i2t_v", T * 128},
         {"final_partials", k::token_to_image_scratch_floats(1, tokens)}, {"hyper", 4 * 32}, {"iou", 4}, {"keys_head", 4096}};
     if (with_mask_h) parts.push_back({"mask_h", (size_t)kTokens * k::kMaskHidden});
+    if (with_hq) parts.push_back({"hyper_hq", 32});
     return parts;
 }
 
 void SamModel::decoder_state(float* out) const { decoder_state(out, kDecTokens); }
 
-void SamModel::decoder_state(float* out, int tokens, bool with_mask_h) const {
-    float const* src[] = {tokens_.get(), sq_.get(), sk_.get(), sv_.get(), tsa_.get(), tt2i_.get(), tmlp_.get(), queries_.get(),
-                          tk_.get(), tv_.get(), t2i_part_.get(), hyper_.get(), iou_.get(), keys_.get(), mask_h_.get()};
-    if (with_mask_h) DLIMG_ASSERT(mask_h_.capacity() >= (size_t)kTokens * k::kMaskHidden);
+void SamModel::decoder_state(float* out, int tokens, bool with_mask_h, bool with_hq) const {
+    std::vector<float const*> src = {tokens_.get(), sq_.get(), sk_.get(), sv_.get(), tsa_.get(), tt2i_.get(), tmlp_.get(), queries_.get(),
+                                     tk_.get(), tv_.get(), t2i_part_.get(), hyper_.get(), iou_.get(), keys_.get()};
+    if (with_mask_h) {
+        DLIMG_ASSERT(mask_h_.capacity() >= (size_t)kTokens * k::kMaskHidden);
+        src.push_back(mask_h_.get());
+    }
+    if (with_hq) {
+        DLIMG_ASSERT(hyper_hq_.capacity() >= 32);
+        src.push_back(hyper_hq_.get());
+    }
     size_t off = 0, i = 0;
-    for (auto const& part : decoder_state_layout(tokens, with_mask_h)) {
+    for (auto const& part : decoder_state_layout(tokens, with_mask_h, with_hq)) {
         HIP_CHECK(hipMemcpy(out + off, src[i++], part.second * sizeof(float), hipMemcpyDeviceToHost));
         off += part.second;
     }

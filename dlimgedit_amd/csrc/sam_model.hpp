@@ -107,8 +107,29 @@ struct SamWeights {
     LinearH up1_, up2_;                   // transposed-conv weights as GEMM operands (sub-pixel-major rows)
     NormW up_ln_;
     std::array<std::array<LinearF, 3>, 5> heads_;   // 4 hyper MLPs + IoU head
-
+    // SAM-HQ's decoder add-on (dec.hq.*), optional in the file, all or nothing: without it the model is plain SAM
+    bool has_hq_ = false;
+    bool has_hq() const { return has_hq_; }
+    DeviceBuffer<float> hq_token_;                  // [256]
+    std::array<LinearF, 3> hq_mlp_;                 // 256 -> 256 -> 256 -> 32
+    LinearH hq_vit1_, hq_vit2_, hq_emb1_, hq_emb2_; // transposed convolutions as GEMM operands, like up1_ / up2_
+    NormW hq_vit_ln_, hq_emb_ln_, hq_mask_ln_;
+    DeviceBuffer<half_t> hq_conv1_w_, hq_conv2_w_;  // 3x3 convolutions, [9][64][32] and [9][32][64]: tap, output, input channel
+    DeviceBuffer<float> hq_conv1_b_, hq_conv2_b_;
+    k::HqMaskWeights hq_mask_weights() const {
+        k::HqMaskWeights w;
+        w.conv1_w = hq_conv1_w_.get(); w.conv1_b = hq_conv1_b_.get(); w.ln_w = hq_mask_ln_.w.get(); w.ln_b = hq_mask_ln_.b.get();
+        w.conv2_w = hq_conv2_w_.get(); w.conv2_b = hq_conv2_b_.get();
+        return w;
+    }
 };
+
+// What a Segmentation handle keeps per image: the embedding [4096][256] fp32 and, behind it in the same buffer when the
+// model is a SAM-HQ one, the image's HQ features [256][256][32] fp32.
+constexpr size_t kEmbeddingFloats = (size_t)kTokens * kEmbedDim;
+constexpr size_t kHqFeatureFloats = (size_t)kLowRes * kLowRes * 32;
+constexpr size_t handle_floats(bool hq) { return kEmbeddingFloats + (hq ? kHqFeatureFloats : 0); }
+constexpr int kHqMaxPoints = 9;      // a SAM-HQ prompt: the HQ token takes the 15th token row
 
 // One execution lane.  What is the lane's own here: the encoder, the decoder, image intake (staging ring, resize tables,
 // staged resizes) and the pass flags with DeferredPass.  The rest are components with contracts of their own, which the
@@ -156,8 +177,11 @@ class SamModel {
     // the others are resampled on the way by the fused resize: one launch per stage for all of them.
     void preprocess_device_images(dlimg_ImageView const* views, int const* resized_wh, int batch);
     // Runs the encoder on `batch` uploaded images; embeddings [batch][4096][256] fp32 in embeddings() and, where
-    // emb_dst[i] is given, in that device buffer too (batch 1: written there directly).
+    // emb_dst[i] is given, in that device buffer too (batch 1: written there directly).  A SAM-HQ model also leaves every
+    // image's HQ features: behind the embedding in emb_dst[i] (a buffer of handle_floats(true) floats), else in a
+    // workspace of the lane.
     void encode(int batch, float* const* emb_dst = nullptr);
+    bool has_hq() const { return weights_->has_hq_; }                          // no mutex needed
     float const* embeddings() const { return emb_.get(); }
 
     // Decoder for `count` prompts of `points` points each (2 .. 10: every prompt of a call has the same number, 5 + points
@@ -166,8 +190,13 @@ class SamModel {
     // mask_input (optional, [count]): every prompt's mask input, SAM's click-to-refine loop -- device logits some decode left
     // (this lane's own logits() / iou() are fine: they are read before this decode writes them, in stream order).  All
     // prompts of a call have one or none; needs a model with the mask branch (has_mask_branch()).
+    // handles: emb[i] are the buffers of Segmentation handles (handle_floats()).  A SAM-HQ model decodes nothing else: the
+    // HQ features of the image lie behind the embedding there, and a bare embedding has none.  It appends the HQ token's
+    // pseudo-point to every prompt itself (5 + points + 1 token rows), so its prompts hold at most kHqMaxPoints points.
     void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2,
-                k::MaskSource const* mask_input = nullptr);
+                k::MaskSource const* mask_input = nullptr, bool handles = false);
+    // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
+    std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
     float const* logits() const { return logits_.get(); }
     // Diagnostic: the token-side workspaces as the last decode of ONE prompt left them (after synchronize()), one after
@@ -176,8 +205,9 @@ class SamModel {
     void decoder_state(float* out) const;
     // The same for a prompt of `tokens` token rows (7 .. 15: 5 + its points); with_mask_h adds "mask_h" [4096][16], the mask
     // branch in front of its last convolution as the last MASKED decode of one prompt left it.
-    static std::vector<std::pair<const char*, size_t>> decoder_state_layout(int tokens, bool with_mask_h = false);
-    void decoder_state(float* out, int tokens, bool with_mask_h = false) const;
+    // with_hq (SAM-HQ models, whose one-point prompt has 8 token rows, the HQ token last): adds "hyper_hq" [32] at the end.
+    static std::vector<std::pair<const char*, size_t>> decoder_state_layout(int tokens, bool with_mask_h = false, bool with_hq = false);
+    void decoder_state(float* out, int tokens, bool with_mask_h = false, bool with_hq = false) const;
     float const* iou() const { return iou_.get(); }
 
     // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):
@@ -237,6 +267,7 @@ class SamModel {
     void reserve_decoder(int count);
     void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points,
                       k::MaskSource const* mask_input);
+    void hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
 
     int device_ = 0;
@@ -264,6 +295,10 @@ class SamModel {
     uint8_t* stage_rows(uint8_t const* pixels, size_t row_bytes, int rows, int stride, hipEvent_t* copied);
     DeviceBuffer<half_t> patches_, xn_, xlo_, qkv_, att_, hid_;
     DeviceBuffer<float> x_, xstat_, neck_f32_, emb_;
+    // SAM-HQ models: first transposed convolution fp32 / after its LayerNorm f16, the two branches' second convolutions,
+    // the f16 copy of the embedding, and the features of passes that have no handle to write them to
+    DeviceBuffer<float> hq_a_, hq_vit_, hq_embf_, hq_feat_;
+    DeviceBuffer<half_t> hq_h_, emb_h_;
     // The residual stream as an f16 pair (xn_ = hi, which is also the consumers' A operand; xlo_ = lo) instead of fp32 x_ +
     // its f16 copy xn_: 8 instead of 10 bytes per element through every stream writer (kernels.hpp, GemmArgs::out_l).
     // Needs the ping-pong epilogue for every stream writer: folded LayerNorms, several lanes (the shared-GPU tile choice) and
@@ -308,6 +343,8 @@ class SamModel {
     // ---- decoder workspace (sized for dec_count_ prompts)
     int dec_count_ = 0;
     DeviceBuffer<float> keys_, logits_, iou_, hyper_;
+    DeviceBuffer<float> hyper_hq_;       // SAM-HQ models: [launch's prompts][32]
+    DeviceBuffer<half_t> hq_u_, hq_mid_; // ... the up-scaled embedding [.][256][256][32] and the 3x3 path's intermediate [.][256][256][64]
     DeviceBuffer<float> mask_h_;         // [launch's prompts][4096][16]: the mask branch in front of its last convolution (first masked decode)
     DeviceBuffer<half_t> keys_h_, kqv_h_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;

@@ -319,6 +319,51 @@ SamWeights::SamWeights(std::string const& weight_path, int device_index) : devic
         ld.linear_f(p + ".1", 256, 256, heads_[m][1]);
         ld.linear_f(p + ".2", last, 256, heads_[m][2]);
     }
+    {   // SAM-HQ's decoder add-on is optional, all or nothing, and independent of the mask branch
+        static const char* const names[] = {
+            "dec.hq.token", "dec.hq.mlp.0.w", "dec.hq.mlp.0.b", "dec.hq.mlp.1.w", "dec.hq.mlp.1.b", "dec.hq.mlp.2.w", "dec.hq.mlp.2.b",
+            "dec.hq.vit.conv1.w", "dec.hq.vit.conv1.b", "dec.hq.vit.ln.w", "dec.hq.vit.ln.b", "dec.hq.vit.conv2.w", "dec.hq.vit.conv2.b",
+            "dec.hq.emb.conv1.w", "dec.hq.emb.conv1.b", "dec.hq.emb.ln.w", "dec.hq.emb.ln.b", "dec.hq.emb.conv2.w", "dec.hq.emb.conv2.b",
+            "dec.hq.mask.conv1.w", "dec.hq.mask.conv1.b", "dec.hq.mask.ln.w", "dec.hq.mask.ln.b", "dec.hq.mask.conv2.w", "dec.hq.mask.conv2.b"};
+        int present = 0;
+        const char* absent = nullptr;
+        for (const char* n : names) {
+            if (file.has(n)) ++present;
+            else absent = n;
+        }
+        if (present != 0 && absent)
+            throw Exception("'" + file.path() + "': the SAM-HQ group dec.hq.* is all or nothing: " + std::to_string(present) +
+                            " of its 25 tensors are there, '" + absent + "' is not");
+        has_hq_ = present != 0;
+        if (has_hq_ && geom_.global_attn_indexes.empty())
+            throw Exception("'" + file.path() + "': the SAM-HQ group needs an encoder with a global-attention block (its early feature)");
+        if (has_hq_) {
+            ld.f32("dec.hq.token", {256}, hq_token_);
+            ld.linear_f("dec.hq.mlp.0", 256, 256, hq_mlp_[0]);
+            ld.linear_f("dec.hq.mlp.1", 256, 256, hq_mlp_[1]);
+            ld.linear_f("dec.hq.mlp.2", 32, 256, hq_mlp_[2]);
+            ld.conv_transpose_h("dec.hq.vit.conv1", D, 256, hq_vit1_);
+            ld.norm("dec.hq.vit.ln", 256, hq_vit_ln_);
+            ld.conv_transpose_h("dec.hq.vit.conv2", 256, 32, hq_vit2_);
+            ld.conv_transpose_h("dec.hq.emb.conv1", 256, 64, hq_emb1_);
+            ld.norm("dec.hq.emb.ln", 64, hq_emb_ln_);
+            ld.conv_transpose_h("dec.hq.emb.conv2", 64, 32, hq_emb2_);
+            // 3x3 convolutions [co][ci][ky][kx] -> [ky * 3 + kx][co][ci], the slices the implicit GEMM of decoder_hq.hip walks
+            auto conv3x3 = [&](std::string const& prefix, int co_n, int ci_n, DeviceBuffer<half_t>& w16, DeviceBuffer<float>& b) {
+                HostTensor const& w = file.get(prefix + ".w", {co_n, ci_n, 3, 3});
+                std::vector<float> g(w.numel());
+                for (int co = 0; co < co_n; ++co)
+                    for (int ci = 0; ci < ci_n; ++ci)
+                        for (int t = 0; t < 9; ++t)
+                            g[((size_t)t * co_n + co) * ci_n + ci] = w.data[((size_t)co * ci_n + ci) * 9 + t];
+                ld.f16_host(g.data(), g.size(), w16, prefix + ".w");
+                ld.f32(prefix + ".b", {co_n}, b);
+            };
+            conv3x3("dec.hq.mask.conv1", 64, 32, hq_conv1_w_, hq_conv1_b_);
+            ld.norm("dec.hq.mask.ln", 64, hq_mask_ln_);
+            conv3x3("dec.hq.mask.conv2", 32, 64, hq_conv2_w_, hq_conv2_b_);
+        }
+    }
     HIP_CHECK(hipStreamSynchronize(stream_));
     HIP_CHECK(hipStreamDestroy(stream_));
 }

@@ -131,6 +131,12 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
         StagedPrompts plan = plan_staged_prompts(has_handle, points != nullptr, regions, mask_branch);
         b.prompts = std::move(plan.prompts);
         b.stages = std::move(plan.stages);
+        // a SAM-HQ model takes one point less (its HQ token is a token row): refused here, before any prompt of the call is launched
+        if (any)
+            for (PromptSpec const& p : b.prompts) {
+                const std::string why = any->environment().lane(any->replica(), 0).hq_refusal(p.points());
+                if (!why.empty()) throw Exception(why);
+            }
     }
     size_t total = 0;
     for (PromptSpec const& p : b.prompts) {
@@ -173,7 +179,7 @@ k::MaskSource run_early_stages(SamModel& model, BatchPrompts const& b, int j, fl
         PromptSpec part = spec;
         part.clicks = st.stage_clicks[s];
         pack_stage(rs, spec, st, part.clicks, points, regions, coords, labels);
-        model.decode(&emb, coords, labels, 1, part.points(), s ? &src : nullptr);
+        model.decode(&emb, coords, labels, 1, part.points(), s ? &src : nullptr, /*handles*/ true);
         // single_mask_job's rule: the best of planes 1..3 for a two-point stage, plane 0 otherwise
         src = k::MaskSource{model.logits(), part.points() > 2 ? nullptr : model.iou()};
     }
@@ -263,7 +269,7 @@ float* SegmentationImpl::embedding_storage(int replica) {
     replica_ = replica;
     if (!embedding_) {
         pool_ = env_.embedding_pool(replica);
-        embedding_ = pool_->take();
+        embedding_ = pool_->take(handle_floats(env_.lane(replica, 0).has_hq()));
     }
     return embedding_;
 }
@@ -563,7 +569,7 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
             float const* emb = embedding_;
             {
                 roctx::Range rd("dlimg.decode");
-                model_.decode(&emb, coords, labels, 1);
+                model_.decode(&emb, coords, labels, 1, 2, nullptr, /*handles*/ true);
             }
             if (is_single_mask) {
                 // single-mask decoder: best of the four by SamOnnxModel.select_masks, chosen on the device
@@ -647,9 +653,9 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
                 std::lock_guard<std::mutex> lock(model.mutex());
                 if (work.staged) {
                     const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
-                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src);
+                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
                 } else {
-                    model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                    model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
                 }
                 for (int j = 0; j < n; ++j) {
                     const int i = prompts[part.prompts[j]].head;
@@ -742,9 +748,9 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
                 std::lock_guard<std::mutex> lock(model.mutex());
                 if (work.staged) {
                     const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
-                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src);
+                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
                 } else {
-                    model.decode(emb.data(), cc.data(), ll.data(), n, npts);
+                    model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
                 }
                 for (int j = 0; j < n; ++j) {
                     const int i = prompts[part.prompts[j]].head;

@@ -398,6 +398,9 @@ DLIMG_API int dlimg_amd_test_decode(dlimg_Environment env, int n_emb, float cons
         // the product's decoder on a lane of replica 0, exactly as dlimg_amd_get_logits runs it: one decode() call for all
         // `count` prompts (chunks of 16 and all)
         SamModel& m = impl(env).next_lane(0);
+        if (m.has_hq())
+            throw Exception("test_decode: a SAM-HQ model (dec.hq.* in the model file) does not decode bare embeddings: there is no "
+                            "handle to take the image's HQ features from");
         std::lock_guard<std::mutex> lock(m.mutex());
         HIP_CHECK(hipSetDevice(m.device()));
         const size_t per = (size_t)kTokens * kEmbedDim;
@@ -427,6 +430,9 @@ DLIMG_API int dlimg_amd_test_decode_prompts(dlimg_Environment env, int n_emb, fl
         const bool masked = mask_planes != nullptr;
         if (out_state && count != 1) throw Exception("test_decode_prompts: the state is that of a one-prompt call");
         SamModel& m = impl(env).next_lane(0);
+        if (m.has_hq())
+            throw Exception("test_decode_prompts: a SAM-HQ model (dec.hq.* in the model file) does not decode bare embeddings: there "
+                            "is no handle to take the image's HQ features from");
         if (masked && !m.has_mask_branch())
             throw Exception("test_decode_prompts: a mask input needs the prompt encoder's mask branch: the model file has no pe.mask.* tensors");
         if (masked && count > k::decoder_max_prompts(tokens))

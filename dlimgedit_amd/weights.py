@@ -78,8 +78,44 @@ def has_mask_branch(params) -> bool:
     return bool(present)
 
 
-def param_specs(cfg: SamConfig, mask_branch: bool = False) -> List[Spec]:
-    """The tensors of one model.  mask_branch: with the optional mask branch (mask_branch_specs), listed behind pe.no_mask."""
+def hq_specs(cfg: SamConfig) -> List[Spec]:
+    """SAM-HQ's decoder add-on (dec.hq.*), optional in a model file, all or nothing and independent of the mask branch: the HQ
+    output token and its hyper-network MLP, the two transposed convolutions that compress the early ViT feature (the output of
+    the first global-attention block) and the two that encode the embedding, and the two 3x3 convolutions on the up-scaled
+    embedding.  The "conv" in the names makes f16_operand() range-check the weights: all of them become f16 MFMA operands."""
+    d, c1, c2 = cfg.embed_dim, DEC_DIM // 4, DEC_DIM // 8
+    s: List[Spec] = [("dec.hq.token", (DEC_DIM,), ("u", 0.5))]
+    for j, (o, i) in enumerate([(DEC_DIM, DEC_DIM), (DEC_DIM, DEC_DIM), (c2, DEC_DIM)]):
+        s += [(f"dec.hq.mlp.{j}.w", (o, i), ("lin", i)), (f"dec.hq.mlp.{j}.b", (o,), ("u", 0.05))]
+    s += [("dec.hq.vit.conv1.w", (d, DEC_DIM, 2, 2), ("lin", d)), ("dec.hq.vit.conv1.b", (DEC_DIM,), ("u", 0.05))]
+    s += _ln_specs("dec.hq.vit.ln", DEC_DIM)
+    s += [("dec.hq.vit.conv2.w", (DEC_DIM, c2, 2, 2), ("lin", DEC_DIM)), ("dec.hq.vit.conv2.b", (c2,), ("u", 0.05))]
+    s += [("dec.hq.emb.conv1.w", (DEC_DIM, c1, 2, 2), ("lin", DEC_DIM)), ("dec.hq.emb.conv1.b", (c1,), ("u", 0.05))]
+    s += _ln_specs("dec.hq.emb.ln", c1)
+    s += [("dec.hq.emb.conv2.w", (c1, c2, 2, 2), ("lin", c1)), ("dec.hq.emb.conv2.b", (c2,), ("u", 0.05))]
+    s += [("dec.hq.mask.conv1.w", (c1, c2, 3, 3), ("lin", c2 * 9)), ("dec.hq.mask.conv1.b", (c1,), ("u", 0.05))]
+    s += _ln_specs("dec.hq.mask.ln", c1)
+    s += [("dec.hq.mask.conv2.w", (c2, c1, 3, 3), ("lin", c1 * 9)), ("dec.hq.mask.conv2.b", (c2,), ("u", 0.05))]
+    return s
+
+
+def has_hq(params) -> bool:
+    """True when `params` holds the whole dec.hq.* group, False when it holds none of it; a partial set is refused."""
+    present = [n for n in params if n.startswith("dec.hq.")]
+    if not present:
+        return False
+    d = int(np.asarray(params["dec.hq.vit.conv1.w"]).shape[0]) if "dec.hq.vit.conv1.w" in params else DEC_DIM
+    names = [n for n, _, _ in hq_specs(SamConfig("hq", d, 1, 1, (0,)))]
+    missing = [n for n in names if n not in params]
+    if missing:
+        raise ValueError(f"partial SAM-HQ group: dec.hq.* is all or nothing, {len(names) - len(missing)} of {len(names)} tensors "
+                         f"given, e.g. {missing[0]} is missing")
+    return True
+
+
+def param_specs(cfg: SamConfig, mask_branch: bool = False, hq: bool = False) -> List[Spec]:
+    """The tensors of one model.  mask_branch: with the optional mask branch (mask_branch_specs), listed behind pe.no_mask.
+    hq: with SAM-HQ's decoder add-on (hq_specs), listed behind the decoder's entries."""
     d, hd, g, w = cfg.embed_dim, cfg.head_dim, cfg.grid, cfg.window_size
     k_patch = 3 * cfg.patch_size ** 2
     s: List[Spec] = [
@@ -140,6 +176,8 @@ def param_specs(cfg: SamConfig, mask_branch: bool = False) -> List[Spec]:
     dims = [(IOU_HIDDEN, DEC_DIM), (IOU_HIDDEN, IOU_HIDDEN), (NUM_MASK_TOKENS, IOU_HIDDEN)]
     for j, (o, i) in enumerate(dims):
         s += [(f"dec.iou.{j}.w", (o, i), ("lin", i)), (f"dec.iou.{j}.b", (o,), ("u", 0.05))]
+    if hq:
+        s += hq_specs(cfg)
     return s
 
 
@@ -168,10 +206,11 @@ def counter_uniform(seed: int, name: str, n: int) -> np.ndarray:
     return (u24 * (2.0 / 16777216.0) - 1.0).astype(np.float32)
 
 
-def synthetic_weights(cfg: SamConfig, seed: int = 0, mask_branch: bool = False) -> Dict[str, np.ndarray]:
-    """Seeded weights; every tensor is a function of (seed, its name) alone, so the mask branch changes no other tensor."""
+def synthetic_weights(cfg: SamConfig, seed: int = 0, mask_branch: bool = False, hq: bool = False) -> Dict[str, np.ndarray]:
+    """Seeded weights; every tensor is a function of (seed, its name) alone, so the mask branch and the SAM-HQ group change
+    no other tensor."""
     out: Dict[str, np.ndarray] = {}
-    for name, shape, init in param_specs(cfg, mask_branch):
+    for name, shape, init in param_specs(cfg, mask_branch, hq):
         n = int(np.prod(shape))
         u = counter_uniform(seed, name, n)
         if init[0] == "lin":
@@ -259,9 +298,10 @@ def check_f16_range(params: Dict[str, np.ndarray], allow_out_of_range: bool = Fa
 
 
 def save_weights(path, cfg: SamConfig, params: Dict[str, np.ndarray], allow_out_of_range: bool = False) -> Path:
-    """Write `params` (must cover param_specs(cfg) exactly; the mask branch as a whole or not at all) to `path` in DLW v1."""
+    """Write `params` (must cover param_specs(cfg) exactly; the mask branch and the SAM-HQ group each as a whole or not at
+    all) to `path` in DLW v1."""
     path = Path(path)
-    specs = param_specs(cfg, has_mask_branch(params))
+    specs = param_specs(cfg, has_mask_branch(params), has_hq(params))
     check_f16_range({s[0]: params[s[0]] for s in specs if s[0] in params}, allow_out_of_range)
     names = [s[0] for s in specs]
     missing = [n for n in names if n not in params]
@@ -319,9 +359,10 @@ def load_weights(path) -> Tuple[Dict[str, int], Dict[str, np.ndarray]]:
     return meta, out
 
 
-def write_synthetic_model_dir(model_dir, cfg: SamConfig, seed: int = 0, mask_branch: bool = False) -> Dict[str, np.ndarray]:
+def write_synthetic_model_dir(model_dir, cfg: SamConfig, seed: int = 0, mask_branch: bool = False,
+                              hq: bool = False) -> Dict[str, np.ndarray]:
     """Create `<model_dir>/segmentation/sam_<variant>.dlw` with seeded weights; returns them."""
-    params = synthetic_weights(cfg, seed, mask_branch)
+    params = synthetic_weights(cfg, seed, mask_branch, hq)
     save_weights(Path(model_dir) / "segmentation" / weight_file_name(cfg), cfg, params)
     return params
 
@@ -411,11 +452,57 @@ def _mask_from(sd, names, a) -> Dict[str, np.ndarray]:
     return p
 
 
+_OUR_HQ = ("vit.conv1", "vit.ln", "vit.conv2", "emb.conv1", "emb.ln", "emb.conv2", "mask.conv1", "mask.ln", "mask.conv2")
+_HF_HQ = ("compress_vit_conv1", "compress_vit_norm", "compress_vit_conv2", "encoder_conv1", "encoder_norm", "encoder_conv2",
+          "mask_conv1", "mask_norm", "mask_conv2")
+_META_HQ = ("compress_vit_feat.0", "compress_vit_feat.1", "compress_vit_feat.3", "embedding_encoder.0", "embedding_encoder.1",
+            "embedding_encoder.3", "embedding_maskfeature.0", "embedding_maskfeature.1", "embedding_maskfeature.3")
+
+
+def _hq_name_map(token: str, mlp, layers) -> List[Tuple[str, str]]:
+    """(our name, their key) of the SAM-HQ group; the token is [256] here and [1, 256] there."""
+    m = [("dec.hq.token", f"mask_decoder.{token}.weight")]
+    for j, h in enumerate(mlp):
+        m += [(f"dec.hq.mlp.{j}.{a}", f"mask_decoder.{h}.{b}") for a, b in (("w", "weight"), ("b", "bias"))]
+    m += [(f"dec.hq.{o}.{a}", f"mask_decoder.{t}.{b}") for o, t in zip(_OUR_HQ, layers) for a, b in (("w", "weight"), ("b", "bias"))]
+    return m
+
+
+def hq_hf_name_map() -> List[Tuple[str, str]]:
+    """The SAM-HQ group under Hugging Face `SamHQModel` keys."""
+    return _hq_name_map("hq_token", [f"hq_mask_mlp.{h}" for h in ("proj_in", "layers.0", "proj_out")], _HF_HQ)
+
+
+def hq_meta_name_map() -> List[Tuple[str, str]]:
+    """The SAM-HQ group under the keys of the original sam-hq checkpoints."""
+    return _hq_name_map("hf_token", [f"hf_mlp.layers.{j}" for j in range(3)], _META_HQ)
+
+
+def _hq_to(params, names) -> Dict[str, np.ndarray]:
+    if not has_hq(params):
+        return {}
+    sd = {theirs: params[ours] for ours, theirs in names}
+    key = dict(names)["dec.hq.token"]
+    sd[key] = sd[key].reshape(1, -1)
+    return sd
+
+
+def _hq_from(sd, names, a) -> Dict[str, np.ndarray]:
+    """The group when the state dict holds all of it; a part of it alone (a stripped checkpoint) is ignored."""
+    if not all(theirs in sd for _, theirs in names):
+        return {}
+    p = {ours: a(sd[theirs]) for ours, theirs in names}
+    p["dec.hq.token"] = p["dec.hq.token"].reshape(-1)
+    return p
+
+
 def to_hf_state_dict(cfg: SamConfig, params: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
-    """Our tensors laid out under HF `SamModel` keys (for cross-checking the oracle); the mask branch when `params` has it."""
+    """Our tensors laid out under HF `SamModel` keys (for cross-checking the oracle); the mask branch when `params` has it,
+    and the SAM-HQ group under `SamHQModel`'s keys when it has that."""
     d, g = cfg.embed_dim, cfg.grid
     sd = {hf: params[ours] for ours, hf in hf_name_map(cfg)}
     sd.update(_mask_to(params, _mask_name_map("prompt_encoder.mask_embed", _HF_MASK)))
+    sd.update(_hq_to(params, hq_hf_name_map()))
     sd["vision_encoder.patch_embed.projection.weight"] = params["enc.patch.w"].reshape(d, 3, cfg.patch_size, cfg.patch_size)
     sd["vision_encoder.pos_embed"] = params["enc.pos"].reshape(1, g, g, d)
     sd["vision_encoder.neck.conv1.weight"] = params["enc.neck.conv1.w"].reshape(cfg.out_chans, d, 1, 1)
@@ -444,7 +531,8 @@ def from_hf_state_dict(cfg: SamConfig, sd) -> Dict[str, np.ndarray]:
     for k in ("pe.not_a_point", "pe.no_mask", "dec.iou_token"):
         p[k] = p[k].reshape(-1)
     p.update(_mask_from(sd, _mask_name_map("prompt_encoder.mask_embed", _HF_MASK), a))
-    want = {n: s for n, s, _ in param_specs(cfg, has_mask_branch(p))}
+    p.update(_hq_from(sd, hq_hf_name_map(), a))
+    want = {n: s for n, s, _ in param_specs(cfg, has_mask_branch(p), has_hq(p))}
     for n, s in want.items():
         if tuple(p[n].shape) != tuple(s):
             raise ValueError(f"{n}: checkpoint shape {p[n].shape} != {s}")
@@ -510,6 +598,7 @@ def to_meta_state_dict(cfg: SamConfig, params: Dict[str, np.ndarray]) -> Dict[st
     d, g = cfg.embed_dim, cfg.grid
     sd = {theirs: params[ours] for ours, theirs in meta_name_map(cfg)}
     sd.update(_mask_to(params, _mask_name_map("prompt_encoder.mask_downscaling", _META_MASK)))
+    sd.update(_hq_to(params, hq_meta_name_map()))
     sd["image_encoder.patch_embed.proj.weight"] = params["enc.patch.w"].reshape(d, 3, cfg.patch_size, cfg.patch_size)
     sd["image_encoder.pos_embed"] = params["enc.pos"].reshape(1, g, g, d)
     sd["image_encoder.neck.0.weight"] = params["enc.neck.conv1.w"].reshape(cfg.out_chans, d, 1, 1)
@@ -539,7 +628,8 @@ def from_meta_state_dict(cfg: SamConfig, sd) -> Dict[str, np.ndarray]:
     p["pe.no_mask"] = a(sd["prompt_encoder.no_mask_embed.weight"]).reshape(-1)
     p["dec.iou_token"] = a(sd["mask_decoder.iou_token.weight"]).reshape(-1)
     p.update(_mask_from(sd, _mask_name_map("prompt_encoder.mask_downscaling", _META_MASK), a))
-    for n, s, _ in param_specs(cfg, has_mask_branch(p)):
+    p.update(_hq_from(sd, hq_meta_name_map(), a))
+    for n, s, _ in param_specs(cfg, has_mask_branch(p), has_hq(p)):
         if tuple(p[n].shape) != tuple(s):
             raise ValueError(f"{n}: checkpoint shape {p[n].shape} != {s} (wrong variant?)")
     return p

@@ -33,13 +33,16 @@ DLIMG_API int dlimg_amd_model_geometry(dlimg_Environment env, int* out);
  * (reference: src/segmentation.hpp:61). */
 DLIMG_API int dlimg_amd_get_embedding(dlimg_Segmentation seg, float* out);
 /* Runs prompt encoder + mask decoder for one prompt and returns the decoder's raw outputs:
- * out_logits [4][256][256] (low_res_masks), out_iou [4] (iou_predictions). */
+ * out_logits [4][256][256] (low_res_masks), out_iou [4] (iou_predictions).  A SAM-HQ model (a model file with the dec.hq.*
+ * group): the planes are masks_sam + masks_hq, the HQ plane added to each of the four. */
 DLIMG_API int dlimg_amd_get_logits(dlimg_Segmentation seg, int const* point, int const* region, float* out_logits,
                                    float* out_iou);
 
 /* Diagnostic: decodes one point prompt and copies out the decoder's token-side workspaces as that decode left them
  * (tokens, projections, attention outputs, MLP hidden layer, final partials, hyper vectors, IoU, the first 4096 keys
- * values), one after the other; out_layout receives "name:floats,name:floats,...".  out == NULL: layout only. */
+ * values), one after the other; out_layout receives "name:floats,name:floats,...".  out == NULL: layout only.
+ * A SAM-HQ model: the prompt has 8 token rows (the HQ token last) and the layout ends with "hyper_hq" [32] and the
+ * image's "hq_features" [256][256][32]. */
 DLIMG_API int dlimg_amd_decoder_state(dlimg_Segmentation seg, int const* point, float* out, int capacity, char* out_layout,
                                       int layout_capacity);
 
