@@ -1084,26 +1084,25 @@ static_assert(k::kDecoderMaxTokens == 15, "DLIMG_FOR_TOKENS names every supporte
 
 namespace k {
 
-namespace {
-// mask: null for the unmasked launch; else the per-prompt h rows and the branch's last convolution
-struct StartMask { const float* const* h; const float* proj_w; const float* proj_b; };
-void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* no_mask, const StartMask* mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
-                          const float* hq_token) {
+void decoder_start(const DecoderStartInputs& in, int P, int T, hipStream_t s) {
+    const DecoderPrompts& prompts = in.prompts;
+    const TokenLinear* first = in.first;
+    const int n_first = in.n_first;
+    const bool masked = in.mask_h || in.mask;
     if (P <= 0) return;
     if (!decoder_tokens_supported(T)) throw_error("decoder_start: 7 to 15 tokens per prompt");
-    if (hq_token) {
+    if (in.hq_token) {
         if (T < 8) throw_error("decoder_start: a SAM-HQ prompt has at least 8 token rows (the HQ token travels as the last one)");
         for (int i = 0; i < P && i < decoder_max_prompts(T); ++i)
             if (prompts.labels[(size_t)i * (T - 5) + (T - 6)] != kDecoderHqLabel)
                 throw_error("decoder_start: the last point of a SAM-HQ prompt is the HQ token's pseudo-point");
     }
     if (P > decoder_max_prompts(T) || n_first < 0 || n_first > TL_MAX_OPS) throw_error("decoder_start: too many prompts or layers");
-    if (mask) {
-        if (!mask->h || !mask->proj_w || !mask->proj_b) throw_error("decoder_start: a masked launch needs the mask branch's rows and weights");
+    if (masked) {
+        if (!in.mask_h || !in.mask || !in.mask->proj_w || !in.mask->proj_b)
+            throw_error("decoder_start: a masked launch needs the mask branch's rows and weights");
         for (int i = 0; i < P; ++i)
-            if (!mask->h[i]) throw_error("decoder_start: a launch never mixes masked and unmasked prompts");
+            if (!in.mask_h[i]) throw_error("decoder_start: a launch never mixes masked and unmasked prompts");
     }
     const size_t n4 = (size_t)NTOK_IMG * DIM / 4;
     const size_t total = n4 * P;
@@ -1114,68 +1113,42 @@ void launch_decoder_start(const DecoderPrompts& prompts, const float* gauss, con
             throw_error("decoder_start: the first linears take the plain 256-wide token rows");
         cols += first[i].N / 4;
     }
-    auto fill = [&](auto& a) {
-        using Args = std::remove_reference_t<decltype(a)>;
-        constexpr int NPTS = decltype(Args::prompts)::NPTS;
-        std::memcpy(a.prompts.coords, prompts.coords, (size_t)P * NPTS * 2 * sizeof(float));
-        std::memcpy(a.prompts.labels, prompts.labels, (size_t)P * NPTS * sizeof(float));
-        for (int i = 0; i < P; ++i) a.prompts.emb[i] = prompts.emb[i];
-        a.gauss = gauss; a.point_embed = point_embed; a.not_a_point = not_a_point; a.iou_token = iou_token; a.mask_tokens = mask_tokens;
-        a.tokens = tokens;
-        a.first.count = n_first;
-        a.first.rows = P * T;
-        for (int i = 0; i < n_first; ++i) a.first.op[i] = first[i];
-        a.lin_cols = cols > 0 ? cols : 1;
-        a.lin_blocks = cols * ((P + decoder_prompt_slice(T) - 1) / decoder_prompt_slice(T));
-        a.no_mask = no_mask; a.keys = keys; a.keys_h = keys_h; a.n4_per_prompt = n4; a.P = P;
-    };
-    DLIMG_FOR_TOKENS(T, "decoder_start",
-        static_assert(TL_PROMPT_SLICE<TOK> == decoder_prompt_slice(TOK), "fill() cuts the first linears as the kernel does");
-        if constexpr (TOK >= 8) {
-            if (hq_token && mask) {
-                WithHqToken<DecoderStartMasked<TOK>> a{};
-                fill(a);
-                for (int i = 0; i < P; ++i) a.h[i] = mask->h[i];
-                a.proj_w = mask->proj_w; a.proj_b = mask->proj_b; a.hq_token = hq_token;
-                hipLaunchKernelGGL((decoder_start_kernel<TOK, true, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
-                return;
+    // one argument block and one launch for every (TOK, MASKED, HQ): the tags pick the kernel and the fields it has
+    auto launch = [&](auto tok_tag, auto masked_tag, auto hq_tag) {
+        constexpr int TOK = decltype(tok_tag)::value;
+        constexpr bool MASKED = decltype(masked_tag)::value, HQ = decltype(hq_tag)::value;
+        static_assert(TL_PROMPT_SLICE<TOK> == decoder_prompt_slice(TOK), "the first linears are cut as the kernel cuts them");
+        if constexpr (!HQ || TOK >= 8) {             // a SAM-HQ prompt of 7 token rows was refused above: no such kernel
+            DecoderStartArgs<TOK, MASKED, HQ> a{};
+            constexpr int NPTS = StartPrompts<TOK>::NPTS;
+            std::memcpy(a.prompts.coords, prompts.coords, (size_t)P * NPTS * 2 * sizeof(float));
+            std::memcpy(a.prompts.labels, prompts.labels, (size_t)P * NPTS * sizeof(float));
+            for (int i = 0; i < P; ++i) a.prompts.emb[i] = prompts.emb[i];
+            a.gauss = in.pe.gauss; a.point_embed = in.pe.point_embed; a.not_a_point = in.pe.not_a_point;
+            a.iou_token = in.pe.iou_token; a.mask_tokens = in.pe.mask_tokens;
+            a.tokens = in.tokens;
+            a.first.count = n_first;
+            a.first.rows = P * T;
+            for (int i = 0; i < n_first; ++i) a.first.op[i] = first[i];
+            a.lin_cols = cols > 0 ? cols : 1;
+            a.lin_blocks = cols * ((P + decoder_prompt_slice(T) - 1) / decoder_prompt_slice(T));
+            a.keys = in.keys; a.keys_h = in.keys_h; a.n4_per_prompt = n4; a.P = P;
+            if constexpr (MASKED) {
+                for (int i = 0; i < P; ++i) a.h[i] = in.mask_h[i];
+                a.proj_w = in.mask->proj_w; a.proj_b = in.mask->proj_b;
+            } else {
+                a.no_mask = in.no_mask;
             }
-            if (hq_token) {
-                WithHqToken<DecoderStart<TOK>> a{};
-                fill(a);
-                a.hq_token = hq_token;
-                hipLaunchKernelGGL((decoder_start_kernel<TOK, false, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
-                return;
-            }
+            if constexpr (HQ) a.hq_token = in.hq_token;
+            hipLaunchKernelGGL((decoder_start_kernel<TOK, MASKED, HQ>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
         }
-        if (mask) {
-            DecoderStartMasked<TOK> a{};
-            fill(a);
-            for (int i = 0; i < P; ++i) a.h[i] = mask->h[i];
-            a.proj_w = mask->proj_w; a.proj_b = mask->proj_b;
-            hipLaunchKernelGGL((decoder_start_kernel<TOK, true>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
-        } else {
-            DecoderStart<TOK> a{};
-            fill(a);
-            hipLaunchKernelGGL((decoder_start_kernel<TOK, false>), dim3(P + a.lin_blocks + key_blocks), dim3(256), 0, s, a);
-        })
-}
-}  // namespace
-
-void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                   const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s, const float* hq_token) {
-    launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, no_mask, nullptr, keys,
-                         keys_h, P, T, s, hq_token);
-}
-
-void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
-                          const float* hq_token) {
-    const StartMask mask{h, branch.proj_w, branch.proj_b};
-    launch_decoder_start(prompts, gauss, point_embed, not_a_point, iou_token, mask_tokens, tokens, first, n_first, nullptr, &mask, keys,
-                         keys_h, P, T, s, hq_token);
+    };
+    constexpr std::true_type yes;
+    constexpr std::false_type no;
+    DLIMG_FOR_TOKENS(T, "decoder_start",
+        const std::integral_constant<int, TOK> tok;
+        if (in.hq_token) masked ? launch(tok, yes, yes) : launch(tok, no, yes);
+        else masked ? launch(tok, yes, no) : launch(tok, no, no);)
 }
 
 void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h, int P, hipStream_t s) {

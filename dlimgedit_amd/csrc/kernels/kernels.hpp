@@ -191,17 +191,6 @@ struct DecoderPrompts {
     float labels[kDecoderMaxPrompts * kDecoderMaxPoints];
     const float* emb[kDecoderMaxPrompts];
 };
-// First launch of a decode.  tokens [P,T,256]: iou token, 4 mask tokens, T - 5 prompt tokens (the positional part later steps
-// add); `first` (n_first <= 5 layers, K = 256, no LayerNorm / residual; their `in` is ignored) are applied to those same
-// rows in this launch.  Image side: keys = emb[p] + no_mask (fp32 + f16) for all prompts.
-// hq_token (optional, [256]): the prompts of a SAM-HQ model.  Their LAST point is a pseudo-point that carries SAM-HQ's output
-// token: its label is kDecoderHqLabel, a value no caller's label can be, and its token row (row T - 1) is hq_token and nothing
-// else -- no Fourier term, no point embedding.  The two-way transformer does not care where a row stands, so the HQ token
-// travels as one more trailing row through every token-side kernel unchanged; output_heads reads it back from row T - 1.
-constexpr float kDecoderHqLabel = -1024.0f;
-void decoder_start(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                   const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                   const float* no_mask, float* keys, half_t* keys_h, int P, int T, hipStream_t s, const float* hq_token = nullptr);
 // Mask input (SAM's click-to-refine loop: the low-res logits of the previous step through the prompt encoder's mask branch).
 // MaskBranch: the branch's tensors as the model file holds them, fp32 -- conv 2x2 / 2 w1 [4][1][2][2], b1 [4]; LayerNorm2d
 // ln1 [4]; conv 2x2 / 2 w2 [16][4][2][2], b2 [16]; LayerNorm2d ln2 [16]; 1x1 conv proj_w [256][16], proj_b [256].
@@ -218,12 +207,34 @@ struct MaskSource { const float* logits4; const float* iou4; };
 // h[p][token][16] = GELU(LN2d(conv2(GELU(LN2d(conv1(plane of src[p])))))) for P prompts (src: host array): everything of the
 // branch but its last convolution.  One launch, 16 workgroups per prompt.
 void mask_embed(const MaskSource* src, const MaskBranch& branch, float* h /*[P][4096][16]*/, int P, hipStream_t);
-// decoder_start for prompts that all have a mask input: keys = emb[p] + proj_b + h[p][token] . proj_w (fp32 + f16) instead
-// of emb[p] + no_mask, which SAM's dense embedding replaces.  h: host array of P device pointers ([4096][16] each).
-void decoder_start_masked(const DecoderPrompts& prompts, const float* gauss, const float* point_embed, const float* not_a_point,
-                          const float* iou_token, const float* mask_tokens, float* tokens, const TokenLinear* first, int n_first,
-                          const float* const* h, const MaskBranch& branch, float* keys, half_t* keys_h, int P, int T, hipStream_t s,
-                          const float* hq_token = nullptr);
+// First launch of a decode.  tokens [P,T,256]: iou token, 4 mask tokens, T - 5 prompt tokens (the positional part later steps
+// add); `first` (n_first <= 5 layers, K = 256, no LayerNorm / residual; their `in` is ignored) are applied to those same
+// rows in this launch.  Image side, for all prompts: keys = emb[p] + no_mask (fp32 + f16), or -- prompts that all have a
+// mask input: mask_h, a host array of P device pointers ([4096][16] each, mask_embed's h), and the branch -- keys = emb[p] +
+// proj_b + h[p][token] . proj_w, SAM's dense embedding in no_mask's place.
+// hq_token (optional, [256]): the prompts of a SAM-HQ model.  Their LAST point is a pseudo-point that carries SAM-HQ's output
+// token: its label is kDecoderHqLabel, a value no caller's label can be, and its token row (row T - 1) is hq_token and nothing
+// else -- no Fourier term, no point embedding.  The two-way transformer does not care where a row stands, so the HQ token
+// travels as one more trailing row through every token-side kernel unchanged; output_heads reads it back from row T - 1.
+constexpr float kDecoderHqLabel = -1024.0f;
+struct PromptEncoderWeights {       // pe.gauss, pe.point, pe.not_a_point and the decoder's output tokens
+    const float* gauss = nullptr; const float* point_embed = nullptr; const float* not_a_point = nullptr;
+    const float* iou_token = nullptr; const float* mask_tokens = nullptr;
+};
+struct DecoderStartInputs {
+    DecoderPrompts prompts{};
+    PromptEncoderWeights pe;
+    float* tokens = nullptr;
+    const TokenLinear* first = nullptr;
+    int n_first = 0;
+    float* keys = nullptr;
+    half_t* keys_h = nullptr;
+    const float* no_mask = nullptr;                 // an unmasked launch; else both of:
+    const float* const* mask_h = nullptr;
+    const MaskBranch* mask = nullptr;
+    const float* hq_token = nullptr;
+};
+void decoder_start(const DecoderStartInputs& in, int P, int T, hipStream_t s);
 // up to 5 layers over the same rows (<= 112, whole prompts of T rows) in one launch
 void token_linears(const TokenLinear* ops, int count, int rows, int T, hipStream_t);
 // self-attention among the T tokens of each prompt + its output projection `out` (K = 256) in one launch

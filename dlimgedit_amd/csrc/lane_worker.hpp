@@ -1,12 +1,17 @@
-// LaneWorker: one host thread that runs posted tasks in order (pure C++, no HIP: tests/sanitize/lane_worker_tsan.cpp builds
-// it under ThreadSanitizer).
+// LaneWorker: one host thread that runs posted tasks in order, and the hand-over of a task whose caller waits for its
+// result (pure C++, no HIP: tests/sanitize/lane_worker_tsan.cpp builds it under ThreadSanitizer).
 #pragma once
 
 #include <condition_variable>
 #include <deque>
+#include <exception>
 #include <functional>
+#include <future>
+#include <memory>
 #include <mutex>
 #include <thread>
+#include <type_traits>
+#include <vector>
 
 namespace dlimg {
 
@@ -65,5 +70,47 @@ class LaneWorker {
     bool running_ = false, stop_ = false;
     std::thread thread_;                                   // last: the members above exist before run() starts
 };
+
+// Posts `task` and returns the future of what it returns or throws.  The promise is shared with the task: it must outlive the
+// task's set_value call, which may still be returning when the caller has its answer.
+template <typename F> auto post_with_result(LaneWorker& worker, F task) {
+    using R = std::invoke_result_t<F&>;
+    auto result = std::make_shared<std::promise<R>>();
+    std::future<R> answer = result->get_future();
+    worker.post([result, task = std::move(task)]() mutable {
+        try {
+            if constexpr (std::is_void_v<R>) {
+                task();
+                result->set_value();
+            } else {
+                result->set_value(task());
+            }
+        } catch (...) {
+            result->set_exception(std::current_exception());
+        }
+    });
+    return answer;
+}
+
+// Waits for EVERY answer, in order (the tasks refer to the caller's frame, so none may be left running): on_result(i, value)
+// -- on_result(i) for void tasks -- where task i returned, on_error(i) where it or on_result threw.  Then the first exception
+// is rethrown: `first` when the caller already has one, else that of the lowest i.
+template <typename R, typename OnResult, typename OnError>
+void wait_for_all(std::vector<std::future<R>>& answers, std::exception_ptr first, OnResult on_result, OnError on_error) {
+    for (size_t i = 0; i < answers.size(); ++i) {
+        try {
+            if constexpr (std::is_void_v<R>) {
+                answers[i].get();
+                on_result(i);
+            } else {
+                on_result(i, answers[i].get());
+            }
+        } catch (...) {
+            if (!first) first = std::current_exception();
+            on_error(i);
+        }
+    }
+    if (first) std::rethrow_exception(first);
+}
 
 }  // namespace dlimg

@@ -1,6 +1,6 @@
 // The entries of a batch mask call (table slot 14, dlimg_amd_get_segmentation_masks_device) as prompts, and the prompts of
-// one GPU as decoder launches: pure host logic (no HIP, no environment), tested without a GPU (tests/prompt_plan_cases.cpp,
-// tests/test_multi_click_oracle.py).
+// one GPU as decoder launches, and a prompt as the points the decoder takes (pack_points): pure host logic (no HIP, no
+// environment), tested without a GPU (tests/prompt_plan_cases.cpp, tests/test_multi_click_oracle.py).
 //
 // Entries -> prompts.  An entry with a handle opens a prompt and is read as it always was: its point (regions == NULL), its
 // region (points == NULL), or -- both arrays given -- its region refined by its foreground point.  An entry WITHOUT a handle
@@ -23,6 +23,8 @@
 // directly after a mark, and a mark as the last entry of a prompt, are refused.  plan_prompts itself knows no marks: the
 // value 4 is one more label it refuses.
 #pragma once
+
+#include "prompt_geometry.hpp"
 
 #include <stdexcept>
 #include <string>
@@ -75,11 +77,6 @@ inline std::vector<PromptSpec> plan_prompts(std::vector<char> const& has_handle,
     return prompts;
 }
 
-// label of click c (0: the head's own) of a prompt
-inline int click_label(PromptSpec const& p, int c, int const* regions) {
-    return (c == 0 || !regions) ? 1 : regions[4 * (p.head + c)];
-}
-
 struct PromptChunk {
     int points = 0;                  // packed points of every prompt of the chunk
     std::vector<int> prompts;        // indices into the call's prompt list, caller's order
@@ -100,6 +97,14 @@ struct StagedPrompts {
 
 inline bool is_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kRefineMark; }
 
+// the one stage of a prompt without marks: its clicks travel in consecutive entries
+inline PromptStages unmarked_stages(PromptSpec const& p) {
+    PromptStages s;
+    for (int c = 0; c < p.clicks; ++c) s.click_entry.push_back(p.head + c);
+    s.stage_clicks.push_back(p.clicks);
+    return s;
+}
+
 // plan_prompts for a call that may hold marks; without one it is plan_prompts (same prompts, same refusals).  mask_branch: the
 // model has the prompt encoder's mask branch (pe.mask.*), without which no stage can take a mask input.
 inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
@@ -109,12 +114,7 @@ inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bo
     StagedPrompts out;
     if (!any_mark) {
         out.prompts = plan_prompts(has_handle, points_given, regions);
-        for (PromptSpec const& p : out.prompts) {
-            PromptStages s;
-            for (int c = 0; c < p.clicks; ++c) s.click_entry.push_back(p.head + c);
-            s.stage_clicks.push_back(p.clicks);
-            out.stages.push_back(s);
-        }
+        for (PromptSpec const& p : out.prompts) out.stages.push_back(unmarked_stages(p));
         return out;
     }
     // the call without its marks is an ordinary call, which plan_prompts reads (a marked prompt has two clicks or more, so
@@ -173,9 +173,41 @@ inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bo
     return out;
 }
 
-// label of click c of a prompt that may hold marks
-inline int staged_click_label(PromptStages const& s, int c, int const* regions) {
+// label of click c (0: the head's own) of a prompt, marked or not
+inline int click_label(PromptStages const& s, int c, int const* regions) {
     return (c == 0 || !regions) ? 1 : regions[4 * s.click_entry[c]];
+}
+// the spellings programs written against the earlier header use: the same rule, by the prompt (unmarked) or by its stages
+inline int click_label(PromptSpec const& p, int c, int const* regions) { return click_label(unmarked_stages(p), c, regions); }
+inline int staged_click_label(PromptStages const& s, int c, int const* regions) { return click_label(s, c, regions); }
+
+// The first n_clicks clicks of a prompt as the decoder takes them, from the call's arrays (points [count][2], regions
+// [count][4]): the clicks in the order given with their labels, each from the entry it travels in, then the corners of the
+// head's box (labels 2, 3), or the padding point (0, 0), label -1, when there is none (SAM's PromptEncoder.forward /
+// SamOnnxModel._embed_points).  n_clicks == spec.clicks: the prompt itself; fewer: a stage of a marked prompt, packed exactly
+// as an unmarked prompt of those clicks.  coords [n][2] in the frame of `rs`, labels [n]; returns n = n_clicks + 2 with a
+// box, n_clicks + 1 without (PromptSpec::points() for the whole prompt).
+inline int pack_points(ResizeLongestSide const& rs, PromptSpec const& spec, PromptStages const& stages, int n_clicks, int const* points,
+                       int const* regions, float* coords, float* labels) {
+    int n = 0;
+    auto set = [&](Point p, int label) {
+        const Point t = rs.transform(p);
+        coords[n * 2 + 0] = float(t.x);
+        coords[n * 2 + 1] = float(t.y);
+        labels[n++] = float(label);
+    };
+    for (int c = 0; c < n_clicks; ++c) {
+        const int e = stages.click_entry[c];
+        set(Point{points[e * 2], points[e * 2 + 1]}, click_label(stages, c, regions));
+    }
+    if (spec.box) {
+        int const* r = regions + 4 * spec.head;
+        set(Point{r[0], r[1]}, 2);
+        set(Point{r[2], r[3]}, 3);
+    } else {
+        set(Point{0, 0}, -1);
+    }
+    return n;
 }
 
 // `mine`: the prompts (indices) one GPU decodes, in the caller's order

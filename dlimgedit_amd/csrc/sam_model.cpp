@@ -664,13 +664,11 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
     float* iou_out = iou_.get() + (size_t)first * 4;
 
     auto body = [&] {
-        // a SAM-HQ model: the last point of every prompt is the HQ token's pseudo-point (decode() appended it)
-        float const* hq_token = hq ? W.hq_token_.get() : nullptr;
         // prompts travel as kernel arguments of the first launch
-        k::DecoderPrompts prompts{};
-        std::memcpy(prompts.coords, coords, (size_t)P * points * 2 * sizeof(float));
-        std::memcpy(prompts.labels, labels, (size_t)P * points * sizeof(float));
-        for (int i = 0; i < P; ++i) prompts.emb[i] = emb[i];
+        k::DecoderStartInputs start;
+        std::memcpy(start.prompts.coords, coords, (size_t)P * points * 2 * sizeof(float));
+        std::memcpy(start.prompts.labels, labels, (size_t)P * points * sizeof(float));
+        for (int i = 0; i < P; ++i) start.prompts.emb[i] = emb[i];
 
         // Token side.  `cur` is the running token matrix as its consumers read it: un-normalised rows plus the
         // LayerNorm that belongs in front of them (applied on the fly by whoever reads, kernels/decoder.hip).
@@ -705,20 +703,23 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
             DecoderLayer const& L = W.dec_[0];
             k::TokenLinear qkv[3] = {lin({}, 256, L.self_attn.q, {}, sq_.get(), 0), lin({}, 256, L.self_attn.k, {}, sk_.get(), 0),
                                      lin({}, 256, L.self_attn.v, {}, sv_.get(), 0)};
+            start.pe = W.prompt_encoder();
+            start.tokens = tokens_.get(); start.first = qkv; start.n_first = 3;
+            start.keys = keys_.get(); start.keys_h = keys_h_.get();
+            // a SAM-HQ model: the last point of every prompt is the HQ token's pseudo-point (decode() appended it)
+            if (hq) start.hq_token = W.hq_token_.get();
+            const k::MaskBranch branch = W.mask_branch();
+            float const* h[k::kDecoderMaxPrompts];
             if (mask_input) {
                 // SAM's mask input: the branch's two strided convolutions on the logits, its last (1x1) one inside the keys'
                 // initialisation, where the dense embedding takes the place of no_mask_embed
-                const k::MaskBranch branch = W.mask_branch();
                 k::mask_embed(mask_input, branch, mask_h_.get(), P, s);
-                float const* h[k::kDecoderMaxPrompts];
                 for (int i = 0; i < P; ++i) h[i] = mask_h_.get() + (size_t)i * kTokens * k::kMaskHidden;
-                k::decoder_start_masked(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
-                                        W.mask_tokens_.get(), tokens_.get(), qkv, 3, h, branch, keys_.get(), keys_h_.get(), P, TOK, s,
-                                        hq_token);
-            } else
-            k::decoder_start(prompts, W.pe_gauss_.get(), W.pe_point_.get(), W.pe_not_a_point_.get(), W.iou_token_.get(),
-                             W.mask_tokens_.get(), tokens_.get(), qkv, 3, W.pe_no_mask_.get(), keys_.get(), keys_h_.get(), P, TOK, s,
-                             hq_token);
+                start.mask_h = h; start.mask = &branch;
+            } else {
+                start.no_mask = W.pe_no_mask_.get();
+            }
+            k::decoder_start(start, P, TOK, s);
         }
         for (int i = 0; i < 2; ++i) {
             DecoderLayer const& L = W.dec_[i];
@@ -840,15 +841,9 @@ void SamModel::masks_on_device(k::PostJob const* jobs, int count) {
 }
 
 void SamModel::masks_to_host(k::PostJob const* jobs, int count) {
-    MaskSlot& slot = acquire_mask_slot();
-    try {
-        enqueue_masks(slot, jobs, count, 0);
-        finish_masks(slot, jobs, count, nullptr, 0);
-    } catch (...) {
-        release_mask_slot(slot);
-        throw;
-    }
-    release_mask_slot(slot);
+    MaskSlotLease lease(*this);
+    enqueue_masks(lease.slot(), jobs, count, 0);
+    finish_masks(lease.slot(), jobs, count, nullptr, 0);
 }
 
 }  // namespace dlimg

@@ -86,6 +86,9 @@ struct SamWeights {
     LinearH neck1_, neck2_;               // 1x1 conv [256, D]; 3x3 conv as [256, 9*256] (tap-major columns)
     NormW neck_ln1_, neck_ln2_;
     DeviceBuffer<float> pe_gauss_, pe_point_, pe_not_a_point_, pe_no_mask_;
+    k::PromptEncoderWeights prompt_encoder() const {
+        return k::PromptEncoderWeights{pe_gauss_.get(), pe_point_.get(), pe_not_a_point_.get(), iou_token_.get(), mask_tokens_.get()};
+    }
     // the prompt encoder's mask branch (pe.mask.*), optional in the file: without it no prompt can take a mask input
     bool has_mask_branch_ = false;
     DeviceBuffer<float> mask_w1_, mask_b1_, mask_w2_, mask_b2_, mask_proj_w_, mask_proj_b_;
@@ -211,9 +214,10 @@ class SamModel {
     float const* iou() const { return iou_.get(); }
 
     // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):
-    // acquire_mask_slot (no mutex needed), enqueue_masks with the first n_iou IoU predictions of the last decode() (under
-    // mutex()), finish_masks (no mutex), release_mask_slot.  enqueue_masks_device / wait_masks: jobs[i].dst are pointers
-    // valid on HIP device dst_device, which may be ANOTHER GPU ("all masks on one device").
+    // acquire_mask_slot (no mutex needed; callers hold the slot as a MaskSlotLease, below), enqueue_masks with the first
+    // n_iou IoU predictions of the last decode() (under mutex()), finish_masks (no mutex), release_mask_slot.
+    // enqueue_masks_device / wait_masks: jobs[i].dst are pointers valid on HIP device dst_device, which may be ANOTHER GPU
+    // ("all masks on one device").
     using MaskSlot = dlimg::MaskSlot;
     MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
     void release_mask_slot(MaskSlot& s) { masks_.release(s); }
@@ -359,6 +363,36 @@ class SamModel {
     StageClock clock_;
     CompletionEvents done_events_;
     MaskTransport masks_;
+};
+
+// A mask slot of one lane for as long as the lease lives: taken in the constructor, handed back in the destructor or by
+// release() before that, on every path.  What may still be queued on the slot is not the lease's business: an error path
+// waits for the lane's stream BEFORE the lease ends (segmentation.cpp, drain_lane).
+class MaskSlotLease {
+  public:
+    explicit MaskSlotLease(SamModel& model) : model_(&model), slot_(&model.acquire_mask_slot()) {}
+    MaskSlotLease(MaskSlotLease&& o) noexcept : model_(o.model_), slot_(o.slot_) { o.slot_ = nullptr; }
+    MaskSlotLease& operator=(MaskSlotLease&& o) noexcept {
+        if (this != &o) {
+            release();
+            model_ = o.model_;
+            slot_ = o.slot_;
+            o.slot_ = nullptr;
+        }
+        return *this;
+    }
+    ~MaskSlotLease() { release(); }
+    void release() noexcept {
+        if (slot_) model_->release_mask_slot(*slot_);
+        slot_ = nullptr;
+    }
+    bool held() const { return slot_ != nullptr; }
+    SamModel& model() const { return *model_; }
+    SamModel::MaskSlot& slot() const { return *slot_; }
+
+  private:
+    SamModel* model_;
+    SamModel::MaskSlot* slot_;
 };
 
 }  // namespace dlimg

@@ -16,97 +16,19 @@ namespace dlimg {
 
 int channel_bytes(int channels) { return channels > 4 ? 4 : channels; }
 
-int scale_coord(int coord, float scale) { return int(float(coord) * scale + 0.5f); }
-
-void ResizeLongestSide::set(Extent image) {
-    original = image;
-    scale = float(max_side_) / float(std::max(image.width, image.height));
-    resized = image;
-    if (scale != 1) resized = Extent{scale_coord(image.width, scale), scale_coord(image.height, scale)};
-}
-
 int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float* coords, float* labels) {
     DLIMG_ASSERT(point != nullptr || region != nullptr);
-    auto set = [&](int index, Point p, int label) {
-        Point t = rs.transform(p);
-        coords[index * 2 + 0] = float(t.x);
-        coords[index * 2 + 1] = float(t.y);
-        labels[index] = float(label);
-    };
-    if (point && region) {
-        set(0, *point, 1);           // PromptEncoder.forward: points first, then the corners; a box takes no padding point
-        set(1, region->top_left, 2);
-        set(2, region->bottom_right, 3);
-        return 3;
+    // a call of one entry: its click when there is a point, its box when there is a region
+    PromptSpec spec;
+    spec.clicks = point ? 1 : 0;
+    spec.box = region != nullptr;
+    const int points[2] = {point ? point->x : 0, point ? point->y : 0};
+    int regions[4] = {0, 0, 0, 0};
+    if (region) {
+        regions[0] = region->top_left.x; regions[1] = region->top_left.y;
+        regions[2] = region->bottom_right.x; regions[3] = region->bottom_right.y;
     }
-    if (point) {
-        set(0, *point, 1);
-        set(1, Point{0, 0}, -1);     // padding point of the exported decoder graph
-    } else {
-        set(0, region->top_left, 2);
-        set(1, region->bottom_right, 3);
-    }
-    return 2;
-}
-
-namespace {
-// One prompt of a batch call (prompt_plan.hpp) from the call's arrays, points [count][2] and regions [count][4]: up to one
-// click it is pack_prompt's prompt; with more, the clicks in the order given with their labels, then the corners of the
-// box, or the padding point when there is none (SamOnnxModel._embed_points).  coords [points()][2], labels [points()].
-void pack_batch_prompt(ResizeLongestSide const& rs, PromptSpec const& spec, int const* points, int const* regions, float* coords,
-                       float* labels) {
-    const int i = spec.head;
-    Point p;
-    Region r;
-    if (spec.clicks) p = Point{points[i * 2], points[i * 2 + 1]};
-    if (spec.box) r = Region{Point{regions[i * 4], regions[i * 4 + 1]}, Point{regions[i * 4 + 2], regions[i * 4 + 3]}};
-    if (spec.clicks <= 1) {
-        pack_prompt(rs, spec.clicks ? &p : nullptr, spec.box ? &r : nullptr, coords, labels);
-        return;
-    }
-    auto set = [&](int index, Point q, int label) {
-        Point t = rs.transform(q);
-        coords[index * 2 + 0] = float(t.x);
-        coords[index * 2 + 1] = float(t.y);
-        labels[index] = float(label);
-    };
-    for (int c = 0; c < spec.clicks; ++c)
-        set(c, Point{points[(i + c) * 2], points[(i + c) * 2 + 1]}, click_label(spec, c, regions));
-    if (spec.box) {
-        set(spec.clicks, r.top_left, 2);
-        set(spec.clicks + 1, r.bottom_right, 3);
-    } else {
-        set(spec.clicks, Point{0, 0}, -1);
-    }
-}
-
-// Stage `n_clicks` of a prompt that holds refinement marks (prompt_plan.hpp): its first n_clicks clicks -- which do not lie in
-// consecutive entries -- then the box or the padding point, packed exactly as an unmarked prompt of those clicks is.
-void pack_stage(ResizeLongestSide const& rs, PromptSpec const& spec, PromptStages const& stages, int n_clicks, int const* points,
-                int const* regions, float* coords, float* labels) {
-    PromptSpec part = spec;
-    part.clicks = n_clicks;
-    if (n_clicks <= 1) {
-        pack_batch_prompt(rs, part, points, regions, coords, labels);
-        return;
-    }
-    const int i = spec.head;
-    auto set = [&](int index, Point q, int label) {
-        Point t = rs.transform(q);
-        coords[index * 2 + 0] = float(t.x);
-        coords[index * 2 + 1] = float(t.y);
-        labels[index] = float(label);
-    };
-    for (int c = 0; c < n_clicks; ++c) {
-        const int e = stages.click_entry[c];
-        set(c, Point{points[e * 2], points[e * 2 + 1]}, staged_click_label(stages, c, regions));
-    }
-    if (spec.box) {
-        set(n_clicks, Point{regions[i * 4], regions[i * 4 + 1]}, 2);
-        set(n_clicks + 1, Point{regions[i * 4 + 2], regions[i * 4 + 3]}, 3);
-    } else {
-        set(n_clicks, Point{0, 0}, -1);
-    }
+    return pack_points(rs, spec, unmarked_stages(spec), spec.clicks, points, regions, coords, labels);
 }
 
 // The prompts of a batch call, packed: prompt j's points start at point at[j] of coords / labels.  A staged prompt (stages[j]
@@ -117,6 +39,10 @@ struct BatchPrompts {
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
+
+namespace {
+constexpr int kPromptChunk = 8;          // prompts of one decode of a batch call, at most (prompt_plan.hpp)
+
 BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions) {
     std::vector<char> has_handle(count);
     SegmentationImpl const* any = nullptr;
@@ -145,13 +71,9 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     }
     b.coords.resize(total * 2);
     b.labels.resize(total);
-    for (size_t j = 0; j < b.prompts.size(); ++j) {
-        ResizeLongestSide const& rs = segs[b.prompts[j].head]->geometry();
-        if (b.stages[j].staged())
-            pack_stage(rs, b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
-        else
-            pack_batch_prompt(rs, b.prompts[j], points, regions, &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
-    }
+    for (size_t j = 0; j < b.prompts.size(); ++j)
+        pack_points(segs[b.prompts[j].head]->geometry(), b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions,
+                    &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
     return b;
 }
 // What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
@@ -171,17 +93,14 @@ std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> c
 // mask input of the last stage: the plane the stage before it would deliver, where that decode left it.
 k::MaskSource run_early_stages(SamModel& model, BatchPrompts const& b, int j, float const* emb, ResizeLongestSide const& rs,
                                int const* points, int const* regions) {
-    PromptSpec const& spec = b.prompts[j];
     PromptStages const& st = b.stages[j];
     float coords[2 * k::kDecoderMaxPoints], labels[k::kDecoderMaxPoints];
     k::MaskSource src{nullptr, nullptr};
     for (size_t s = 0; s + 1 < st.stage_clicks.size(); ++s) {
-        PromptSpec part = spec;
-        part.clicks = st.stage_clicks[s];
-        pack_stage(rs, spec, st, part.clicks, points, regions, coords, labels);
-        model.decode(&emb, coords, labels, 1, part.points(), s ? &src : nullptr, /*handles*/ true);
+        const int npts = pack_points(rs, b.prompts[j], st, st.stage_clicks[s], points, regions, coords, labels);
+        model.decode(&emb, coords, labels, 1, npts, s ? &src : nullptr, /*handles*/ true);
         // single_mask_job's rule: the best of planes 1..3 for a two-point stage, plane 0 otherwise
-        src = k::MaskSource{model.logits(), part.points() > 2 ? nullptr : model.iou()};
+        src = k::MaskSource{model.logits(), npts > 2 ? nullptr : model.iou()};
     }
     return src;
 }
@@ -308,24 +227,15 @@ template <typename F> void for_each_replica(EnvironmentImpl& env, std::vector<in
         helpers.workers.push_back(std::make_unique<LaneWorker>());
         helpers.bound_to.push_back(-1);
     }
-    struct Handed { std::promise<void> result; std::future<void> answer; };
-    std::vector<std::shared_ptr<Handed>> handed;
+    std::vector<std::future<void>> answers;
     for (size_t t = 0; t < n_help; ++t) {
-        auto h = std::make_shared<Handed>();
-        h->answer = h->result.get_future();
-        handed.push_back(h);
         const int replica = used[t + 1], device = env.device_of(replica);
         const bool bind = helpers.bound_to[t] != device;
         helpers.bound_to[t] = device;
-        helpers.workers[t]->post([h, &body, replica, device, bind] {
-            try {
-                if (bind) bind_thread_near_device(device);
-                body(replica);
-                h->result.set_value();
-            } catch (...) {
-                h->result.set_exception(std::current_exception());
-            }
-        });
+        answers.push_back(post_with_result(*helpers.workers[t], [&body, replica, device, bind] {
+            if (bind) bind_thread_near_device(device);
+            body(replica);
+        }));
     }
     std::exception_ptr first;
     try {
@@ -333,14 +243,7 @@ template <typename F> void for_each_replica(EnvironmentImpl& env, std::vector<in
     } catch (...) {
         first = std::current_exception();
     }
-    for (auto& h : handed) {                     // every task is waited for: they refer to the caller's frame
-        try {
-            h->answer.get();
-        } catch (...) {
-            if (!first) first = std::current_exception();
-        }
-    }
-    if (first) std::rethrow_exception(first);
+    wait_for_all(answers, first, [](size_t) {}, [](size_t) {});
 }
 
 // overflow: the pass's report (SamModel::last_pass_flag), read once its event has been waited for
@@ -468,36 +371,18 @@ void SegmentationImpl::process_batch(EnvironmentImpl& env, SegmentationImpl* con
                 // which one thread would spend lane after lane while the later lanes' part of the chip waits (8 images
                 // from one thread: 718 -> 734 images/s).  With several callers the lanes are fed in parallel anyway and
                 // the hand-over only costs (two threads x 8 images: 846 without, 824 with)
-                // (the promise is shared with the task: it must outlive the task's set_value call, which may still be
-                // returning when this thread has its answer)
-                struct Handed { SamModel* model; std::promise<Queued> result; std::future<Queued> answer; };
-                std::vector<std::shared_ptr<Handed>> handed;
+                std::vector<SamModel*> lanes_used;
+                std::vector<std::future<Queued>> answers;
                 for (size_t base = 0; base < mine.size(); base += chunk) {
                     const int n = (int)std::min<size_t>(chunk, mine.size() - base);
-                    SamModel& model = env.next_lane(replica);
-                    auto h = std::make_shared<Handed>();
-                    h->model = &model;
-                    h->answer = h->result.get_future();
-                    handed.push_back(h);
-                    env.lane_worker(replica, model.lane_index()).post([h, &run_chunk, base, n] {
-                        try {
-                            h->result.set_value(run_chunk(*h->model, base, n));
-                        } catch (...) {
-                            h->result.set_exception(std::current_exception());
-                        }
-                    });
+                    SamModel* model = &env.next_lane(replica);
+                    lanes_used.push_back(model);
+                    answers.push_back(post_with_result(env.lane_worker(replica, model->lane_index()),
+                                                       [&run_chunk, model, base, n] { return run_chunk(*model, base, n); }));
                 }
-                std::exception_ptr first;
-                for (auto& h : handed) {             // every task is waited for: they refer to this frame
-                    try {
-                        const Queued q = h->answer.get();
-                        waiting.push_back(Waiting{h->model, q.done, q.overflow});
-                    } catch (...) {
-                        drain_lane(h->model);        // whatever the failed pass queued runs to completion first
-                        if (!first) first = std::current_exception();
-                    }
-                }
-                if (first) std::rethrow_exception(first);
+                wait_for_all(
+                    answers, nullptr, [&](size_t i, Queued q) { waiting.push_back(Waiting{lanes_used[i], q.done, q.overflow}); },
+                    [&](size_t i) { drain_lane(lanes_used[i]); });     // whatever the failed pass queued runs to completion first
             } else {
                 for (size_t base = 0; base < mine.size(); base += chunk) {
                     const int n = (int)std::min<size_t>(chunk, mine.size() - base);
@@ -561,7 +446,7 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
     k::PostJob jobs[3];
     int n_jobs = 0;
     float iou[4] = {0.f, 0.f, 0.f, 0.f};
-    SamModel::MaskSlot& slot = model_.acquire_mask_slot();
+    MaskSlotLease lease(model_);
     try {
         {
             roctx::Range range("dlimg.compute_mask");
@@ -581,30 +466,119 @@ void SegmentationImpl::compute_mask(Point const* point, Region const* region, ui
                                                 o.width, o.height, r.width, r.height};
             }
             roctx::Range rp("dlimg.post");
-            model_.enqueue_masks(slot, jobs, n_jobs, is_single_mask ? 0 : 4);
+            model_.enqueue_masks(lease.slot(), jobs, n_jobs, is_single_mask ? 0 : 4);
         }
-        model_.finish_masks(slot, jobs, n_jobs, iou, is_single_mask ? 0 : 4);      // waits outside the lane's mutex
+        model_.finish_masks(lease.slot(), jobs, n_jobs, iou, is_single_mask ? 0 : 4);      // waits outside the lane's mutex
     } catch (...) {
         drain_lane(&model_);                     // a copy into the slot's staging memory may still be queued
-        model_.release_mask_slot(slot);
         throw;
     }
-    model_.release_mask_slot(slot);
+    lease.release();
     if (behind) settle();                        // has completed; an embedding with non-finite values: no masks, the error
     if (!is_single_mask)
         for (int i = 0; i < 3; ++i) out_accuracy[i] = iou[i + 1];
 }
 
-// Prompts are grouped by the replica that holds their image's embedding; on each GPU they are grouped by their number of
-// points (a decoder launch holds one count) and cut into chunks of at most kPromptChunk prompts (prompt_plan.hpp), each chunk
-// decoded as one batch on the next lane, its masks copied out while the next chunk runs.  A prompt with refinement marks is a
-// chunk of its own behind them: its stages run in order on one lane's stream, each taking the logits of the one before it as
-// its mask input, and only the last one is post-processed.
+namespace {
+// Where the masks of a batch call go and how a chunk of them gets there: what the two forms of the call differ in.
+//   kRange         ROCTX range around a chunk's enqueue
+//   kFinishBehind  the chunk that many chunks back is finished before the next one takes its slot (0: all at the end)
+//   dst(head)      where the mask of the prompt that entry `head` opened goes
+//   enqueue        under the lane's mutex, behind the chunk's decode;  finish: no mutex, returns when the masks are in place
+struct HostMasks {
+    static constexpr const char* kRange = "dlimg.compute_masks";
+    // masks of a chunk are copied to the caller while the two chunks behind it are on the GPU
+    static constexpr size_t kFinishBehind = 3;
+    uint8_t* const* out_masks;
+    uint8_t* dst(int head) const { return out_masks[head]; }
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
+        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0);
+    }
+    void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
+        model.finish_masks(slot, jobs.data(), (int)jobs.size(), nullptr, 0);
+    }
+};
+struct DeviceMasks {
+    static constexpr const char* kRange = "dlimg.compute_masks_device";
+    static constexpr size_t kFinishBehind = 0;
+    uint8_t* dev_out;
+    std::vector<size_t> const& offsets;          // [entry]
+    int root_device;
+    uint8_t* dst(int head) const { return dev_out + offsets[head]; }
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
+        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device);
+    }
+    void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const&) const { model.wait_masks(slot); }
+};
+}  // namespace
+
+// The prompts of a batch call whose embeddings `replica` holds: grouped by their number of points (a decoder launch holds one
+// count) and cut into chunks of at most kPromptChunk prompts (prompt_plan.hpp), each chunk decoded as one batch on the next
+// lane and its masks handed to `sink`.  A prompt with refinement marks is a chunk of its own behind them: its stages run in
+// order on one lane's stream, each taking the logits of the one before it as its mask input, and only the last one is
+// post-processed.
+template <typename Sink>
+void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
+                                       int const* regions, Sink const& sink) {
+    std::vector<PromptSpec> const& prompts = batch.prompts;
+    EnvironmentImpl& env = segs[prompts[0].head]->env_;
+    HIP_CHECK(hipSetDevice(env.device_of(replica)));
+    std::vector<int> mine;
+    for (int j = 0; j < (int)prompts.size(); ++j)
+        if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
+    struct Chunk { MaskSlotLease lease; std::vector<k::PostJob> jobs; };
+    std::vector<Chunk> chunks;
+    auto finish = [&](Chunk& c) {
+        if (!c.lease.held()) return;
+        const MaskSlotLease lease = std::move(c.lease);      // the slot goes back whether the wait throws or not
+        sink.finish(lease.model(), lease.slot(), c.jobs);
+    };
+    try {
+        std::vector<float> cc, ll;
+        for (BatchWork const& work : plan_batch_work(batch, mine, kPromptChunk)) {
+            PromptChunk const& part = work.part;
+            const int n = (int)part.prompts.size(), npts = part.points;
+            std::vector<float const*> emb(n);
+            for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
+            gather_chunk(batch, part, cc, ll);
+            SamModel& model = env.next_lane(replica);
+            if (Sink::kFinishBehind && chunks.size() >= Sink::kFinishBehind) finish(chunks[chunks.size() - Sink::kFinishBehind]);
+            chunks.push_back(Chunk{MaskSlotLease(model), std::vector<k::PostJob>(n)});
+            Chunk& cur = chunks.back();
+            roctx::Range range(Sink::kRange);
+            std::lock_guard<std::mutex> lock(model.mutex());
+            if (work.staged) {
+                const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
+                model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
+            } else {
+                model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
+            }
+            for (int j = 0; j < n; ++j) {
+                const int i = prompts[part.prompts[j]].head;
+                const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
+                cur.jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
+                                              sink.dst(i), o, r);
+            }
+            sink.enqueue(model, cur.lease.slot(), cur.jobs);
+        }
+        for (auto& c : chunks) finish(c);
+    } catch (...) {
+        // a chunk whose enqueue failed has no valid completion event: drain the lanes before the slots go back
+        for (auto& c : chunks)
+            if (c.lease.held()) drain_lane(&c.lease.model());
+        for (auto& c : chunks) {
+            try { finish(c); } catch (...) {}
+        }
+        throw;
+    }
+}
+
+// Prompts are grouped by the replica that holds their image's embedding and decoded there (decode_batch_on), the masks of a
+// chunk copied out while the next chunks run.
 void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, int count, int const* points,
                                           int const* regions, uint8_t* const* out_masks) {
     if (count <= 0) return;
     DLIMG_ASSERT(points != nullptr || regions != nullptr);
-    constexpr int kPromptChunk = 8;
     const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
     std::vector<PromptSpec> const& prompts = batch.prompts;
     EnvironmentImpl& env = segs[prompts[0].head]->env_;
@@ -616,73 +590,15 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
         seg->settle();                           // prompts of a batch go to any lane: the embeddings are complete first
         if (std::find(used.begin(), used.end(), seg->replica_) == used.end()) used.push_back(seg->replica_);
     }
-    for_each_replica(env, used, [&](int replica) {
-        HIP_CHECK(hipSetDevice(env.device_of(replica)));
-        std::vector<int> mine;
-        for (int j = 0; j < (int)prompts.size(); ++j)
-            if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
-        struct Chunk { SamModel* model; SamModel::MaskSlot* slot; std::vector<k::PostJob> jobs; };
-        std::vector<Chunk> chunks;
-        auto finish = [&](Chunk& c) {
-            if (!c.slot) return;
-            SamModel::MaskSlot* slot = c.slot;
-            c.slot = nullptr;
-            try {
-                c.model->finish_masks(*slot, c.jobs.data(), (int)c.jobs.size(), nullptr, 0);
-            } catch (...) {
-                c.model->release_mask_slot(*slot);
-                throw;
-            }
-            c.model->release_mask_slot(*slot);
-        };
-        try {
-            std::vector<float> cc, ll;
-            for (BatchWork const& work : plan_batch_work(batch, mine, kPromptChunk)) {
-                PromptChunk const& part = work.part;
-                const int n = (int)part.prompts.size(), npts = part.points;
-                std::vector<float const*> emb(n);
-                for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
-                gather_chunk(batch, part, cc, ll);
-                SamModel& model = env.next_lane(replica);
-                // masks of a chunk are copied to the caller while the two chunks behind it are on the GPU
-                if (chunks.size() >= 3) finish(chunks[chunks.size() - 3]);
-                Chunk c{&model, &model.acquire_mask_slot(), std::vector<k::PostJob>(n)};
-                chunks.push_back(std::move(c));
-                Chunk& cur = chunks.back();
-                roctx::Range range("dlimg.compute_masks");
-                std::lock_guard<std::mutex> lock(model.mutex());
-                if (work.staged) {
-                    const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
-                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
-                } else {
-                    model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
-                }
-                for (int j = 0; j < n; ++j) {
-                    const int i = prompts[part.prompts[j]].head;
-                    const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
-                    cur.jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
-                                                  out_masks[i], o, r);
-                }
-                model.enqueue_masks(*cur.slot, cur.jobs.data(), n, 0);
-            }
-            for (auto& c : chunks) finish(c);
-        } catch (...) {
-            // a chunk whose enqueue failed has no valid completion event: drain the lanes before the slots go back
-            for (auto& c : chunks)
-                if (c.slot) drain_lane(c.model);
-            for (auto& c : chunks) {
-                try { finish(c); } catch (...) {}
-            }
-            throw;
-        }
-    });
+    const HostMasks sink{out_masks};
+    for_each_replica(env, used, [&](int replica) { decode_batch_on(replica, segs, batch, points, regions, sink); });
 }
 
 // Device-output variant: the "gather" of SURVEY.md 8e.  Every GPU of the environment decodes the prompts whose
 // embeddings it holds; a mask whose GPU is the root is written in place by the post-processing kernel, the others cross
 // xGMI as one peer copy each (hipMemcpyPeerAsync on the producing lane's stream, so the copy of one chunk runs beside the
-// decoder of the next).  No host memory is touched.  The reference has nothing comparable (one device, host tensors:
-// /root/reference/src/session.cpp:63-66, /root/reference/src/environment.cpp:142).
+// decoder of the next).  No host memory is touched; every chunk is waited for at the end.  The reference has nothing
+// comparable (one device, host tensors: /root/reference/src/session.cpp:63-66, /root/reference/src/environment.cpp:142).
 void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* segs, int count, int const* points,
                                                  int const* regions, int root_device, uint8_t* dev_out,
                                                  size_t* out_offsets) {
@@ -692,7 +608,6 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
     if (root_device < 0 || root_device >= EnvironmentImpl::device_count())
         throw Exception("root device " + std::to_string(root_device) + " is out of range: " +
                         std::to_string(EnvironmentImpl::device_count()) + " device(s) visible");
-    constexpr int kPromptChunk = 8;
     const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
     std::vector<PromptSpec> const& prompts = batch.prompts;
     EnvironmentImpl& env = segs[prompts[0].head]->env_;
@@ -711,61 +626,8 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
         if (std::find(used.begin(), used.end(), seg->replica_) == used.end()) used.push_back(seg->replica_);
     }
     if (out_offsets) std::copy(offsets.begin(), offsets.end(), out_offsets);
-    for_each_replica(env, used, [&](int replica) {
-        HIP_CHECK(hipSetDevice(env.device_of(replica)));
-        std::vector<int> mine;
-        for (int j = 0; j < (int)prompts.size(); ++j)
-            if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
-        struct Chunk { SamModel* model; SamModel::MaskSlot* slot; };
-        std::vector<Chunk> chunks;
-        auto settle = [&](bool drain) {          // wait for every chunk, hand the slots back; first error wins
-            std::exception_ptr first;
-            for (auto& c : chunks) {
-                if (!c.slot) continue;
-                if (drain) drain_lane(c.model);
-                try {
-                    c.model->wait_masks(*c.slot);
-                } catch (...) {
-                    if (!first) first = std::current_exception();
-                }
-                c.model->release_mask_slot(*c.slot);
-                c.slot = nullptr;
-            }
-            if (first) std::rethrow_exception(first);
-        };
-        try {
-            std::vector<float> cc, ll;
-            for (BatchWork const& work : plan_batch_work(batch, mine, kPromptChunk)) {
-                PromptChunk const& part = work.part;
-                const int n = (int)part.prompts.size(), npts = part.points;
-                std::vector<float const*> emb(n);
-                std::vector<k::PostJob> jobs(n);
-                for (int j = 0; j < n; ++j) emb[j] = segs[prompts[part.prompts[j]].head]->embedding_;
-                gather_chunk(batch, part, cc, ll);
-                SamModel& model = env.next_lane(replica);
-                chunks.push_back(Chunk{&model, &model.acquire_mask_slot()});
-                roctx::Range range("dlimg.compute_masks_device");
-                std::lock_guard<std::mutex> lock(model.mutex());
-                if (work.staged) {
-                    const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
-                    model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
-                } else {
-                    model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
-                }
-                for (int j = 0; j < n; ++j) {
-                    const int i = prompts[part.prompts[j]].head;
-                    const Extent o = segs[i]->image_size_.original, r = segs[i]->image_size_.resized;
-                    jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
-                                              dev_out + offsets[i], o, r);
-                }
-                model.enqueue_masks_device(*chunks.back().slot, jobs.data(), n, root_device);
-            }
-            settle(false);
-        } catch (...) {
-            try { settle(true); } catch (...) {}
-            throw;
-        }
-    });
+    const DeviceMasks sink{dev_out, offsets, root_device};
+    for_each_replica(env, used, [&](int replica) { decode_batch_on(replica, segs, batch, points, regions, sink); });
 }
 
 }  // namespace dlimg

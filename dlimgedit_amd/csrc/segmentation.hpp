@@ -5,37 +5,20 @@
 
 #include "common.hpp"
 #include "environment.hpp"
+#include "prompt_geometry.hpp"       // Extent, Point, Region, scale_coord, ResizeLongestSide
 
 #include <dlimgedit/dlimgedit.h>
 
 namespace dlimg {
 
-struct Extent { int width = 0, height = 0; };
-struct Point { int x = 0, y = 0; };
-struct Region { Point top_left, bottom_right; };
+static_assert(kPromptFrame == kImageSize, "prompts are packed in the encoder's frame");
 
 int channel_bytes(int channels);          // 4 for bgra/argb (reference: dlimgedit.impl.hpp:15)
-int scale_coord(int coord, float scale);  // reference: segmentation.cpp:26
-
-// Longest-side-to-1024 geometry (reference: segmentation.cpp:58-74).  The pixel resampling itself is
-// a device kernel here; this struct only keeps the numbers needed later for prompts and masks.
-struct ResizeLongestSide {
-    Extent original;
-    Extent resized;
-    float scale = 1.f;
-
-    explicit ResizeLongestSide(int max_side = kImageSize) : max_side_(max_side) {}
-    void set(Extent image);
-    Point transform(Point p) const { return Point{scale_coord(p.x, scale), scale_coord(p.y, scale)}; }
-
-  private:
-    int max_side_;
-};
 
 // Packs one prompt and returns its number of points.  A point OR a region: two points, the way
 // SegmentationImpl::compute_mask does (reference: segmentation.cpp:135-152; coords[4], labels[2]).  A point AND a region
 // (the batch calls only): three points as SAM's PromptEncoder.forward orders them, the point in front of the box corners
-// and no pad token, labels 1, 2, 3 (coords[6], labels[3]).
+// and no pad token, labels 1, 2, 3 (coords[6], labels[3]).  A one-entry call of pack_points (prompt_plan.hpp).
 int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* region, float* coords, float* labels);
 // Which logits plane a single-mask query of `points` prompt points takes (SamOnnxModel.select_masks adds
 // (points - 2.5) * 1000 to prediction 0): with two points the best of planes 1..3, chosen on the device from the IoU
@@ -43,6 +26,8 @@ int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* r
 inline k::PostJob single_mask_job(float const* logits4, float const* iou4, int points, uint8_t* dst, Extent o, Extent r) {
     return k::PostJob{logits4, points > 2 ? nullptr : iou4, dst, o.width, o.height, r.width, r.height};
 }
+
+struct BatchPrompts;         // segmentation.cpp
 
 class SegmentationImpl {
   public:
@@ -82,6 +67,11 @@ class SegmentationImpl {
     float* embedding_storage(int replica);
 
   private:
+    // the per-GPU body of the two batch mask calls; Sink: where the masks go (segmentation.cpp)
+    template <typename Sink>
+    static void decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
+                                int const* regions, Sink const& sink);
+
     EnvironmentImpl& env_;
     int replica_ = 0;
     ResizeLongestSide image_size_;

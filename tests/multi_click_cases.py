@@ -80,3 +80,25 @@ def reference_mask(emb, rs, clicks, labels, box, params, hw):
     """float64 reference decode of one prompt on a given embedding -> (boolean mask [h, w] of the single-mask mode, plane)."""
     coords, labs = pack(rs, clicks, labels, box)
     return B.reference_mask(emb, coords, labs, len(labs), params, hw)
+
+
+def packed_lines(out):
+    """`packed <head> [stage <clicks>] coords x,y;... labels l,...` lines -> [(the ints in front, coords [[x, y], ...], labels)]"""
+    rows = []
+    for line in out:
+        if not line.startswith("packed"):
+            continue
+        words = line.split()
+        at = words.index("coords")
+        coords = [[float(v) for v in xy.split(",")] for xy in words[at + 1].split(";")]
+        rows.append(([int(w) for w in words[1:at] if w != "stage"], coords, [float(v) for v in words[at + 3].split(",")]))
+    return rows
+
+
+def oracle_frame(name):
+    """-> (the oracle's ResizeLongestSide of image `name`, its extent as the case programs take it: <width>x<height>)"""
+    from oracle import sam_oracle as O
+    _, w, h = IMAGES[name]
+    rs = O.ResizeLongestSide()
+    rs.target_extent(w, h)
+    return rs, f"{w}x{h}"

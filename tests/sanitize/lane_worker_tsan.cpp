@@ -2,9 +2,12 @@
 //   1. several producer threads post to several workers while other threads drain them;
 //   2. the step queue's ticket protocol (environment.hpp, StepTicket): the worker writes `done`, then state (release); the
 //      planner reads state (acquire), then `done`;
-//   3. the batch call's promise hand-over (segmentation.cpp, process_batch): the task shares the promise with the caller.
+//   3. the batch calls' hand-over (post_with_result / wait_for_all, as segmentation.cpp's process_batch and
+//      for_each_replica use them): the task shares the promise with the caller, every task is waited for although one throws,
+//      and the first exception is the one the caller sees.
 #include "lane_worker.hpp"
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <future>
@@ -60,17 +63,38 @@ int main() {
     {   // 3
         LaneWorker a, b;
         for (int round = 0; round < 200; ++round) {
-            struct Handed { std::promise<int> result; std::future<int> answer; };
-            std::vector<std::shared_ptr<Handed>> handed;
             int frame_local = round;                        // the tasks refer to the caller's frame, as run_chunk does
-            for (int i = 0; i < 4; ++i) {
-                auto h = std::make_shared<Handed>();
-                h->answer = h->result.get_future();
-                handed.push_back(h);
-                (i & 1 ? a : b).post([h, &frame_local, i] { h->result.set_value(frame_local * 4 + i); });
-            }
+            const int thrower = round % 5 - 1;              // -1: nobody throws
+            std::vector<std::future<int>> answers;
             for (int i = 0; i < 4; ++i)
-                if (handed[i]->answer.get() != round * 4 + i) { std::printf("round %d: wrong answer\n", round); return 1; }
+                answers.push_back(dlimg::post_with_result(i & 1 ? a : b, [&frame_local, i, thrower] {
+                    if (i == thrower || i == 3 - thrower) throw frame_local * 4 + i;
+                    return frame_local * 4 + i;
+                }));
+            int got = 0, failed = 0, thrown = -1;
+            try {
+                dlimg::wait_for_all(
+                    answers, nullptr, [&](size_t i, int v) { got += v == round * 4 + (int)i; }, [&](size_t) { ++failed; });
+            } catch (int v) {
+                thrown = v;
+            }
+            const int throwers = thrower < 0 ? 0 : 2;       // tasks `thrower` and 3 - thrower (never the same one)
+            if (got != 4 - throwers || failed != throwers || thrown != (thrower < 0 ? -1 : round * 4 + std::min(thrower, 3 - thrower))) {
+                std::printf("round %d: %d answers, %d failures, %d thrown\n", round, got, failed, thrown);
+                return 1;
+            }
+            // void tasks beside the caller's own exception, which wins (for_each_replica)
+            std::vector<std::future<void>> done;
+            std::atomic<int> ran{0};
+            for (int i = 0; i < 4; ++i)
+                done.push_back(dlimg::post_with_result(i & 1 ? a : b, [&ran, i] { ++ran; if (i == 2) throw 2; }));
+            try {
+                dlimg::wait_for_all(done, std::make_exception_ptr(-7), [](size_t) {}, [](size_t) {});
+                std::printf("round %d: no exception\n", round);
+                return 1;
+            } catch (int v) {
+                if (v != -7 || ran != 4) { std::printf("round %d: thrown %d after %d tasks\n", round, v, (int)ran); return 1; }
+            }
         }
     }
     std::printf("ok\n");

@@ -1,11 +1,13 @@
 // ASan + UBSan harness for the pure host planners (tests/test_sanitizers.py): csrc/step_queue.hpp (which lane takes which
 // requests), csrc/mask_pieces.hpp (how a batch of masks is cut into transfer pieces), csrc/mask_transport.hpp (which road
 // the masks of a request take to the caller), csrc/resize_tables.cpp (the contributor tables the resize kernels index
-// with) and csrc/gemm_plan.cpp (which tile configuration runs a GEMM) on a few hundred thousand random inputs,
-// with the invariants the callers rely on checked on every one.
+// with), csrc/gemm_plan.cpp (which tile configuration runs a GEMM) and csrc/prompt_plan.hpp (the entries of a batch mask
+// call as prompts, stages and packed points) on a few hundred thousand random inputs, with the invariants the callers rely
+// on checked on every one.
 #include "gemm_plan.hpp"
 #include "mask_pieces.hpp"
 #include "mask_transport.hpp"
+#include "prompt_plan.hpp"
 #include "resize_tables.hpp"
 #include "step_queue.hpp"
 
@@ -231,8 +233,83 @@ static const char* fuzz_mask_transport_once(MaskTransportInput& in, MaskTranspor
     return nullptr;
 }
 
+// csrc/prompt_plan.hpp: calls of 1 to 24 entries -- handles, clicks, marks, now and then a bad label or a mark out of place --
+// with any combination of the two arrays.  What the batch calls rely on: a call is refused or read into prompts whose clicks
+// travel in entries of the call, whose stages grow and end at all clicks; and pack_points writes exactly the points of the
+// stage -- the buffers here hold that many and not one more -- clicks first (labels 0 / 1, the head's 1), then the corners
+// (2, 3) or the padding point (-1).
+static const char* fuzz_prompt_plan_once(int* valid) {
+    const int count = 1 + (int)rnd(24);
+    std::vector<char> has_handle(count);
+    std::vector<int> points(2 * count), regions(4 * count, 0);
+    const bool points_given = rnd(6) != 0, regions_given = rnd(4) != 0, branch = rnd(8) != 0;
+    for (int i = 0; i < count; ++i) {
+        has_handle[i] = i == 0 ? rnd(30) != 0 : rnd(3) == 0;
+        points[2 * i] = (int)rnd(5000) - 500;
+        points[2 * i + 1] = (int)rnd(5000) - 500;
+        int* r = &regions[4 * i];
+        if (has_handle[i]) {
+            r[0] = (int)rnd(2000); r[1] = (int)rnd(2000);
+            r[2] = rnd(3) ? r[0] + (int)rnd(2000) : -1; r[3] = rnd(3) ? r[1] + (int)rnd(2000) : -1;
+        } else {
+            r[0] = rnd(5) == 0 ? kRefineMark : rnd(40) ? (int)rnd(2) : (int)rnd(8) - 2;
+            if (!rnd(60)) r[1 + rnd(3)] = 1 + (int)rnd(3);
+        }
+    }
+    int const* reg = regions_given ? regions.data() : nullptr;
+    StagedPrompts plan;
+    try {
+        plan = plan_staged_prompts(has_handle, points_given, reg, branch);
+    } catch (std::invalid_argument const&) {
+        return nullptr;
+    }
+    ++*valid;
+    if (plan.prompts.empty() || plan.prompts.size() != plan.stages.size()) return "prompts and stages";
+    for (size_t j = 0; j < plan.prompts.size(); ++j) {
+        PromptSpec const& p = plan.prompts[j];
+        PromptStages const& st = plan.stages[j];
+        if (p.head < 0 || p.head >= count || !has_handle[p.head] || p.clicks < 0 || p.clicks > kMaxClicks) return "prompt";
+        if (p.clicks != (points_given ? (int)st.click_entry.size() : 0) || (p.box && !reg)) return "clicks or box without their array";
+        for (int c = 0; c < p.clicks; ++c) {
+            const int e = st.click_entry[c];
+            if (e < p.head || e >= count || (c == 0 ? e != p.head : (has_handle[e] || e <= st.click_entry[c - 1]))) return "click entry";
+            if (c && is_mark_entry(reg, e)) return "a mark read as a click";
+        }
+        if (st.stage_clicks.empty() || st.stage_clicks.back() != p.clicks) return "the last stage does not take all clicks";
+        for (size_t k = 1; k < st.stage_clicks.size(); ++k)
+            if (st.stage_clicks[k] <= st.stage_clicks[k - 1] || st.stage_clicks[0] < 1) return "stages do not grow";
+        ResizeLongestSide rs;
+        rs.set(Extent{1 + (int)rnd(rnd(2) ? 1024 : 8000), 1 + (int)rnd(rnd(2) ? 1024 : 8000)});
+        for (int clicks : st.stage_clicks) {
+            const int want = clicks + (p.box ? 2 : 1);
+            if (clicks == p.clicks && want != p.points()) return "points()";
+            std::vector<float> coords(2 * want), labels(want);          // exactly: ASan sees one write too many
+            if (pack_points(rs, p, st, clicks, points_given ? points.data() : nullptr, reg, coords.data(), labels.data()) != want) return "pack_points: count";
+            for (int c = 0; c < clicks; ++c) {
+                if (labels[c] != (c == 0 ? 1.f : reg ? (float)reg[4 * st.click_entry[c]] : 1.f) || (labels[c] != 0.f && labels[c] != 1.f)) return "pack_points: click label";
+                const Point t = rs.transform(Point{points[2 * st.click_entry[c]], points[2 * st.click_entry[c] + 1]});
+                if (coords[2 * c] != (float)t.x || coords[2 * c + 1] != (float)t.y) return "pack_points: click";
+            }
+            if (p.box) {
+                const Point a = rs.transform(Point{reg[4 * p.head], reg[4 * p.head + 1]}), b = rs.transform(Point{reg[4 * p.head + 2], reg[4 * p.head + 3]});
+                if (labels[clicks] != 2.f || labels[clicks + 1] != 3.f || coords[2 * clicks] != (float)a.x || coords[2 * clicks + 1] != (float)a.y ||
+                    coords[2 * clicks + 2] != (float)b.x || coords[2 * clicks + 3] != (float)b.y) return "pack_points: box";
+            } else if (labels[clicks] != -1.f || coords[2 * clicks] != 0.f || coords[2 * clicks + 1] != 0.f) {
+                return "pack_points: padding point";
+            }
+        }
+    }
+    return nullptr;
+}
+
 int main() {
     if (!fuzz_gemm_plan()) return 1;
+    {
+        int valid = 0;
+        for (int iter = 0; iter < 100000; ++iter)
+            if (const char* bad = fuzz_prompt_plan_once(&valid)) { std::printf("prompt plan: %s (iteration %d)\n", bad, iter); return 1; }
+        if (valid < 20000) { std::printf("prompt plan: only %d of the random calls are served\n", valid); return 1; }
+    }
     {
         MaskTransportInput in;                   // re-used like a slot's
         MaskTransportPlan plan;

@@ -9,7 +9,8 @@
   set is refused, and no other tensor changes;
 * the wrapper's builder (dlimgedit_amd.api.click_entries with refine_after) and the library's planner
   (csrc/prompt_plan.hpp: plan_staged_prompts, printed by tests/mask_input_plan_cases.cpp, built with the host compiler):
-  entry lists and stage lists worked out by hand, and every refusal;
+  entry lists and stage lists worked out by hand, and every refusal; the points it packs for every stage (pack_points) equal
+  the Python side's stage prefixes exactly;
 * the inputs of the GPU tests: for every case the reference mask with mask input differs from the reference of the same
   clicks without it in at least ten times what the GPU tests let a mask disagree in.
 """
@@ -287,6 +288,29 @@ def test_library_refusals_name_the_mark(plan):
         assert line.startswith("error") and "mark" in line, (what, line)
     line = plan([EMPTY, MARK, FG], branch=False)[0]
     assert line.startswith("error") and "mark" in line and "pe.mask" in line
+
+
+def test_library_packs_every_stage_as_the_python_side_does(plan):
+    """pack_points on every stage of every case, both images, in one call: stage k is multi_click_cases.pack of the first k
+    clicks with the prompt's box or the padding point; exact equality (integers held in floats: no tolerance)."""
+    entries, heads = [], []
+    for case in C.CASES:
+        name, clicks, labels, box, _ = case
+        marks = C.stage_clicks(case)[:-1]
+        heads.append(len(entries))
+        region = ",".join(map(str, box)) if box is not None else "0,0,-1,-1"
+        entries.append(f"h:{region}@{clicks[0][0]},{clicks[0][1]}@{M.oracle_frame(name)[1]}")
+        for c in range(1, len(clicks)):
+            if c in marks:
+                entries.append(MARK)
+            entries.append(f"c:{labels[c]},0,0,0@{clicks[c][0]},{clicks[c][1]}")
+    rows = M.packed_lines(plan(entries))
+    want = [(head, k, case) for head, case in zip(heads, C.CASES) for k in C.stage_clicks(case)]
+    assert [r[0] for r in rows] == [[head, k] for head, k, _ in want] and len(rows) == sum(len(C.stage_clicks(c)) for c in C.CASES)
+    for (_, coords, labels), (_, k, case) in zip(rows, want):
+        name, clicks, labs, box, _ = case
+        want_c, want_l = M.pack(M.oracle_frame(name)[0], clicks[:k], labs[:k], box)
+        assert coords == want_c.tolist() and labels == want_l.tolist(), (C.case_id(case), k)
 
 
 def test_mask_input_moves_every_reference_mask(references):

@@ -6,8 +6,9 @@
   box, and a background click on each image;
 * the Python wrapper's entry-list builder (dlimgedit_amd.api.click_entries / pack_clicks, pure host code): order of the
   entries, the padding-point rule, labels, grouping by token rows with the per-launch cuts, the 8-click cap, the refusals;
-* the library's own reading of the entry lists and its grouping of prompts into decoder chunks (csrc/prompt_plan.hpp, printed
-  by tests/prompt_plan_cases.cpp, built here with the host compiler).
+* the library's own reading of the entry lists, its grouping of prompts into decoder chunks and the points it packs for
+  the decoder (csrc/prompt_plan.hpp, printed by tests/prompt_plan_cases.cpp, built here with the host compiler): the packed
+  coordinates and labels equal the Python side's exactly.
 Every expectation is worked out by hand from the rules; none is printed from the code under test."""
 import shutil
 import subprocess
@@ -189,3 +190,36 @@ def test_library_refusals(plan):
     # a click needs `points`; a call needs one of the arrays
     assert plan([f"h0:{BOX}", "c0:1,0,0,0"], points=False)[0].startswith("error")
     assert plan([f"h0:{BOX}"], points=False, regions=False)[0].startswith("error")
+
+
+def test_library_packs_the_multi_click_cases_as_the_python_side_does(plan):
+    """pack_points on the eight CASES, both images, in one call: exact equality with multi_click_cases.pack (integers held
+    in floats: no tolerance)."""
+    entries, heads = [], []
+    for name, clicks, labels, box in M.CASES:
+        heads.append(len(entries))
+        extent = M.oracle_frame(name)[1]
+        region = ",".join(map(str, box)) if box is not None else EMPTY
+        entries.append(f"h0:{region}@{clicks[0][0]},{clicks[0][1]}@{extent}")
+        entries += [f"c0:{l},0,0,0@{x},{y}" for (x, y), l in zip(clicks[1:], labels[1:])]
+    rows = M.packed_lines(plan(entries))
+    assert [r[0] for r in rows] == [[h] for h in heads]
+    for (_, coords, labels), case in zip(rows, M.CASES):
+        want_c, want_l = M.pack(M.oracle_frame(case[0])[0], *case[1:])
+        assert coords == want_c.tolist() and labels == want_l.tolist(), M.case_id(case)
+    assert any(c != [list(map(float, xy)) for xy in case[1]] + c[len(case[1]):] for (_, c, _), case in zip(rows, M.CASES)
+               if case[0] == "wide")         # the image whose longest side is not 1024 is scaled
+
+
+def test_library_packs_the_single_prompt_forms_as_the_oracle_does(plan):
+    """A point, a box, a box and a point, on both images: oracle.sam_oracle.pack_prompt and box_point_cases.prompts."""
+    import box_point_cases as B
+    for name, box, point in B.PAIRS:
+        rs, extent = M.oracle_frame(name)
+        want, _ = B.prompts(rs, box, point)
+        entry = f"h0:{','.join(map(str, box))}@{point[0]},{point[1]}@{extent}"
+        for kind, given in (("point", dict(regions=False)), ("box", dict(points=False)), ("both", {})):
+            rows = M.packed_lines(plan([entry], **given))
+            assert len(rows) == 1 and rows[0][0] == [0]
+            assert rows[0][1] == want[kind][0].tolist() and rows[0][2] == want[kind][1].tolist(), (name, kind)
+    assert {p[0] for p in B.PAIRS} == set(M.IMAGES)

@@ -160,7 +160,8 @@ def _build(tmp, name, source, sanitize, extra=()):
 
 def test_lane_worker_and_its_hand_over_protocols_under_thread_sanitizer(tmp_path):
     """csrc/lane_worker.hpp (the lanes' enqueue threads) under ThreadSanitizer: posts from several threads beside drains,
-    the step queue's ticket protocol, the batch call's shared promise (tests/sanitize/lane_worker_tsan.cpp)."""
+    the step queue's ticket protocol, the batch calls' hand-over (post_with_result / wait_for_all, tasks that throw included)
+    (tests/sanitize/lane_worker_tsan.cpp)."""
     exe = _build(tmp_path, "lane_worker_tsan", "lane_worker_tsan.cpp", "thread")
     r = subprocess.run([str(exe)], capture_output=True, text=True, errors="replace", timeout=600, env={"TSAN_OPTIONS": "halt_on_error=1"})
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (r.stdout[-1000:], r.stderr[-4000:])
@@ -170,8 +171,9 @@ def test_lane_worker_and_its_hand_over_protocols_under_thread_sanitizer(tmp_path
 def test_planners_on_random_inputs_under_address_sanitizer(tmp_path):
     """csrc/step_queue.hpp and csrc/mask_pieces.hpp on 220 000 random inputs, csrc/mask_transport.hpp on 30 000 requests of
     1 to 33 masks (both forms), csrc/resize_tables.cpp on 1 500 axis pairs
-    (1 pixel to 40 000, both filters) and csrc/gemm_plan.cpp on 100 000 random GEMM problems with ASan + UBSan, every result
-    checked against the invariants its caller relies on (tests/sanitize/planners_fuzz.cpp)."""
+    (1 pixel to 40 000, both filters), csrc/gemm_plan.cpp on 100 000 random GEMM problems and csrc/prompt_plan.hpp on 100 000
+    random batch mask calls (prompts, stages, and pack_points into buffers of exactly the points of each stage) with ASan +
+    UBSan, every result checked against the invariants its caller relies on (tests/sanitize/planners_fuzz.cpp)."""
     csrc = ROOT / "dlimgedit_amd" / "csrc"
     exe = _build(tmp_path, "planners_fuzz", "planners_fuzz.cpp", "address,undefined",
                  extra=["-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", str(csrc / "resize_tables.cpp"),
