@@ -155,6 +155,36 @@ def hooks_library() -> C.CDLL:
     return _hooks_lib
 
 
+_neck_hooks_lib = None
+NECK_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_neck_test.so")
+# the hooks of the two encoder-neck launches (csrc/neck_test_hooks.cpp): bound by name, no header declares them
+NECK_HOOK_EXPORTS = ("dlimg_amd_test_neck_conv1x1_ln", "dlimg_amd_test_neck_conv3x3_ln")
+
+
+def neck_hooks_library() -> C.CDLL:
+    """Loads lib/libdlimgedit_neck_test.so: the product's objects plus the hooks of the two encoder-neck launches.  Raises if
+    it has not been built; there is no fallback."""
+    global _neck_hooks_lib
+    if _neck_hooks_lib is None:
+        if not NECK_HOOKS_LIB_PATH.exists():
+            raise Error(f"{NECK_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+        lib = C.CDLL(str(NECK_HOOKS_LIB_PATH))
+        lib.dlimg_init.restype = C.POINTER(_Api)
+        lib.dlimg_init.argtypes = []
+        vp, ci, cf = C.c_void_p, C.c_int, C.c_float
+        lib.dlimg_amd_test_neck_conv1x1_ln.argtypes = [vp, ci, ci, vp, vp, vp, cf, vp, vp, vp, C.POINTER(ci)]
+        lib.dlimg_amd_test_neck_conv3x3_ln.argtypes = [vp, ci, vp, vp, vp, cf, vp, vp, vp, C.POINTER(ci)]
+        lib.dlimg_amd_test_neck_conv1x1_ln.restype = lib.dlimg_amd_test_neck_conv3x3_ln.restype = ci
+        _neck_hooks_lib = lib
+    return _neck_hooks_lib
+
+
+def _check_neck_hook(result: int) -> None:
+    if result != 0:
+        msg = neck_hooks_library().dlimg_init().contents.last_error()
+        raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+
+
 def _check_hook(result: int) -> None:
     """As _check, with the message of the library the hook lives in (last_error is per library and per thread)."""
     if result != 0:
@@ -1011,6 +1041,73 @@ class ext:
         _check_hook(cls._h().dlimg_amd_test_layernorm(x.ctypes.data, w.ctypes.data, b.ctypes.data, eps, rows, dim, act,
                                                  o32.ctypes.data, o16.ctypes.data))
         return o32, o16
+
+    NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
+    NECK_GUARD_BYTE = 0xA5
+
+    @classmethod
+    def test_neck_conv_ln(cls, env: Environment, x, w, gamma, beta, eps: float, want_f16: bool = True, want_f32: bool = True,
+                          own_buffer=None):
+        """One launch of the encoder neck on device buffers (the hooks of neck_hooks_library()): convolution +
+        LayerNorm2d.  x: f16 [B*4096][K] with w [256][K] (1x1), or f16 [B][64][64][256] with w [256][2304] (3x3, zero pad 1,
+        columns (ky*3+kx)*256 + c).  own_buffer (optional, one bool per image): image i's fp32 result goes to a device buffer
+        of its own with NECK_GUARD bytes of NECK_GUARD_BYTE on either side, the others to the shared workspace.
+        Returns (f16 [B*4096][256] or None, fp32 [B*4096][256] or None, flag, guards) -- guards: per image with a buffer of
+        its own the (front, back) guard bytes as they are after the launch, else None."""
+        x = np.ascontiguousarray(x, dtype=np.float16)
+        w = np.ascontiguousarray(w, dtype=np.float16)
+        gamma = np.ascontiguousarray(gamma, dtype=np.float32)
+        beta = np.ascontiguousarray(beta, dtype=np.float32)
+        conv3 = x.ndim == 4
+        B = x.shape[0] if conv3 else x.shape[0] // 4096
+        K = 2304 if conv3 else x.shape[1]
+        assert x.size == B * 4096 * (256 if conv3 else K) and w.shape == (256, K) and gamma.shape == beta.shape == (256,)
+        own = [False] * B if own_buffer is None else [bool(o) for o in own_buffer]
+        assert len(own) == B and (want_f32 or not any(own))
+        img_bytes, G = 4096 * 256 * 4, cls.NECK_GUARD
+        held = []
+
+        def dev(a=None, nbytes=0):
+            ptr = cls.device_alloc(env, a.nbytes if a is not None else nbytes)
+            held.append(ptr)
+            if a is not None:
+                cls.copy_to_device(env, ptr, a)
+            return ptr
+
+        try:
+            d_x, d_w, d_g, d_b = dev(x), dev(w), dev(gamma), dev(beta)
+            d_h = dev(nbytes=B * 4096 * 256 * 2) if want_f16 else None
+            d_ws = dev(nbytes=B * img_bytes) if want_f32 else None
+            ptrs = (C.c_void_p * B)()
+            fill = np.full(img_bytes + 2 * G, cls.NECK_GUARD_BYTE, np.uint8)
+            for i in range(B):
+                ptrs[i] = dev(fill) + G if own[i] else None
+            flag = C.c_int(-1)
+            h = neck_hooks_library()
+            if conv3:
+                rc = h.dlimg_amd_test_neck_conv3x3_ln(d_x, B, d_w, d_g, d_b, eps, d_h, ptrs if any(own) else None, d_ws, C.byref(flag))
+            else:
+                rc = h.dlimg_amd_test_neck_conv1x1_ln(d_x, B, K, d_w, d_g, d_b, eps, d_h, ptrs if any(own) else None, d_ws,
+                                                      C.byref(flag))
+            _check_neck_hook(rc)
+            out16 = out32 = None
+            guards = [None] * B
+            if want_f16:
+                out16 = np.empty((B * 4096, 256), np.float16)
+                cls.copy_to_host(env, out16, d_h)
+            if want_f32:
+                out32 = np.empty((B * 4096, 256), np.float32)
+                cls.copy_to_host(env, out32, d_ws)
+                for i in range(B):
+                    if own[i]:
+                        whole = np.empty(img_bytes + 2 * G, np.uint8)
+                        cls.copy_to_host(env, whole, ptrs[i] - G)
+                        guards[i] = (whole[:G].copy(), whole[-G:].copy())
+                        out32[i * 4096:(i + 1) * 4096] = whole[G:-G].view(np.float32).reshape(4096, 256)
+            return out16, out32, flag.value, guards
+        finally:
+            for ptr in held:
+                cls.device_free(env, ptr)
 
     @classmethod
     def test_attention(cls, is_global: bool, qkv, qkv_bias, rel_h, rel_w, batch: int, heads: int, hd: int):

@@ -29,6 +29,7 @@
 #include <hip/hip_ext.h>
 
 #include <mutex>
+#include <string>
 #include <cstdlib>
 #include <type_traits>
 
@@ -70,6 +71,10 @@ constexpr bool kNoStreamStore = false;
 #endif
 
 #include "gemm_f16_tile.inc"
+
+// Fourth epilogue flavour, ping-pong 64 x 256 tiles only (the neck launches, k::neck_conv1x1_ln / neck_conv3x3_ln):
+// LayerNorm2d over the tile's 256 columns, which are the whole output row
+constexpr int EPI_LN2D = 3;
 
 typedef float float4v __attribute__((ext_vector_type(4)));
 
@@ -359,6 +364,11 @@ struct PPAux {
     // 128 h .. of group g's partials (GP pieces of 1 KB per group; a 64-row tile has half a piece per group)
     static constexpr int GP = BM * 8 > 1024 ? BM * 8 / 1024 : 1;
     static DLIMG_DEVICE void issue(const k::GemmArgs& a, int m0, int n0, float* colvec, float2_t* raw, int wave, int lane) {
+        if (EPI == EPI_LN2D) {                   // LayerNorm2d scale and shift in the places of bias and column sums
+            if (wave == 0) glds16(a.ln2d_w + lane * 4, colvec);
+            if (wave == 1) glds16(a.ln2d_b + lane * 4, colvec + BN);
+            return;
+        }
         if (wave == 0) {
             if (a.bias) glds16(a.bias + n0 + lane * 4, colvec);
             else *reinterpret_cast<float4_t*>(colvec + lane * 4) = float4_t{0.f, 0.f, 0.f, 0.f};
@@ -397,6 +407,82 @@ struct PPAux {
     }
 };
 
+// EPI_LN2D (64 x 256 tiles, N = 256: the tile holds whole output rows).  The wave's bands go through its fp32 slabs as in the
+// stream writers' epilogue and come back with a row's 64 columns in 8 adjacent lanes; (sum, squared deviations from the
+// group mean) per 64-column group are EPI_STATS's arithmetic (taken from the group mean because trained models have single
+// channels hundreds of times larger than the rest), the four groups of a row meet in rowpart and are merged (Chan et al.) by
+// every lane that holds a piece of the row.  The values stay in registers across the one workgroup barrier between the two.
+template <int NI>
+DLIMG_DEVICE void pp_epilogue_ln2d(const k::GemmArgs& a, float4v (&acc)[NI][4], char* smem, const float* colvec,
+                                   float2_t* rowpart, int m0, int row_base, int wc, int wave, int lane) {
+    constexpr int BN = 256;
+    const int l15 = lane & 15, quad = lane >> 4;
+    const int rd_row = lane >> 3, rd_col = (lane & 7) * 8;
+    char* slab = smem + wave * 8192;
+    float4_t v[NI][2][2];
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+        char* sl = slab + (i & 1) * 4096;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            *reinterpret_cast<float4_t*>(sl + l15 * 256 + (((j * 4 + quad) ^ (l15 & 7)) << 4)) =
+                float4_t{acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int r = kk * 8 + rd_row;
+            const int slot = (lane & 7) * 2;
+            const float4_t v0 = *reinterpret_cast<const float4_t*>(sl + r * 256 + ((slot ^ (r & 7)) << 4));
+            const float4_t v1 = *reinterpret_cast<const float4_t*>(sl + r * 256 + (((slot + 1) ^ (r & 7)) << 4));
+            float s1 = ((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]));
+            s1 = sum_over_8_lanes(s1);
+            const float4_t d0 = v0 - s1 * (1.0f / 64.0f), d1 = v1 - s1 * (1.0f / 64.0f);
+            float m2 = ((d0[0] * d0[0] + d0[1] * d0[1]) + (d0[2] * d0[2] + d0[3] * d0[3])) +
+                       ((d1[0] * d1[0] + d1[1] * d1[1]) + (d1[2] * d1[2] + d1[3] * d1[3]));
+            m2 = sum_over_8_lanes(m2);
+            if ((lane & 7) == 0) rowpart[(row_base + i * 16 + r) * 4 + wc] = float2_t{s1, m2};
+            v[i][kk][0] = v0;
+            v[i][kk][1] = v1;
+        }
+    }
+    __syncthreads();
+    const int col = wc * 64 + rd_col;
+    const float4_t g0 = *reinterpret_cast<const float4_t*>(colvec + col), g1 = *reinterpret_cast<const float4_t*>(colvec + col + 4);
+    const float4_t b0 = *reinterpret_cast<const float4_t*>(colvec + BN + col);
+    const float4_t b1 = *reinterpret_cast<const float4_t*>(colvec + BN + col + 4);
+    float* const out32 = a.out_img[m0 >> 12];    // a tile lies inside one image (64 of its 4096 rows)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+            const int r = row_base + i * 16 + kk * 8 + rd_row;
+            float s1 = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) s1 += rowpart[r * 4 + g][0];
+            const float mean = s1 * (1.0f / (float)BN);
+            float m2 = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float dm = rowpart[r * 4 + g][0] * (1.0f / 64.0f) - mean;
+                m2 += rowpart[r * 4 + g][1] + 64.0f * dm * dm;
+            }
+            const float rstd = 1.0f / sqrtf(m2 * (1.0f / (float)BN) + a.ln_eps);
+            // a row that holds an infinity or a NaN has no finite statistics: reported as layernorm_vec_kernel reports it
+            if (a.nonfinite && wc == 0 && (lane & 7) == 0 && !(fabsf(mean) < INFINITY && fabsf(rstd) < INFINITY)) *a.nonfinite = 1;
+            const float4_t y0 = (v[i][kk][0] - mean) * rstd * g0 + b0, y1 = (v[i][kk][1] - mean) * rstd * g1 + b1;
+            const size_t m = (size_t)(m0 + r);
+            if (out32) {
+                store16_result(out32 + (m & 4095) * BN + col, y0);
+                store16_result(out32 + (m & 4095) * BN + col + 4, y1);
+            }
+            if (a.out_h) {
+                const half8_t h = {(half_t)y0[0], (half_t)y0[1], (half_t)y0[2], (half_t)y0[3],
+                                   (half_t)y1[0], (half_t)y1[1], (half_t)y1[2], (half_t)y1[3]};
+                store16_result(a.out_h + m * a.ldc16 + col, h);
+            }
+        }
+}
+
 // Epilogue of the ping-pong kernels: the wave's (NI * 16) x 64 part of the tile, rows row_base .. of the workgroup's tile.
 // PRE: the residual of the whole wave tile was requested before the main loop (pre[band][kk]; only where the
 // registers allow it) -- the epilogue is bound by the CU's memory pipe (~30 B/clk: 320 KB per 128 x 256 tile of a
@@ -413,6 +499,10 @@ DLIMG_DEVICE void pp_epilogue(const k::GemmArgs& a, float4v (&acc)[NI][4], char*
     //   fp32 output (residual stream writers): fp32 slab rows of 256 B, 16 lanes per row; residual, both outputs and
     //   the row statistics after the read-back, where a row's 64 columns sit in 16 adjacent lanes (DPP row)
     constexpr int BN = 256;
+    if constexpr (EPI == EPI_LN2D) {
+        pp_epilogue_ln2d<NI>(a, acc, smem, colvec, rowpart, m0, row_base, wc, wave, lane);
+        return;
+    }
     const int l15 = lane & 15, quad = lane >> 4;
     const int col_base = wc * 64 + quad * 4;
     float4_t bias4[4], csum4[4];
@@ -770,9 +860,15 @@ constexpr int pp128_operands(int bm) { return 3 * pp128_a_bytes(bm) + 3 * 2 * kP
 constexpr int pp128_lds(int bm) { return pp128_operands(bm) + pp_aux_bytes(bm); }
 static_assert(pp128_lds(128) <= 160 * 1024 && pp128_lds(64) <= 160 * 1024, "gemm_pp128_kernel: LDS");
 
-template <int BM, int ACT, int EPI>
+// CONV3 (the neck's 3x3 convolution, BM = 64, A = the f16 map [B * 4096][256]): the A operand is the im2col matrix without
+// that matrix existing.  K = 9 * 256, K tile t = tap t / 4 (ky * 3 + kx), channels 64 (t % 4) ..: a lane's source row for tap
+// (dy, dx) is row token + 64 dy + dx of the map where (y + dy, x + dx) lies inside the token's own image, and a line of zeros
+// (GemmArgs::zeros) elsewhere.  The source is SELECTED, the request itself is unconditional, like the pad slots of
+// attention_window.hip: a branch around a DMA request would drain the memory counter where it joins.
+template <int BM, int ACT, int EPI, bool CONV3 = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp128_kernel(k::GemmArgs a) {
     static_assert(BM == 128 || BM == 64, "128 or 64 rows per tile");
+    static_assert((EPI != EPI_LN2D && !CONV3) || BM == 64, "the neck flavours exist for 64-row tiles");
     constexpr int BN = 256;
     constexpr int NI = BM / 32;                  // 16-row accumulator tiles per wave (the group's BM / 2 rows)
     constexpr int APIECES = BM / 64;             // DMA wave-instructions per wave for one A tile (8 rows each)
@@ -814,8 +910,27 @@ __global__ __launch_bounds__(512, 2) void gemm_pp128_kernel(k::GemmArgs a) {
         src_a[q] = a.A + (size_t)(m0 + row) * a.lda + chunk * 8;
     }
     const size_t w_half = (size_t)128 * a.ldw;
+    unsigned tap_ok = 0;                         // CONV3: bit tap = the lane's source row for that tap lies inside its image
+    const half_t* zero_src = nullptr;
+    if (CONV3) {
+        const int token = m0 + wave * 8 + (lane >> 3);
+        const int y = (token >> 6) & 63, x = token & 63;
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap)
+            if ((unsigned)(y + tap / 3 - 1) < 64u && (unsigned)(x + tap % 3 - 1) < 64u) tap_ok |= 1u << tap;
+        zero_src = a.zeros + (lane & 7) * 8;
+    }
     auto stage_a = [&](int t, int abuf) {
         char* dst = smem + abuf * pp128_a_bytes(BM) + wave * (APIECES * 1024);
+        if (CONV3) {
+            const int tap = t >> 2;
+            const int shift = ((tap / 3 - 1) * 64 + (tap % 3 - 1)) * 256 + (t & 3) * 64;      // halves, wave-uniform
+            // (the shift is masked, not selected: hipcc turns "ok ? base + shift : zeros" into a branch around the
+            // address arithmetic)
+            const int ok = -(int)((tap_ok >> tap) & 1u);                                      // all ones / zero
+            glds16((ok ? src_a[0] : zero_src) + (shift & ok), dst);
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < APIECES; ++q) glds16(src_a[q] + (size_t)t * 64, dst + q * 1024);
     };
@@ -1018,6 +1133,19 @@ void launch_pp(const k::GemmArgs& a, hipStream_t s, Timing t) {
     launch_tile<TILE>(kernels, attr_once, a, s, t);
 }
 
+// The neck launches: 64 x 256 tiles, LayerNorm2d epilogue, plain or implicit-3x3 A operand.  Not a row of k::kGemmTiles:
+// the tile is fixed, the planner never sees these.
+template <bool CONV3>
+void launch_neck(const k::GemmArgs& a, hipStream_t s, Timing t) {
+    static k::LdsOptIn attr_once;
+    const GemmKernel kernel = gemm_pp128_kernel<64, k::ACT_NONE, EPI_LN2D, CONV3>;
+    attr_once.ensure((const void*)kernel, pp128_lds(64), "neck convolution: the device refuses the LDS size of its tile");
+    if (t.start || t.stop)
+        hipExtLaunchKernelGGL(kernel, dim3(a.M / 64), dim3(512), pp128_lds(64), s, t.start, t.stop, 0, a);
+    else
+        hipLaunchKernelGGL(kernel, dim3(a.M / 64), dim3(512), pp128_lds(64), s, a);
+}
+
 template <int TILE, int BM>
 void launch_pp128(const k::GemmArgs& a, hipStream_t s, Timing t) {
     static_assert(tile_row_is<TILE>(BM, 256, 512, pp128_lds(BM), k::TileFamily::pingpong, kPPStatGroups), "gemm_pp128_kernel: the kernel and its row of k::kGemmTiles disagree");
@@ -1047,6 +1175,49 @@ void gemm(const GemmArgs& a, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
     const int tile = gemm_pick_tile(a);          // fits the problem (gemm_plan.cpp), or -1
     if (tile < 0) gemm_no_tile(a);
     kLaunchers[tile](a, s, Timing{start, stop});
+}
+
+namespace {
+// up to 8 images per launch (GemmArgs::out_img); the first launch carries the start event, the last one the stop event
+template <bool CONV3>
+void neck_launches(GemmArgs g, int B, const NeckOutputs& out, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    const half_t* in = g.A;
+    for (int base = 0; base < B; base += 8) {
+        const int n = B - base < 8 ? B - base : 8;
+        g.A = in + (size_t)base * 4096 * g.lda;
+        g.M = n * 4096;
+        g.out_h = out.out_h ? out.out_h + (size_t)base * 4096 * 256 : nullptr;
+        for (int i = 0; i < 8; ++i) g.out_img[i] = (out.out_f32 && i < n) ? out.out_f32[base + i] : nullptr;
+        launch_neck<CONV3>(g, s, Timing{base == 0 ? start : nullptr, base + 8 >= B ? stop : nullptr});
+    }
+}
+GemmArgs neck_args(const char* who, const half_t* in, int B, int K, const half_t* w, const float* gamma, const float* beta,
+                   float eps, const NeckOutputs& out) {
+    if (B <= 0 || K < 64 || K % 64) throw_error((std::string(who) + ": needs at least one image and K a multiple of 64").c_str());
+    if (!in || !w || !gamma || !beta) throw_error((std::string(who) + ": null operand").c_str());
+    uintptr_t bits = (uintptr_t)in | (uintptr_t)w | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)out.out_h;
+    for (int i = 0; out.out_f32 && i < B; ++i) bits |= (uintptr_t)out.out_f32[i];
+    if (bits & 15) throw_error((std::string(who) + ": operands and results must be 16-byte aligned").c_str());
+    GemmArgs g;
+    g.A = in; g.W = w; g.ldw = K; g.N = 256; g.K = K; g.ldc16 = 256;
+    g.ln2d_w = gamma; g.ln2d_b = beta; g.ln_eps = eps; g.nonfinite = out.nonfinite;
+    return g;
+}
+}  // namespace
+
+void neck_conv1x1_ln(const half_t* in, int B, int K, const half_t* w, const float* gamma, const float* beta, float eps,
+                     const NeckOutputs& out, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    GemmArgs g = neck_args("neck_conv1x1_ln", in, B, K, w, gamma, beta, eps, out);
+    g.lda = K;
+    neck_launches<false>(g, B, out, s, start, stop);
+}
+
+void neck_conv3x3_ln(const half_t* in, int B, const half_t* w, const half_t* zeros, const float* gamma, const float* beta,
+                     float eps, const NeckOutputs& out, hipStream_t s, hipEvent_t start, hipEvent_t stop) {
+    GemmArgs g = neck_args("neck_conv3x3_ln", in, B, 9 * 256, w, gamma, beta, eps, out);
+    if (!zeros || ((uintptr_t)zeros & 15)) throw_error("neck_conv3x3_ln: needs a 16-byte aligned line of zeros");
+    g.lda = 256; g.zeros = zeros;
+    neck_launches<true>(g, B, out, s, start, stop);
 }
 
 }  // namespace k

@@ -83,6 +83,15 @@ struct GemmArgs {
     // Diagnostics (tuning builds of the benchmark hook only; null in the product): per workgroup 4 x u64 =
     // { shader cycles, 100 MHz ticks } of the main loop and of the whole kernel, written by wave 0.
     unsigned long long* stamps = nullptr;
+    // The neck launches only (neck_conv1x1_ln / neck_conv3x3_ln below; k::gemm ignores them): LayerNorm2d scale and shift
+    // [256] applied in the epilogue (eps in ln_eps), the fp32 result per image (entry i: rows 4096 i .. of the launch, or null),
+    // the host-visible non-finite report, and the 128-byte line of zeros the implicit 3x3 operand reads for taps outside
+    // the image.
+    const float* ln2d_w = nullptr;
+    const float* ln2d_b = nullptr;
+    float* out_img[8] = {};
+    int* nonfinite = nullptr;
+    const half_t* zeros = nullptr;
 };
 const char* gemm_check(const GemmArgs&);
 bool gemm_tile_fits(const GemmArgs&, int tile);   // may `tile` (index into k::kGemmTiles, gemm_plan.hpp) run this problem?
@@ -91,6 +100,25 @@ int gemm_choose_tile(GemmArgs&);              // sets a.tile; returns BN (column
 // start/stop (both or neither): events attached to the kernel's own dispatch (hipExtLaunchKernelGGL): their elapsed time
 // is the kernel's execution time as a profiler reports it, without the marker packets an hipEventRecord pair adds.
 void gemm(const GemmArgs&, hipStream_t, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+
+// ---- encoder neck: convolution + LayerNorm2d in one launch -------------------------------------
+// Both neck convolutions have 256 output channels, one column tile of the ping-pong kernels, so a whole output row lies in
+// one workgroup and LayerNorm2d over the channels is an epilogue: y = gamma (v - mean) rstd + beta with the row statistics of
+// the fp32 accumulators.  Fixed 64 x 256 tiles whatever the batch (B * 64 workgroups, no planner): a batch computes the bits of
+// its images one at a time.  No bias (the neck's convolutions have none).
+struct NeckOutputs {
+    half_t* out_h = nullptr;             // [B * 4096][256] f16, or null
+    float* const* out_f32 = nullptr;     // HOST array of B device pointers, [4096][256] fp32 per image (null entries: not
+                                         // written), or null
+    int* nonfinite = nullptr;            // as layernorm(): set to 1 when a row's statistics are not finite
+};
+// 1x1: in [B * 4096][K] f16 (K a multiple of 64), w [256][K] f16
+void neck_conv1x1_ln(const half_t* in, int B, int K, const half_t* w, const float* gamma, const float* beta, float eps,
+                     const NeckOutputs& out, hipStream_t, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// 3x3, zero pad 1, over the f16 map in [B][64][64][256]; w [256][9 * 256] f16, column = (ky * 3 + kx) * 256 + c (im2col3x3's
+// order).  The A operand is read straight from the map: no im2col matrix.  zeros: 128 bytes of zeros, 16-byte aligned.
+void neck_conv3x3_ln(const half_t* in, int B, const half_t* w, const half_t* zeros, const float* gamma, const float* beta,
+                     float eps, const NeckOutputs& out, hipStream_t, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 // ---- row LayerNorm ---------------------------------------------------------------------------
 // y = (x-mean)/sqrt(var+eps)*w+b over rows of length D (<= 1280); optional GELU; f32 and/or f16 out.

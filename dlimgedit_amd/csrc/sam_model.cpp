@@ -85,6 +85,17 @@ void SamModel::gemm(k::GemmArgs const& args, Stage shape) {
     clock_.add(p);
 }
 
+// A neck launch, clocked like a GEMM of the "other" flavour (events attached to its dispatch)
+template <typename F> void SamModel::neck_launch(double flops, F&& launch) {
+    if (!clock_.profiling()) {
+        launch(nullptr, nullptr);
+        return;
+    }
+    const StageClock::Pending p = clock_.event_pair(ST_GEMM, flops, ST_GEMM_OTHER);
+    launch(p.a, p.b);
+    clock_.add(p);
+}
+
 void SamModel::synchronize() { HIP_CHECK(hipStreamSynchronize(stream_)); }
 
 std::shared_ptr<SamModel::DeferredPass> SamModel::defer_last_pass() {
@@ -128,7 +139,7 @@ void SamModel::reserve_encoder(int batch) {
     qkv_.reserve(M * 3 * D);
     att_.reserve(M * std::max<size_t>(D, kEmbedDim));
     hid_.reserve(M * wide);
-    neck_f32_.reserve(M * kEmbedDim);
+    if (!W.fused_ln_) neck_f32_.reserve(M * kEmbedDim);
     emb_.reserve(M * kEmbedDim);
     if (W.has_hq()) {
         hq_a_.reserve(M * 4 * kEmbedDim);
@@ -483,31 +494,9 @@ void SamModel::encode(int batch, float* const* emb_dst) {
         ++layer_index;
     }
 
-    // neck: 1x1 conv -> LayerNorm2d -> 3x3 conv (pad 1) -> LayerNorm2d, all channel-last
-    if (!fused) {
-        clock_.timed(ST_ENC_OTHER, (double)M * D * 6, [&] {
-            k::add_cast(x_.get(), nullptr, 0, (size_t)M * D, nullptr, xn_.get(), stream_);
-        });
-    }
-    g = k::GemmArgs{};
-    g.A = xn_.get(); g.lda = D; g.W = W.neck1_.w.get(); g.ldw = D;
-    g.out_f32 = neck_f32_.get(); g.ldc32 = kEmbedDim; g.M = M; g.N = kEmbedDim; g.K = D;
-    gemm(g);
-    clock_.timed(ST_LAYERNORM, (double)M * kEmbedDim * 6, [&] {
-        k::layernorm(neck_f32_.get(), W.neck_ln1_.w.get(), W.neck_ln1_.b.get(), kLnEps, M, kEmbedDim, k::ACT_NONE, nullptr,
-                     att_.get(), stream_);
-    });
-    clock_.timed(ST_ENC_OTHER, (double)M * kEmbedDim * 2 * 10, [&] {
-        k::im2col3x3(att_.get(), batch, kEmbedDim, hid_.get(), stream_);
-    });
-    g = k::GemmArgs{};
-    g.A = hid_.get(); g.lda = 9 * kEmbedDim; g.W = W.neck2_.w.get(); g.ldw = 9 * kEmbedDim;
-    g.out_f32 = neck_f32_.get(); g.ldc32 = kEmbedDim; g.M = M; g.N = kEmbedDim; g.K = 9 * kEmbedDim;
-    gemm(g);
-    // the embedding goes straight into the handle's storage when there is one image; a batch is copied out per image
-    float* direct = (emb_dst && batch == 1 && emb_dst[0]) ? emb_dst[0] : nullptr;
+    // neck: 1x1 conv -> LayerNorm2d -> 3x3 conv (pad 1) -> LayerNorm2d, all channel-last.
     // f16 operands and the f16 residual pair overflow to infinity beyond 65504; an infinity anywhere in an image turns
-    // into NaNs that reach this LayerNorm's input, which reports it (last_pass_flag) so that the caller refuses the
+    // into NaNs that reach the last LayerNorm's input, which reports it (last_pass_flag) so that the caller refuses the
     // embedding instead of decoding masks from it
     if (!pass_flags_) {
         HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&pass_flags_), kPassFlags * sizeof(int), hipHostMallocDefault));
@@ -520,10 +509,49 @@ void SamModel::encode(int batch, float* const* emb_dst) {
     }
     pass_flag_ = pass_flags_ + flag_slot;
     *pass_flag_ = 0;
-    clock_.timed(ST_LAYERNORM, (double)M * kEmbedDim * 8, [&] {
-        k::layernorm(neck_f32_.get(), W.neck_ln2_.w.get(), W.neck_ln2_.b.get(), kLnEps, M, kEmbedDim, k::ACT_NONE,
-                     direct ? direct : emb_.get(), W.has_hq() ? emb_h_.get() : nullptr, stream_, pass_flag_);
-    });
+    // the embedding goes straight into the handle's storage where there is one; the unfused path copies a batch out per image
+    float* direct = (emb_dst && batch == 1 && emb_dst[0]) ? emb_dst[0] : nullptr;
+    if (fused) {
+        // Two launches (kernels.hpp, neck_conv*_ln): each convolution with its LayerNorm2d as the epilogue, the 3x3 one
+        // reading its operand straight from the f16 map.  No fp32 intermediate, no im2col matrix, no copy per image.
+        std::vector<float*> dst(batch);
+        for (int i = 0; i < batch; ++i)
+            dst[i] = (emb_dst && emb_dst[i]) ? emb_dst[i] : emb_.get() + (size_t)i * kEmbeddingFloats;
+        k::NeckOutputs map, emb;
+        map.out_h = att_.get();
+        emb.out_f32 = dst.data(); emb.out_h = W.has_hq() ? emb_h_.get() : nullptr; emb.nonfinite = pass_flag_;
+        neck_launch(2.0 * M * kEmbedDim * D, [&](hipEvent_t a, hipEvent_t b) {
+            k::neck_conv1x1_ln(xn_.get(), batch, D, W.neck1_.w.get(), W.neck_ln1_.w.get(), W.neck_ln1_.b.get(), kLnEps, map,
+                               stream_, a, b);
+        });
+        neck_launch(2.0 * M * kEmbedDim * 9 * kEmbedDim, [&](hipEvent_t a, hipEvent_t b) {
+            k::neck_conv3x3_ln(att_.get(), batch, W.neck2_.w.get(), W.zero_line_.get(), W.neck_ln2_.w.get(), W.neck_ln2_.b.get(),
+                               kLnEps, emb, stream_, a, b);
+        });
+    } else {
+        clock_.timed(ST_ENC_OTHER, (double)M * D * 6, [&] {
+            k::add_cast(x_.get(), nullptr, 0, (size_t)M * D, nullptr, xn_.get(), stream_);
+        });
+        g = k::GemmArgs{};
+        g.A = xn_.get(); g.lda = D; g.W = W.neck1_.w.get(); g.ldw = D;
+        g.out_f32 = neck_f32_.get(); g.ldc32 = kEmbedDim; g.M = M; g.N = kEmbedDim; g.K = D;
+        gemm(g);
+        clock_.timed(ST_LAYERNORM, (double)M * kEmbedDim * 6, [&] {
+            k::layernorm(neck_f32_.get(), W.neck_ln1_.w.get(), W.neck_ln1_.b.get(), kLnEps, M, kEmbedDim, k::ACT_NONE, nullptr,
+                         att_.get(), stream_);
+        });
+        clock_.timed(ST_ENC_OTHER, (double)M * kEmbedDim * 2 * 10, [&] {
+            k::im2col3x3(att_.get(), batch, kEmbedDim, hid_.get(), stream_);
+        });
+        g = k::GemmArgs{};
+        g.A = hid_.get(); g.lda = 9 * kEmbedDim; g.W = W.neck2_.w.get(); g.ldw = 9 * kEmbedDim;
+        g.out_f32 = neck_f32_.get(); g.ldc32 = kEmbedDim; g.M = M; g.N = kEmbedDim; g.K = 9 * kEmbedDim;
+        gemm(g);
+        clock_.timed(ST_LAYERNORM, (double)M * kEmbedDim * 8, [&] {
+            k::layernorm(neck_f32_.get(), W.neck_ln2_.w.get(), W.neck_ln2_.b.get(), kLnEps, M, kEmbedDim, k::ACT_NONE,
+                         direct ? direct : emb_.get(), W.has_hq() ? emb_h_.get() : nullptr, stream_, pass_flag_);
+        });
+    }
     if (W.has_hq()) {
         // the embedding branch of the HQ features, then per image: both branches and their biases, in raster order, behind
         // the embedding in the handle's buffer (or in the lane's workspace when the pass has no handle)
@@ -536,7 +564,7 @@ void SamModel::encode(int batch, float* const* emb_dst) {
             }
         });
     }
-    if (emb_dst && !direct) {
+    if (emb_dst && !direct && !fused) {
         const size_t n = (size_t)kTokens * kEmbedDim;
         for (int i = 0; i < batch; ++i)
             if (emb_dst[i])

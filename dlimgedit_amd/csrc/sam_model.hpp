@@ -85,6 +85,7 @@ struct SamWeights {
     std::vector<EncoderLayer> layers_;
     LinearH neck1_, neck2_;               // 1x1 conv [256, D]; 3x3 conv as [256, 9*256] (tap-major columns)
     NormW neck_ln1_, neck_ln2_;
+    DeviceBuffer<half_t> zero_line_;      // 128 bytes of zeros: the padding the implicit 3x3 operand reads
     DeviceBuffer<float> pe_gauss_, pe_point_, pe_not_a_point_, pe_no_mask_;
     k::PromptEncoderWeights prompt_encoder() const {
         return k::PromptEncoderWeights{pe_gauss_.get(), pe_point_.get(), pe_not_a_point_.get(), iou_token_.get(), mask_tokens_.get()};
@@ -179,10 +180,10 @@ class SamModel {
     // extent image i is encoded at (ResizeLongestSide); an image already of that extent takes the pre-processing launch,
     // the others are resampled on the way by the fused resize: one launch per stage for all of them.
     void preprocess_device_images(dlimg_ImageView const* views, int const* resized_wh, int batch);
-    // Runs the encoder on `batch` uploaded images; embeddings [batch][4096][256] fp32 in embeddings() and, where
-    // emb_dst[i] is given, in that device buffer too (batch 1: written there directly).  A SAM-HQ model also leaves every
-    // image's HQ features: behind the embedding in emb_dst[i] (a buffer of handle_floats(true) floats), else in a
-    // workspace of the lane.
+    // Runs the encoder on `batch` uploaded images; embedding i [4096][256] fp32 in emb_dst[i] where that is given, else at
+    // embeddings() + i * 4096 * 256 (DLIMGEDIT_FUSED_LN=0: there in any case, and copied to emb_dst[i]).  A SAM-HQ model
+    // also leaves every image's HQ features: behind the embedding in emb_dst[i] (a buffer of handle_floats(true) floats),
+    // else in a workspace of the lane.
     void encode(int batch, float* const* emb_dst = nullptr);
     bool has_hq() const { return weights_->has_hq_; }                          // no mutex needed
     float const* embeddings() const { return emb_.get(); }
@@ -273,6 +274,7 @@ class SamModel {
                       k::MaskSource const* mask_input);
     void hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
+    template <typename F> void neck_launch(double flops, F&& launch);     // launch(start, stop): one of k::neck_conv*_ln
 
     int device_ = 0;
     bool shared_gpu_ = false;            // other lanes run on this device too (GEMM tile choice, gemm_plan.cpp)
@@ -298,7 +300,8 @@ class SamModel {
     bool caller_copy_pending_ = false;
     uint8_t* stage_rows(uint8_t const* pixels, size_t row_bytes, int rows, int stride, hipEvent_t* copied);
     DeviceBuffer<half_t> patches_, xn_, xlo_, qkv_, att_, hid_;
-    DeviceBuffer<float> x_, xstat_, neck_f32_, emb_;
+    DeviceBuffer<float> x_, xstat_, emb_;
+    DeviceBuffer<float> neck_f32_;       // DLIMGEDIT_FUSED_LN=0 only: the neck convolutions' fp32 results
     // SAM-HQ models: first transposed convolution fp32 / after its LayerNorm f16, the two branches' second convolutions,
     // the f16 copy of the embedding, and the features of passes that have no handle to write them to
     DeviceBuffer<float> hq_a_, hq_vit_, hq_embf_, hq_feat_;

@@ -225,6 +225,9 @@ SamWeights::SamWeights(std::string const& weight_path, int device_index) : devic
         neck2_.in = 9 * kEmbedDim;
     }
     ld.norm("enc.neck.ln2", kEmbedDim, neck_ln2_);
+    // what the fused 3x3 launch reads for the taps that fall outside the image (k::neck_conv3x3_ln)
+    zero_line_.reserve(64);
+    HIP_CHECK(hipMemsetAsync(zero_line_.get(), 0, 64 * sizeof(half_t), stream_));
 
     DeviceBuffer<half_t> pe_h;      // dense positional encoding as a GEMM operand, only needed below
     ld.f32("pe.gauss", {2, 128}, pe_gauss_);
