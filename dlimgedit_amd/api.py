@@ -179,6 +179,29 @@ def neck_hooks_library() -> C.CDLL:
     return _neck_hooks_lib
 
 
+_cleanup_hooks_lib = None
+CLEANUP_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_cleanup_test.so")
+# the hook of the mask clean-up kernels alone (csrc/cleanup_test_hooks.cpp): bound by name, no header declares it
+CLEANUP_HOOK_EXPORTS = ("dlimg_amd_test_mask_cleanup",)
+
+
+def cleanup_hooks_library() -> C.CDLL:
+    """Loads lib/libdlimgedit_cleanup_test.so: the product's objects plus the hook of the mask clean-up kernels.  Raises if it
+    has not been built; there is no fallback."""
+    global _cleanup_hooks_lib
+    if _cleanup_hooks_lib is None:
+        if not CLEANUP_HOOKS_LIB_PATH.exists():
+            raise Error(f"{CLEANUP_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+        lib = C.CDLL(str(CLEANUP_HOOKS_LIB_PATH))
+        lib.dlimg_init.restype = C.POINTER(_Api)
+        lib.dlimg_init.argtypes = []
+        ip = C.POINTER(C.c_int)
+        lib.dlimg_amd_test_mask_cleanup.argtypes = [C.POINTER(C.c_void_p), ip, ip, ip, ip, C.c_int]
+        lib.dlimg_amd_test_mask_cleanup.restype = C.c_int
+        _cleanup_hooks_lib = lib
+    return _cleanup_hooks_lib
+
+
 def _check_neck_hook(result: int) -> None:
     if result != 0:
         msg = neck_hooks_library().dlimg_init().contents.last_error()
@@ -336,6 +359,7 @@ MAX_CLICKS = 8               # clicks of one prompt (csrc/prompt_plan.hpp: kMaxC
 TOKEN_ROWS_MAX = 112         # token rows of one decoder launch (csrc/kernels/kernels.hpp: kDecoderMaxRows)
 EMPTY_REGION = (0, 0, -1, -1)    # x1 < x0: "no box" for the head of a multi-click prompt
 REFINE_MARK = 4              # regions[4 i] of a refinement mark (dlimgedit.h: DLIMG_REFINE_MARK; csrc/prompt_plan.hpp: kRefineMark)
+CLEAN_MARK = 6               # regions[4 i] of a clean-up mark (dlimgedit.h: DLIMG_CLEAN_MARK; csrc/prompt_plan.hpp: kCleanMark)
 
 
 @dataclass
@@ -348,7 +372,10 @@ class ClickEntries:
     rows in order of first appearance and cut at the 112 rows a launch holds.
     A refinement mark is a continuation entry (REFINE_MARK, 0, 0, 0) whose point is not read.  stage_clicks[j]: the clicks each
     stage of prompt j takes (one stage without marks; token_rows[j] are the last stage's).  A prompt with marks is decoded
-    behind the others, one launch per stage."""
+    behind the others, one launch per stage.
+    A clean-up mark is a continuation entry (CLEAN_MARK, max_hole, max_island, 0), the last entry of its prompt, whose point is
+    not read either: the prompt's mask is delivered with its small holes filled and its small islands dropped.  It changes
+    neither token_rows nor stage_clicks nor launches."""
     heads: list
     points: list
     regions: list
@@ -423,12 +450,66 @@ def _checked_marks(n_clicks: int, refine_after) -> list:
     return ks
 
 
-def click_entries(clicks, labels=None, regions=None, refine_after=None) -> ClickEntries:
+def _checked_clean(clean, n: int) -> list:
+    """`clean` of a call of n prompts -> per prompt None or (max_hole, max_island): None: no prompt is cleaned; one pair of
+    ints: every prompt; else one entry (None or a pair) per prompt.  Thresholds are pixels of the delivered mask, >= 0 and not
+    both 0 (what the library refuses is refused here, before anything reaches it)."""
+    if clean is None:
+        return [None] * n
+    def pair(c):
+        c = tuple(c)
+        if len(c) != 2 or not all(isinstance(v, (int, np.integer)) for v in c):
+            raise Error("clean: a clean-up mark is a pair of ints (max_hole, max_island)")
+        a, b = int(c[0]), int(c[1])
+        if a < 0 or b < 0 or (a == 0 and b == 0):
+            raise Error("clean: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0")
+        if max(a, b) > 0x7fffffff:
+            raise Error("clean: a clean-up mark's thresholds are C ints")
+        return a, b
+
+    clean = list(clean)
+    if len(clean) == 2 and all(isinstance(v, (int, np.integer)) for v in clean):
+        return [pair(clean)] * n
+    if len(clean) != n:
+        raise Error("clean: None, one (max_hole, max_island) pair for all prompts, or one entry (None or a pair) per prompt")
+    return [None if c is None else pair(c) for c in clean]
+
+
+def _marked_entries(n: int, points, regions, clean: list):
+    """The `points` / `regions` form of a batch call with clean-up marks as entry lists: entry i of the caller's, then its mark.
+    -> (index into segs or None per entry, [(x, y)] or None, [(4 ints)]).  A point prompt gets the empty region (no box)."""
+    heads, pts, regs = [], ([] if points is not None else None), []
+    for i in range(n):
+        heads.append(i)
+        if pts is not None:
+            pts.append((points[i].x, points[i].y))
+        q = None if regions is None else regions[i]
+        regs.append(EMPTY_REGION if q is None else (q.top_left.x, q.top_left.y, q.bottom_right.x, q.bottom_right.y))
+        if clean[i] is not None:
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((CLEAN_MARK, clean[i][0], clean[i][1], 0))
+    return heads, pts, regs
+
+
+def _marked_arrays(segs, heads, pts, regs):
+    n = len(heads)
+    handles = (C.c_void_p * n)(*[None if h is None else segs[h]._handle for h in heads])
+    p = None if pts is None else (C.c_int * (2 * n))(*[v for q in pts for v in q])
+    r = (C.c_int * (4 * n))(*[v for q in regs for v in q])
+    return n, handles, p, r
+
+
+def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
-    decoded in stages, each taking the low-res logits of the one before it as SAM's mask input.  Pure host code."""
+    decoded in stages, each taking the low-res logits of the one before it as SAM's mask input.  clean: None, one
+    (max_hole, max_island) pair for every prompt, or per prompt None / a pair -- a clean-up mark behind the prompt's last click.
+    Pure host code."""
     n = len(clicks)
+    clean = _checked_clean(clean, n)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -453,6 +534,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None) -> Click
                 out.regions.append((lab, 0, 0, 0))
             else:
                 out.regions.append(EMPTY_REGION if r is None else (r.top_left.x, r.top_left.y, r.bottom_right.x, r.bottom_right.y))
+        if clean[j] is not None:
+            out.heads.append(None)
+            out.points.append((0, 0))
+            out.regions.append((CLEAN_MARK, clean[j][0], clean[j][1], 0))
     return out
 
 
@@ -535,27 +620,34 @@ class Segmentation:
         return [Mask(m, a) for m, a in zip(masks, acc)]
 
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
-                            region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None) -> np.ndarray:
+                            region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
+                            clean=None) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
         them: the first k clicks give a mask whose low-res logits are the mask input of the next stage (on the GPU), and so on;
-        the mask of the last stage is returned.  Needs a model with the mask branch (pe.mask.*)."""
+        the mask of the last stage is returned.  Needs a model with the mask branch (pe.mask.*).
+        clean: (max_hole, max_island) -- the mask is delivered with background components below max_hole pixels filled and then
+        foreground components below max_island pixels dropped (8-connectivity; the largest island stays when all are below)."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
                                                out=None if out is None else [out],
-                                               refine_after=None if refine_after is None else [refine_after])[0]
+                                               refine_after=None if refine_after is None else [refine_after],
+                                               clean=None if clean is None else [tuple(clean)])[0]
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
-                           clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None) -> list:
+                           clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
+                           clean=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
         `clicks` instead of `points`: prompt i is the clicks clicks[i] (1 .. 8) with labels[i] (1 / 0; None: foreground) and
         the box regions[i] (None: no box); prompts of different sizes may share the call (click_entries builds the lists).
         refine_after (with `clicks`): per prompt None, "each" or click counts, or one "each" for all -- refinement marks, see
-        compute_mask_clicks."""
+        compute_mask_clicks.
+        clean (either form): None, one (max_hole, max_island) pair for all prompts, or per prompt None / a pair -- clean-up
+        marks, see compute_mask_clicks; a box-only call may carry them too."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -565,7 +657,7 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
-            entries = click_entries(clicks, labels, regions, refine_after)
+            entries = click_entries(clicks, labels, regions, refine_after, clean)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
@@ -573,9 +665,18 @@ class Segmentation:
                 _check(api().get_segmentation_masks(handles, n, p, r, ptrs))
             return outs
         n = len(segs)
-        handles = (C.c_void_p * n)(*[s._handle for s in segs])
         outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
         assert len(outs) == n and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
+        marks = _checked_clean(clean, n)
+        if any(m is not None for m in marks):
+            if points is None and regions is None:
+                raise Error("compute_mask_batch: neither points nor regions given")
+            heads, pts, regs = _marked_entries(n, points, regions, marks)
+            m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
+            ptrs = (C.c_void_p * m)(*[None if h is None else outs[h].ctypes.data for h in heads])
+            _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
+            return outs
+        handles = (C.c_void_p * n)(*[s._handle for s in segs])
         ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
         p = r = None
         if points is not None:
@@ -881,10 +982,10 @@ class ext:
 
     @classmethod
     def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0, clicks=None,
-                                  labels=None, refine_after=None) -> list:
+                                  labels=None, refine_after=None, clean=None) -> list:
         """Device-output form of Segmentation.compute_mask_batch (points, regions or both, or clicks / labels / regions, as
         there): masks land tightly packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their
-        embeddings live; returns the byte offset of every mask.  refine_after: as there."""
+        embeddings live; returns the byte offset of every mask.  refine_after, clean: as there."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch_device: refine_after goes with `clicks`")
         if clicks is not None:
@@ -892,7 +993,7 @@ class ext:
                 raise Error("compute_mask_batch_device: `points` or `clicks`, not both")
             if len(clicks) != len(segs):
                 raise Error("compute_mask_batch_device: one list of clicks per segmentation")
-            entries = click_entries(clicks, labels, regions, refine_after)
+            entries = click_entries(clicks, labels, regions, refine_after, clean)
             calls = _entry_calls(entries)
             if len(calls) > 1:      # one-click prompts with and without a box: a call each, so that the masks stay in order
                 calls = [([i], entries.regions[i] != EMPTY_REGION) for i in range(len(entries.heads))]
@@ -906,6 +1007,15 @@ class ext:
                 base += e.width * e.height if len(calls) > 1 else 0
             return result
         n = len(segs)
+        marks = _checked_clean(clean, n)
+        if any(m is not None for m in marks):
+            if points is None and regions is None:
+                raise Error("compute_mask_batch_device: neither points nor regions given")
+            heads, pts, regs = _marked_entries(n, points, regions, marks)
+            m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
+            offsets = (C.c_size_t * m)()
+            _check(cls._l().dlimg_amd_get_segmentation_masks_device(handles, m, p, r, root_device, dev_out, offsets))
+            return [offsets[k] for k, h in enumerate(heads) if h is not None]
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         p = r = None
         if points is not None:
@@ -1041,6 +1151,31 @@ class ext:
         _check_hook(cls._h().dlimg_amd_test_layernorm(x.ctypes.data, w.ctypes.data, b.ctypes.data, eps, rows, dim, act,
                                                  o32.ctypes.data, o16.ctypes.data))
         return o32, o16
+
+    @classmethod
+    def test_mask_cleanup(cls, masks, max_hole, max_island, shapes=None) -> list:
+        """The mask clean-up kernels alone (the hook of cleanup_hooks_library()): `masks`, (h, w) uint8 arrays of 0 / 255 of
+        possibly different sizes, as ONE k::mask_cleanup call on the default device; max_hole / max_island: one int for all or
+        one per mask.  Returns the cleaned masks (the inputs are left alone).  For the launcher's refusals a mask may be None
+        (a null pointer) and shapes[i] = (h, w) may claim an extent of its own; a refusal raises Error."""
+        n = len(masks)
+        hole = [int(max_hole)] * n if isinstance(max_hole, (int, np.integer)) else [int(v) for v in max_hole]
+        isle = [int(max_island)] * n if isinstance(max_island, (int, np.integer)) else [int(v) for v in max_island]
+        if len(hole) != n or len(isle) != n:
+            raise Error("test_mask_cleanup: one threshold for all masks or one per mask")
+        outs = [None if m is None else np.array(m, dtype=np.uint8, order="C", copy=True) for m in masks]
+        if shapes is None:
+            if any(o is None or o.ndim != 2 for o in outs):
+                raise Error("test_mask_cleanup: a mask is an (h, w) array; a None mask needs `shapes`")
+            shapes = [o.shape for o in outs]
+        ptrs = (C.c_void_p * n)(*[None if o is None else o.ctypes.data for o in outs])
+        w = (C.c_int * n)(*[int(s[1]) for s in shapes])
+        h = (C.c_int * n)(*[int(s[0]) for s in shapes])
+        rc = cleanup_hooks_library().dlimg_amd_test_mask_cleanup(ptrs, w, h, (C.c_int * n)(*hole), (C.c_int * n)(*isle), n)
+        if rc != 0:
+            msg = cleanup_hooks_library().dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        return outs
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

@@ -332,5 +332,19 @@ void birefnet_process_mask(const float* logits, int w, int h, uint8_t* out, hipS
 struct PostJob { const float* src; const float* select_iou; uint8_t* dst; int out_w, out_h, pre_w, pre_h; };
 void postprocess_masks(const PostJob* jobs_host, int count, hipStream_t);
 
+// ---- mask clean-up (K17, kernels/mask_cleanup.hip) --------------------------------------------
+// SAM's remove_small_regions on 0 / 255 masks, in place, 8-connectivity for both polarities.  Per job: (1) when max_hole > 0,
+// every connected component of the BACKGROUND with area < max_hole becomes foreground; (2) when max_island > 0, on the result
+// of (1), every connected component of the FOREGROUND with area < max_island becomes background -- except that when all
+// components are below the threshold the largest one stays, among equal largest the one whose first pixel in raster order
+// comes first.  Jobs of one call may differ in size.  Refused before anything is launched: a job with both thresholds 0 or
+// a negative one, a null mask, an extent that is not positive or whose w * h does not fit an int.  Stream-ordered, no host
+// synchronisation: at most four launches per polarity and 16 jobs.  workspace: mask_cleanup_workspace_bytes(jobs, count)
+// bytes of device memory (8 per pixel and 8 per job), contents irrelevant before and after.
+struct CleanJob { uint8_t* mask; int w, h; int max_hole, max_island; };   // mask: device memory, packed rows, in place
+size_t mask_cleanup_workspace_bytes(const CleanJob* jobs, int count);
+int mask_cleanup_launches(const CleanJob* jobs, int count);          // kernel launches mask_cleanup makes for these jobs
+void mask_cleanup(const CleanJob* jobs_host, int count, void* workspace, hipStream_t);
+
 }  // namespace k
 }  // namespace dlimg

@@ -10,6 +10,7 @@ namespace dlimg {
 namespace {
 
 constexpr double kLogitBytes = 256.0 * 256.0 * 4.0;     // what the kernel reads per mask: the low-resolution logits
+constexpr double kCleanBytesPerPixelAndPass = 2 * 1 + 2 * 4 + 4 + 4 * 4 + 1;     // k::mask_cleanup, see MaskTransport::run
 
 // Direct xGMI copies between two GPUs need peer access switched on once per direction (without it the runtime stages
 // the copy through host memory: still correct, slower).  Failures are not errors: the copy falls back by itself.
@@ -33,6 +34,12 @@ void enable_peer_access(int from_device, int to_device) {
         if (hipDeviceEnablePeerAccess(from_device, 0) != hipSuccess) (void)hipGetLastError();
     }
     (void)hipSetDevice(prev);
+}
+
+bool any_cleanup(CleanSpec const* clean, int count) {
+    for (int i = 0; clean && i < count; ++i)
+        if (clean[i].any()) return true;
+    return false;
 }
 
 void fill_sizes(std::vector<size_t>& sizes, k::PostJob const* jobs, int count) {
@@ -82,7 +89,7 @@ hipEvent_t MaskTransport::piece_event(MaskSlot& slot, int i) {
 }
 
 // The plan of the slot, step by step, on the lane's stream; slot.done behind the last of them.
-void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device) {
+void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean) {
     MaskTransportPlan const& p = slot.plan;
     // the slot is ours, and its previous user waited for the slot's event before letting go of it
     slot.dev.reserve(p.reserve_device);
@@ -107,6 +114,25 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
             double bytes = 0;
             for (int i = s.first; i < s.first + s.count; ++i) bytes += kLogitBytes + (double)slot.input.sizes[i];
             clock_.timed(ST_POST, bytes, [&] { k::postprocess_masks(&slot.kernel_jobs[s.first], s.count, stream_); });
+            if (!clean) continue;
+            // the masks of this launch that are cleaned, in place where the launch wrote them: device memory in every mode a
+            // request with clean-up marks is planned in (never the direct mode, whose kernel writes pinned host memory)
+            slot.clean_jobs.clear();
+            double clean_bytes = 0;
+            for (int i = s.first; i < s.first + s.count; ++i) {
+                if (!clean[i].any()) continue;
+                DLIMG_ASSERT(p.mode != MaskMode::direct);
+                k::PostJob const& j = slot.kernel_jobs[i];
+                slot.clean_jobs.push_back(k::CleanJob{j.dst, j.out_w, j.out_h, clean[i].max_hole, clean[i].max_island});
+                // per polarity pass and pixel: the mask read (K1, K4), labels and areas written (K1) and read (K3: areas,
+                // K4: both twice), at most one byte written
+                clean_bytes += kCleanBytesPerPixelAndPass * (double)slot.input.sizes[i] * ((clean[i].max_hole > 0) + (clean[i].max_island > 0));
+            }
+            if (slot.clean_jobs.empty()) continue;
+            const int n_clean = (int)slot.clean_jobs.size();
+            slot.clean_workspace.reserve(k::mask_cleanup_workspace_bytes(slot.clean_jobs.data(), n_clean));
+            clock_.timed(ST_POST, clean_bytes, [&] { k::mask_cleanup(slot.clean_jobs.data(), n_clean, slot.clean_workspace.get(), stream_); },
+                         clock_.profiling() ? k::mask_cleanup_launches(slot.clean_jobs.data(), n_clean) : 1);
         } else if (s.kind == MaskStep::event) {
             HIP_CHECK(hipEventRecord(piece_event(slot, s.first), stream_));
         } else if (s.to == MaskMem::peer) {
@@ -119,15 +145,16 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
     HIP_CHECK(hipEventRecord(slot.done, stream_));
 }
 
-void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count) {
+void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean) {
     if (count <= 0) return;
     // DLIMGEDIT_DIRECT_MASKS=0: measurement aid (always the copy path)
     static const bool direct_allowed = [] { const char* e = std::getenv("DLIMGEDIT_DIRECT_MASKS"); return !e || std::atoi(e) != 0; }();
     MaskTransportInput& in = slot.input;
     fill_sizes(in.sizes, jobs, count);
     in.iou_count = iou_count;
-    in.direct_allowed = direct_allowed;
-    in.others_idle = mask_mode_asks_idle(count, direct_allowed) && (!board_ || board_->others_idle(lane_index_));
+    if (!any_cleanup(clean, count)) clean = nullptr;
+    in.direct_allowed = direct_allowed && !clean;      // a mask to clean goes through the slot's device buffer
+    in.others_idle = mask_mode_asks_idle(count, in.direct_allowed) && (!board_ || board_->others_idle(lane_index_));
     // a destination in pinned image memory of the library (the Image the reference's wrapper allocates for the result
     // through create_image).  Direct mode looks at every destination, staged mode only asks whether all of them are pinned:
     // no lookup behind the first that is not
@@ -138,7 +165,7 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
         if (!in.dst_pinned[i] && !every) break;
     }
     plan_mask_transport(in, slot.plan);
-    run(slot, jobs, count, iou, device_);
+    run(slot, jobs, count, iou, device_, clean);
     if (board_) board_->mark(lane_index_, stream_);
 }
 
@@ -168,7 +195,7 @@ void MaskTransport::finish(MaskSlot& slot, k::PostJob const* jobs, int count, fl
                      std::chrono::duration<double, std::micro>(t1 - t0).count(), waited_us, p.piece_end.size(), p.iou_offset);
 }
 
-void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device) {
+void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean) {
     if (count <= 0) return;
     // test hook: take the staging + peer-copy path even when the destination is this lane's own GPU (a one-GPU box
     // has no second device to copy to; the path is the same code, the copy degenerates to device-to-device)
@@ -176,7 +203,7 @@ void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int c
     const bool force_peer = fp && std::atoi(fp) != 0;
     fill_sizes(slot.input.sizes, jobs, count);
     plan_mask_transport_device(slot.input.sizes, dst_device == device_ && !force_peer, slot.plan);
-    run(slot, jobs, count, nullptr, dst_device);
+    run(slot, jobs, count, nullptr, dst_device, any_cleanup(clean, count) ? clean : nullptr);
 }
 
 void MaskTransport::wait(MaskSlot& slot) { HIP_CHECK(hipEventSynchronize(slot.done)); }

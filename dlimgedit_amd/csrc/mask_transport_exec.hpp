@@ -6,6 +6,11 @@
 //   finish(slot, jobs, n, iou_out, n_iou)    no lock: waits piece by piece and copies what the plan left in the slot's
 //                                            pinned buffer into jobs[i].dst (HOST pointers of out_w*out_h bytes) and iou_out
 //   enqueue_device / wait                    the same for destinations in DEVICE memory of any GPU; slot.done only
+//   clean (enqueue, enqueue_device)          optional, [count]: the clean-up of mask i (prompt_plan.hpp: CleanSpec; both
+//                                            thresholds 0: none).  A request with a mask to clean never takes the direct
+//                                            mode: k::mask_cleanup runs right behind the post-processing launch, in place
+//                                            where that launch wrote -- the slot's device buffer, or the destination itself
+//                                            when that is memory of the lane's own GPU -- before any copy or event
 // Contract: acquire / release are thread-safe (a mutex of the component's own around the free list, nothing else); a slot
 // has one user at a time, who waits for slot.done before letting go of it, so its buffers and its plan need no lock.  The
 // lane hands in what is the lane's: its stream and stage clock (used under the lane's mutex, as by the lane itself), its
@@ -15,6 +20,7 @@
 #include "kernels/kernels.hpp"
 #include "lane_board.hpp"
 #include "mask_transport.hpp"
+#include "prompt_plan.hpp"
 #include "stage_clock.hpp"
 
 namespace dlimg {
@@ -27,6 +33,8 @@ struct MaskSlot {
     MaskTransportInput input;               // of the request the slot holds, kept for finish(); the vectors below are
     MaskTransportPlan plan;                 // re-used from request to request like these
     std::vector<k::PostJob> kernel_jobs;    // the caller's jobs with the destinations the plan gives the kernel
+    std::vector<k::CleanJob> clean_jobs;    // the masks of the request that are cleaned, where the kernel wrote them
+    DeviceBuffer<uint8_t> clean_workspace;  // labels and areas of k::mask_cleanup, pooled with the slot like `dev`
 };
 
 class MaskTransport {
@@ -39,14 +47,14 @@ class MaskTransport {
 
     MaskSlot& acquire();
     void release(MaskSlot& s);
-    void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count);
+    void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean = nullptr);
     void finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
-    void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device);
+    void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr);
     void wait(MaskSlot& slot);
 
   private:
     hipEvent_t piece_event(MaskSlot& slot, int i);
-    void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device);
+    void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean);
 
     int device_;
     hipStream_t stream_;

@@ -22,6 +22,13 @@
 // stage takes the low-res logits of the stage before it as SAM's mask input.  Every stage adds at least one click: a mark
 // directly after a mark, and a mark as the last entry of a prompt, are refused.  plan_prompts itself knows no marks: the
 // value 4 is one more label it refuses.
+//
+// Clean-up marks (plan_cleaned_prompts).  A continuation entry whose four ints are {kCleanMark, max_hole, max_island, 0} is a
+// clean-up mark: neither a click nor a stage, but a modifier of the one mask its prompt delivers (small holes filled, small
+// islands dropped: kernels.hpp, k::mask_cleanup).  A prompt has at most one, as the LAST entry of its prompt.  The call
+// without its clean-up marks is an ordinary call, which plan_staged_prompts reads -- with one thing kept: a call that holds
+// any continuation entry, a clean-up mark included, reads an empty head region as "no box", and the mark itself needs
+// `regions` but not `points` (a box-only call may clean its masks).  A call without clean-up marks is plan_staged_prompts.
 #pragma once
 
 #include "prompt_geometry.hpp"
@@ -34,6 +41,7 @@ namespace dlimg {
 
 constexpr int kMaxClicks = 8;
 constexpr int kRefineMark = 4;       // regions[4 i] of a mark: the first value SAM's labels (-1 pad, 0 / 1 clicks, 2 / 3 corners) leave free
+constexpr int kCleanMark = 6;        // regions[4 i] of a clean-up mark (5 stays a refused label)
 
 struct PromptSpec {
     int head = 0;            // entry that opened the prompt (its handle, its out_masks, its region)
@@ -43,11 +51,15 @@ struct PromptSpec {
 };
 
 // has_handle[i]: entry i has a handle.  Throws std::invalid_argument with the message the caller reports.
-inline std::vector<PromptSpec> plan_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions) {
+// had_continuation: the caller's list held continuation entries that are not in this one (clean-up marks): an empty region is
+// "no box" as in any call with continuation entries.
+inline std::vector<PromptSpec> plan_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions,
+                                            bool had_continuation = false) {
     const int count = (int)has_handle.size();
     std::vector<PromptSpec> prompts;
     bool any_continuation = false;
     for (int i = 0; i < count; ++i) any_continuation |= !has_handle[i];
+    const bool empty_is_no_box = any_continuation || had_continuation;
     if (!points_given && !regions) throw std::invalid_argument("mask batch: neither points nor regions given");
     if (any_continuation && !points_given) throw std::invalid_argument("mask batch: a continuation entry (null handle) is a click and needs `points`");
     prompts.reserve(count);
@@ -58,7 +70,7 @@ inline std::vector<PromptSpec> plan_prompts(std::vector<char> const& has_handle,
             p.clicks = points_given ? 1 : 0;
             p.box = regions != nullptr;
             // the empty region of a multi-click call: no box
-            if (any_continuation && regions && regions[4 * i + 2] < regions[4 * i]) p.box = false;
+            if (empty_is_no_box && regions && regions[4 * i + 2] < regions[4 * i]) p.box = false;
             prompts.push_back(p);
             continue;
         }
@@ -96,6 +108,21 @@ struct StagedPrompts {
 };
 
 inline bool is_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kRefineMark; }
+inline bool is_clean_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kCleanMark; }
+
+// A refusal that names "entry N" of a list some entries were taken out of, with N put back to the caller's numbering:
+// entry_of[n] is the caller's entry that became entry n.
+inline std::string renumber_entry(std::string msg, std::vector<int> const& entry_of) {
+    const std::string key = "entry ";
+    const size_t at = msg.find(key);
+    if (at == std::string::npos) return msg;
+    size_t end = at + key.size();
+    while (end < msg.size() && msg[end] >= '0' && msg[end] <= '9') ++end;
+    if (end == at + key.size()) return msg;
+    const size_t n = std::stoul(msg.substr(at + key.size(), end - at - key.size()));
+    if (n < entry_of.size()) msg = msg.substr(0, at + key.size()) + std::to_string(entry_of[n]) + msg.substr(end);
+    return msg;
+}
 
 // the one stage of a prompt without marks: its clicks travel in consecutive entries
 inline PromptStages unmarked_stages(PromptSpec const& p) {
@@ -107,13 +134,14 @@ inline PromptStages unmarked_stages(PromptSpec const& p) {
 
 // plan_prompts for a call that may hold marks; without one it is plan_prompts (same prompts, same refusals).  mask_branch: the
 // model has the prompt encoder's mask branch (pe.mask.*), without which no stage can take a mask input.
-inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
+inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch,
+                                         bool had_continuation = false) {
     const int count = (int)has_handle.size();
     bool any_mark = false;
     for (int i = 0; i < count; ++i) any_mark |= !has_handle[i] && is_mark_entry(regions, i);
     StagedPrompts out;
     if (!any_mark) {
-        out.prompts = plan_prompts(has_handle, points_given, regions);
+        out.prompts = plan_prompts(has_handle, points_given, regions, had_continuation);
         for (PromptSpec const& p : out.prompts) out.stages.push_back(unmarked_stages(p));
         return out;
     }
@@ -143,21 +171,10 @@ inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bo
     }
     std::vector<PromptSpec> packed;
     try {
-        packed = plan_prompts(handles, points_given, ints.data());
+        packed = plan_prompts(handles, points_given, ints.data(), had_continuation);
     } catch (std::invalid_argument const& e) {
         // plan_prompts numbers the entries of the list without marks: name the caller's entry instead
-        std::string msg = e.what();
-        const std::string key = "entry ";
-        const size_t at = msg.find(key);
-        if (at != std::string::npos) {
-            size_t end = at + key.size();
-            while (end < msg.size() && msg[end] >= '0' && msg[end] <= '9') ++end;
-            if (end > at + key.size()) {
-                const size_t n = std::stoul(msg.substr(at + key.size(), end - at - key.size()));
-                if (n < entry_of.size()) msg = msg.substr(0, at + key.size()) + std::to_string(entry_of[n]) + msg.substr(end);
-            }
-        }
-        throw std::invalid_argument(msg);
+        throw std::invalid_argument(renumber_entry(e.what(), entry_of));
     }
     for (PromptSpec p : packed) {
         PromptStages s;
@@ -169,6 +186,66 @@ inline StagedPrompts plan_staged_prompts(std::vector<char> const& has_handle, bo
         s.stage_clicks.push_back(p.clicks);
         out.prompts.push_back(p);
         out.stages.push_back(s);
+    }
+    return out;
+}
+
+// What a clean-up mark asks for: both 0 = the prompt's mask is delivered as it is.
+struct CleanSpec {
+    int max_hole = 0, max_island = 0;
+    bool any() const { return max_hole > 0 || max_island > 0; }
+};
+struct CleanedPrompts {
+    StagedPrompts staged;                // the call without its clean-up marks; heads and click entries in the caller's numbering
+    std::vector<CleanSpec> clean;      // [prompt]
+    bool any_clean = false;
+};
+
+// plan_staged_prompts for a call that may hold clean-up marks; without one it is plan_staged_prompts (same prompts, same
+// refusals).  Every refusal about a clean-up mark says "mark" and names the caller's entry.
+inline CleanedPrompts plan_cleaned_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
+    const int count = (int)has_handle.size();
+    CleanedPrompts out;
+    for (int i = 0; i < count; ++i) out.any_clean |= !has_handle[i] && is_clean_mark_entry(regions, i);
+    if (!out.any_clean) {
+        out.staged = plan_staged_prompts(has_handle, points_given, regions, mask_branch);
+        out.clean.resize(out.staged.prompts.size());
+        return out;
+    }
+    std::vector<char> handles;
+    std::vector<int> ints, entry_of;
+    std::vector<CleanSpec> by_head;        // [prompt of the list without clean-up marks]
+    for (int i = 0; i < count; ++i) {
+        if (has_handle[i] || !is_clean_mark_entry(regions, i)) {
+            if (has_handle[i]) by_head.push_back(CleanSpec{});
+            handles.push_back(has_handle[i]);
+            ints.insert(ints.end(), regions + 4 * i, regions + 4 * i + 4);
+            entry_of.push_back(i);
+            continue;
+        }
+        const int* r = regions + 4 * i;
+        const std::string who = "mask batch: entry " + std::to_string(i) + ": a clean-up mark ";
+        if (r[1] < 0 || r[2] < 0 || (r[1] == 0 && r[2] == 0) || r[3] != 0)
+            throw std::invalid_argument(who + "is {6, max_hole, max_island, 0} in regions[4 i ..]: thresholds >= 0 and not both 0, the fourth int 0");
+        if (by_head.empty()) throw std::invalid_argument(who + "needs a prompt in front of it");
+        if (i + 1 < count && !has_handle[i + 1])
+            throw std::invalid_argument(who + "is the last entry of its prompt, and a prompt has one at most");
+        by_head.back() = CleanSpec{r[1], r[2]};
+    }
+    try {
+        out.staged = plan_staged_prompts(handles, points_given, ints.data(), mask_branch, /*had_continuation*/ true);
+    } catch (std::invalid_argument const& e) {
+        throw std::invalid_argument(renumber_entry(e.what(), entry_of));
+    }
+    // prompts come out in head order, one per handle
+    out.clean = by_head;
+    for (size_t j = 0; j < out.staged.prompts.size(); ++j) {
+        PromptSpec& p = out.staged.prompts[j];
+        p.head = entry_of[p.head];
+        for (int& e : out.staged.stages[j].click_entry) e = entry_of[e];
+        if (p.clicks == 0 && !p.box)
+            throw std::invalid_argument("mask batch: entry " + std::to_string(p.head) + ": a prompt with a clean-up mark still needs a click or "
+                                        "a box (an empty region is no box, and there are no `points`)");
     }
     return out;
 }

@@ -222,9 +222,13 @@ class SamModel {
     using MaskSlot = dlimg::MaskSlot;
     MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
     void release_mask_slot(MaskSlot& s) { masks_.release(s); }
-    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count) { masks_.enqueue(slot, jobs, count, iou_.get(), iou_count); }
+    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count, CleanSpec const* clean = nullptr) {
+        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean);
+    }
     void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) { masks_.finish(slot, jobs, count, iou_out, iou_count); }
-    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device) { masks_.enqueue_device(slot, jobs, count, dst_device); }
+    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr) {
+        masks_.enqueue_device(slot, jobs, count, dst_device, clean);
+    }
     void wait_masks(MaskSlot& slot) { masks_.wait(slot); }
     // Blocking convenience form of the three calls above (mutex() held throughout).
     void masks_to_host(k::PostJob const* jobs, int count);

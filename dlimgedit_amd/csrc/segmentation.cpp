@@ -36,6 +36,8 @@ int pack_prompt(ResizeLongestSide const& rs, Point const* point, Region const* r
 struct BatchPrompts {
     std::vector<PromptSpec> prompts;
     std::vector<PromptStages> stages;
+    std::vector<CleanSpec> clean;      // [prompt]: what its clean-up mark asks for (nothing without one)
+    bool any_clean = false;
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -54,9 +56,11 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        StagedPrompts plan = plan_staged_prompts(has_handle, points != nullptr, regions, mask_branch);
-        b.prompts = std::move(plan.prompts);
-        b.stages = std::move(plan.stages);
+        CleanedPrompts plan = plan_cleaned_prompts(has_handle, points != nullptr, regions, mask_branch);
+        b.prompts = std::move(plan.staged.prompts);
+        b.stages = std::move(plan.staged.stages);
+        b.clean = std::move(plan.clean);
+        b.any_clean = plan.any_clean;
         // a SAM-HQ model takes one point less (its HQ token is a token row): refused here, before any prompt of the call is launched
         if (any)
             for (PromptSpec const& p : b.prompts) {
@@ -484,15 +488,16 @@ namespace {
 //   kRange         ROCTX range around a chunk's enqueue
 //   kFinishBehind  the chunk that many chunks back is finished before the next one takes its slot (0: all at the end)
 //   dst(head)      where the mask of the prompt that entry `head` opened goes
-//   enqueue        under the lane's mutex, behind the chunk's decode;  finish: no mutex, returns when the masks are in place
+//   enqueue        under the lane's mutex, behind the chunk's decode (clean: null, or per job what its prompt's clean-up mark
+//                  asks for);  finish: no mutex, returns when the masks are in place
 struct HostMasks {
     static constexpr const char* kRange = "dlimg.compute_masks";
     // masks of a chunk are copied to the caller while the two chunks behind it are on the GPU
     static constexpr size_t kFinishBehind = 3;
     uint8_t* const* out_masks;
     uint8_t* dst(int head) const { return out_masks[head]; }
-    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
-        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0);
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean) const {
+        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
         model.finish_masks(slot, jobs.data(), (int)jobs.size(), nullptr, 0);
@@ -505,8 +510,8 @@ struct DeviceMasks {
     std::vector<size_t> const& offsets;          // [entry]
     int root_device;
     uint8_t* dst(int head) const { return dev_out + offsets[head]; }
-    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
-        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device);
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean) const {
+        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const&) const { model.wait_masks(slot); }
 };
@@ -516,7 +521,8 @@ struct DeviceMasks {
 // count) and cut into chunks of at most kPromptChunk prompts (prompt_plan.hpp), each chunk decoded as one batch on the next
 // lane and its masks handed to `sink`.  A prompt with refinement marks is a chunk of its own behind them: its stages run in
 // order on one lane's stream, each taking the logits of the one before it as its mask input, and only the last one is
-// post-processed.
+// post-processed.  A prompt with a clean-up mark has its mask cleaned on the GPU behind the post-processing (the mask of the
+// last stage only; the logits fed back between stages are untouched).
 template <typename Sink>
 void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
                                        int const* regions, Sink const& sink) {
@@ -528,6 +534,7 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
         if (segs[prompts[j].head]->replica_ == replica) mine.push_back(j);
     struct Chunk { MaskSlotLease lease; std::vector<k::PostJob> jobs; };
     std::vector<Chunk> chunks;
+    std::vector<CleanSpec> clean;              // of the chunk being enqueued, [job]
     auto finish = [&](Chunk& c) {
         if (!c.lease.held()) return;
         const MaskSlotLease lease = std::move(c.lease);      // the slot goes back whether the wait throws or not
@@ -559,7 +566,11 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 cur.jobs[j] = single_mask_job(model.logits() + (size_t)j * 4 * kLowRes * kLowRes, model.iou() + (size_t)j * 4, npts,
                                               sink.dst(i), o, r);
             }
-            sink.enqueue(model, cur.lease.slot(), cur.jobs);
+            if (batch.any_clean) {
+                clean.resize(n);
+                for (int j = 0; j < n; ++j) clean[j] = batch.clean[part.prompts[j]];
+            }
+            sink.enqueue(model, cur.lease.slot(), cur.jobs, batch.any_clean ? clean.data() : nullptr);
         }
         for (auto& c : chunks) finish(c);
     } catch (...) {

@@ -23,12 +23,12 @@ void StageClock::flush_events() {
         HIP_CHECK(hipEventElapsedTime(&ms, p.a, p.b));
         stats_.ms[p.st] += ms;
         stats_.work[p.st] += p.work;
-        stats_.launches[p.st] += 1;
+        stats_.launches[p.st] += p.launches;
         for (Stage extra : {p.also, p.shape}) {
             if (extra == ST_COUNT) continue;
             stats_.ms[extra] += ms;
             stats_.work[extra] += p.work;
-            stats_.launches[extra] += 1;
+            stats_.launches[extra] += p.launches;
         }
         event_pool_.push_back(p.a);
         event_pool_.push_back(p.b);

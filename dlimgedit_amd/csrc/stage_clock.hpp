@@ -35,12 +35,14 @@ class StageClock {
     void set_profiling(bool on);
     StageStats take_stats();
 
-    template <typename F> void timed(Stage st, double work, F&& launch) {
+    // launches: kernel launches inside `launch` (one event pair around all of them)
+    template <typename F> void timed(Stage st, double work, F&& launch, int launches = 1) {
         if (!profiling_) {
             launch();
             return;
         }
         Pending p = event_pair(st, work);
+        p.launches = launches;
         HIP_CHECK(hipEventRecord(p.a, stream_));
         launch();
         HIP_CHECK(hipEventRecord(p.b, stream_));
@@ -48,7 +50,7 @@ class StageClock {
     }
     // For a launch that takes its own time (events attached to the dispatch, kernels.hpp: gemm): the pair to hand to it,
     // and add() once it has been enqueued.  The time also counts for the stages `also` and `shape` (ST_COUNT: none).
-    struct Pending { hipEvent_t a, b; Stage st; double work; Stage also = ST_COUNT; Stage shape = ST_COUNT; };
+    struct Pending { hipEvent_t a, b; Stage st; double work; Stage also = ST_COUNT; Stage shape = ST_COUNT; int launches = 1; };
     Pending event_pair(Stage st, double work, Stage also = ST_COUNT, Stage shape = ST_COUNT) {
         return Pending{take_event(), take_event(), st, work, also, shape};
     }

@@ -132,7 +132,22 @@ typedef struct dlimg_Api {
      * stage on a stage takes the low-res logits of the stage before it as its mask input, the way SAM's interactive
      * predictor feeds them back.  The mask of the last stage is delivered.  Refused (the message names the mark): a
      * mark directly after a mark, a mark as the last entry of a prompt, a mark with non-zero trailing ints, a mark
-     * for a model whose file has no mask branch (pe.mask.*).  A call without marks is read as it always was. */
+     * for a model whose file has no mask branch (pe.mask.*).  A call without marks is read as it always was.
+     * Clean-up marks (SAM's remove_small_regions): a continuation entry whose four ints are {DLIMG_CLEAN_MARK, max_hole,
+     * max_island, 0} is neither a click nor a stage -- points[i] is not read and it does not count towards the 8 clicks.
+     * The ONE mask its prompt delivers is cleaned on the GPU before it is copied out, thresholds in pixels of that mask,
+     * 8-connectivity for both polarities: first every connected component of the background with fewer than max_hole
+     * pixels becomes foreground (max_hole 0: skipped), then, on that result, every connected component of the foreground
+     * with fewer than max_island pixels becomes background (max_island 0: skipped) -- except that when all components
+     * are below max_island the largest one stays, and among equal largest the one whose first pixel in raster order comes
+     * first (SAM leaves this tie to OpenCV's label numbering; the raster-order rule is this library's).  For a prompt
+     * with refinement marks the mask of the last stage is cleaned; the logits fed back between stages are untouched.
+     * A call with a clean-up mark needs `regions`, not `points`: a box-only call may clean its masks, and like every call
+     * with continuation entries it reads an empty head region as "no box".  Refused (the message says "mark" and names
+     * the entry): a clean-up mark that is not the last entry of its prompt (so at most one per prompt; a refinement mark
+     * directly in front of it is still that prompt's last click-side entry and refused as such), one in front of any
+     * head, a negative threshold, both thresholds 0, a non-zero fourth int, and a prompt left with neither a click nor a
+     * box.  A call without clean-up marks is read as it always was. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -140,6 +155,9 @@ typedef struct dlimg_Api {
 /* regions[4 i] of a refinement mark in get_segmentation_masks (slot 14): the first value SAM's label space leaves
  * free (-1 padding point, 0 / 1 clicks, 2 / 3 box corners). */
 #define DLIMG_REFINE_MARK 4
+/* regions[4 i] of a clean-up mark in get_segmentation_masks (slot 14): {DLIMG_CLEAN_MARK, max_hole, max_island, 0}.
+ * 5 stays what it was, a refused label. */
+#define DLIMG_CLEAN_MARK 6
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

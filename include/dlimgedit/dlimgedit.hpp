@@ -203,6 +203,13 @@ struct Region {
 constexpr bool operator==(Region a, Region b) { return a.top_left == b.top_left && a.bottom_right == b.bottom_right; }
 constexpr bool operator!=(Region a, Region b) { return !(a == b); }
 
+// Clean-up of a delivered mask (SAM's remove_small_regions, on the GPU): background components below max_hole pixels are
+// filled, then foreground components below max_island pixels dropped (8-connectivity; 0 skips a step; when every island is
+// below max_island the largest stays, the first in raster order among equals).  Travels as a clean-up mark of table slot 14.
+struct MaskCleanup {
+    int max_hole = 0, max_island = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -292,9 +299,11 @@ class Segmentation {
     // clicks": the clicks are replayed in stages the way SAM's interactive predictor takes them, each stage with the low-res
     // logits of the one before it as its mask input (on the GPU); the mask of the last stage is returned.  refine_each(n):
     // a mark after every click but the last.  Needs a model with the mask branch.
+    // clean: the mask is delivered cleaned (MaskCleanup).
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
-                       std::vector<int> const& refine_after = {}) const {
-        return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after})[0]);
+                       std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt) const {
+        return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
+                                            clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{})[0]);
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -303,14 +312,19 @@ class Segmentation {
     }
 
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
-    // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none).
+    // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
+    // optional clean-up per prompt.
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
-                                                 std::vector<std::vector<int>> const& refine_after = {}) {
+                                                 std::vector<std::vector<int>> const& refine_after = {},
+                                                 std::vector<std::optional<MaskCleanup>> const& clean = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
-            (!refine_after.empty() && refine_after.size() != segs.size()))
+            (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
+        for (auto const& c : clean)
+            if (c && (c->max_hole < 0 || c->max_island < 0 || (c->max_hole == 0 && c->max_island == 0)))
+                throw Exception("compute_mask_batch: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         for (size_t j = 0; j < refine_after.size(); ++j)
             for (size_t m = 0; m < refine_after[j].size(); ++m)
                 if (refine_after[j][m] < 1 || refine_after[j][m] >= int(clicks[j].size()) || (m && refine_after[j][m] <= refine_after[j][m - 1]))
@@ -320,7 +334,7 @@ class Segmentation {
         for (size_t j = 0; j < segs.size(); ++j) {
             if (clicks[j].empty() || clicks[j].size() > 8) throw Exception("compute_mask_batch: a prompt takes 1 to 8 clicks");
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
-            refined = refined || clicks[j].size() > 1;
+            refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value());     // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -347,6 +361,12 @@ class Segmentation {
                     ptrs.push_back(c == 0 ? out[j].pixels() : nullptr);
                     if (c == 0) regs.push_back(box ? *regions[j] : Region(Point{0, 0}, Point{-1, -1}));
                     else regs.push_back(Region(Point{clicks[j][c].foreground ? 1 : 0, 0}, Point{0, 0}));
+                }
+                if (!clean.empty() && clean[j]) {
+                    hs.push_back(nullptr);               // the clean-up mark, the last entry of its prompt: its point is not read
+                    pts.push_back(Point{0, 0});
+                    ptrs.push_back(nullptr);
+                    regs.push_back(Region(Point{DLIMG_CLEAN_MARK, clean[j]->max_hole}, Point{clean[j]->max_island, 0}));
                 }
             }
             if (hs.empty()) continue;

@@ -101,7 +101,10 @@ DLIMG_API int dlimg_amd_segmentation_device(dlimg_Segmentation seg, int* out_rep
  * refined by a foreground point; entries with a NULL handle are further clicks of the prompt in front of them, as there:
  * then there is one mask and one offset per PROMPT, in the order of the head entries, and out_offsets of a continuation
  * entry repeats its head's; refinement marks, {DLIMG_REFINE_MARK, 0, 0, 0}, are continuation entries too and stage the
- * prompt with the previous stage's logits as mask input, as there).  Mask i is produced on the GPU that holds
+ * prompt with the previous stage's logits as mask input, as there; clean-up marks, {DLIMG_CLEAN_MARK, max_hole,
+ * max_island, 0}, mean what they mean there: the prompt's one mask is cleaned on the GPU that produced it -- in place at its
+ * destination when that is memory of the same GPU, else in the lane's staging buffer before the peer copy -- and the mark's
+ * out_offsets repeats its head's).  Mask i is produced on the GPU that holds
  * segs[i]'s embedding and is delivered into the memory of HIP device `root_device` at dev_out + offset_i, where
  * offset_i = sum over the entries before i of width*height (tightly packed, 0 / 255 bytes); the offsets are also written
  * to out_offsets[count] when it is non-null.  Masks of other GPUs cross xGMI as peer-to-peer copies (hipMemcpyPeerAsync);
