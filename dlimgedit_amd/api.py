@@ -202,6 +202,30 @@ def cleanup_hooks_library() -> C.CDLL:
     return _cleanup_hooks_lib
 
 
+_grid_hooks_lib = None
+GRID_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_grid_test.so")
+# the hook of the label-map kernels alone (csrc/grid_test_hooks.cpp): bound by name, no header declares it
+GRID_HOOK_EXPORTS = ("dlimg_amd_test_grid_kernels",)
+
+
+def grid_hooks_library() -> C.CDLL:
+    """Loads lib/libdlimgedit_grid_test.so: the product's objects plus the hook of the label-map kernels.  Raises if it has
+    not been built; there is no fallback."""
+    global _grid_hooks_lib
+    if _grid_hooks_lib is None:
+        if not GRID_HOOKS_LIB_PATH.exists():
+            raise Error(f"{GRID_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+        lib = C.CDLL(str(GRID_HOOKS_LIB_PATH))
+        lib.dlimg_init.restype = C.POINTER(_Api)
+        lib.dlimg_init.argtypes = []
+        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
+        lib.dlimg_amd_test_grid_kernels.argtypes = [fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
+                                                    C.c_int, C.POINTER(C.c_int32), fp, C.c_void_p, ip, ip, ip, C.c_int, fp]
+        lib.dlimg_amd_test_grid_kernels.restype = C.c_int
+        _grid_hooks_lib = lib
+    return _grid_hooks_lib
+
+
 def _check_neck_hook(result: int) -> None:
     if result != 0:
         msg = neck_hooks_library().dlimg_init().contents.last_error()
@@ -360,6 +384,8 @@ TOKEN_ROWS_MAX = 112         # token rows of one decoder launch (csrc/kernels/ke
 EMPTY_REGION = (0, 0, -1, -1)    # x1 < x0: "no box" for the head of a multi-click prompt
 REFINE_MARK = 4              # regions[4 i] of a refinement mark (dlimgedit.h: DLIMG_REFINE_MARK; csrc/prompt_plan.hpp: kRefineMark)
 CLEAN_MARK = 6               # regions[4 i] of a clean-up mark (dlimgedit.h: DLIMG_CLEAN_MARK; csrc/prompt_plan.hpp: kCleanMark)
+GRID_MARK = 7                # regions[4 i] of a grid mark (dlimgedit.h: DLIMG_GRID_MARK; csrc/grid_plan.hpp: kGridMark)
+GRID_MAX_SIDE = 32
 
 
 @dataclass
@@ -375,21 +401,29 @@ class ClickEntries:
     behind the others, one launch per stage.
     A clean-up mark is a continuation entry (CLEAN_MARK, max_hole, max_island, 0), the last entry of its prompt, whose point is
     not read either: the prompt's mask is delivered with its small holes filled and its small islands dropped.  It changes
-    neither token_rows nor stage_clicks nor launches."""
+    neither token_rows nor stage_clicks nor launches.
+    A grid prompt is two entries: a head with EMPTY_REGION and a continuation entry (GRID_MARK, side, iou_permille,
+    stability_permille); neither point is read.  grid_sides[j]: the side of prompt j's grid, 0 for any other prompt.  It is
+    decoded behind the others in launches of its own (side * side one-click prompts, 16 per launch), which `launches` does
+    not list; token_rows[j] are those of one of its prompts."""
     heads: list
     points: list
     regions: list
     prompt_heads: list
     token_rows: list
     stage_clicks: list = field(default_factory=list)
+    grid_sides: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
         return j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1
 
+    def _grid(self, j) -> bool:
+        return j < len(self.grid_sides) and self.grid_sides[j] > 0
+
     @property
     def launches(self) -> list:
         out = []
-        plain = [j for j in range(len(self.token_rows)) if not self._staged(j)]
+        plain = [j for j in range(len(self.token_rows)) if not self._staged(j) and not self._grid(j)]
         for t in dict.fromkeys(self.token_rows[j] for j in plain):
             group = [j for j in plain if self.token_rows[j] == t]
             cut = TOKEN_ROWS_MAX // t
@@ -475,14 +509,45 @@ def _checked_clean(clean, n: int) -> list:
     return [None if c is None else pair(c) for c in clean]
 
 
-def _marked_entries(n: int, points, regions, clean: list):
-    """The `points` / `regions` form of a batch call with clean-up marks as entry lists: entry i of the caller's, then its mark.
-    -> (index into segs or None per entry, [(x, y)] or None, [(4 ints)]).  A point prompt gets the empty region (no box)."""
+def _checked_grid(grid, n: int) -> list:
+    """`grid` of a call of n prompts -> per prompt None or (side, iou_permille, stability_permille): None: no grid prompt; else
+    one entry (None, or a triple of ints, side 1 .. 32) per prompt."""
+    if grid is None:
+        return [None] * n
+    grid = list(grid)
+    if len(grid) != n:
+        raise Error("grid: None, or one entry (None or (side, iou_permille, stability_permille)) per prompt")
+
+    def triple(g):
+        g = tuple(g)
+        if len(g) != 3 or not all(isinstance(v, (int, np.integer)) for v in g):
+            raise Error("grid: a grid mark is three ints (side, iou_permille, stability_permille)")
+        if not 1 <= int(g[0]) <= GRID_MAX_SIDE:
+            raise Error(f"grid: the side of a grid mark is 1..{GRID_MAX_SIDE}")
+        if any(abs(int(v)) > 0x7fffffff for v in g):
+            raise Error("grid: a grid mark's thresholds are C ints")
+        return int(g[0]), int(g[1]), int(g[2])
+    return [None if g is None else triple(g) for g in grid]
+
+
+def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None):
+    """The `points` / `regions` form of a batch call with clean-up or grid marks as entry lists: entry i of the caller's, then
+    its mark.  -> (index into segs or None per entry, [(x, y)] or None, [(4 ints)]).  A point prompt gets the empty region (no
+    box); a grid prompt is its head with the empty region and its mark (its point and region, if any were given, are not used)."""
     heads, pts, regs = [], ([] if points is not None else None), []
     for i in range(n):
         heads.append(i)
         if pts is not None:
-            pts.append((points[i].x, points[i].y))
+            pts.append((points[i].x, points[i].y) if points[i] is not None else (0, 0))
+        if grid is not None and grid[i] is not None:
+            if clean[i] is not None:
+                raise Error("a grid prompt takes no clean-up mark")
+            regs.append(EMPTY_REGION)
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((GRID_MARK,) + tuple(grid[i]))
+            continue
         q = None if regions is None else regions[i]
         regs.append(EMPTY_REGION if q is None else (q.top_left.x, q.top_left.y, q.bottom_right.x, q.bottom_right.y))
         if clean[i] is not None:
@@ -501,15 +566,18 @@ def _marked_arrays(segs, heads, pts, regs):
     return n, handles, p, r
 
 
-def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None) -> ClickEntries:
+def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
     decoded in stages, each taking the low-res logits of the one before it as SAM's mask input.  clean: None, one
     (max_hole, max_island) pair for every prompt, or per prompt None / a pair -- a clean-up mark behind the prompt's last click.
+    grid: None, or per prompt None / (side, iou_permille, stability_permille) -- prompt j is a grid prompt ("segment
+    everything"): clicks[j] is None or empty, and it takes no labels, region, refinement or clean-up marks.
     Pure host code."""
     n = len(clicks)
     clean = _checked_clean(clean, n)
+    grid = _checked_grid(grid, n)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -517,6 +585,17 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
         raise Error("one list of labels, one region (or None) and one refine_after (or None) per prompt")
     out = ClickEntries([], [], [], [], [])
     for j in range(n):
+        out.grid_sides.append(0 if grid[j] is None else grid[j][0])
+        if grid[j] is not None:
+            if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None:
+                raise Error("a grid prompt is its grid mark alone: no clicks, labels, region, refinement or clean-up marks")
+            out.prompt_heads.append(len(out.heads))
+            out.token_rows.append(7)
+            out.stage_clicks.append([1])
+            out.heads += [j, None]
+            out.points += [(0, 0), (0, 0)]
+            out.regions += [EMPTY_REGION, (GRID_MARK,) + grid[j]]
+            continue
         cs, ls = _checked_clicks(clicks[j], labels[j])
         marks = _checked_marks(len(cs), refine_after[j])
         r = regions[j]
@@ -619,6 +698,15 @@ class Segmentation:
         masks, acc = self._query(point, None, 3)
         return [Mask(m, a) for m, a in zip(masks, acc)]
 
+    def segment_everything(self, side: int = 32, iou_permille: int = 0, stability_permille: int = 0,
+                           out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Segment everything: the label map of a side x side point grid (1 .. 32) -- (h, w) uint8, 0 where no segment lies, k in
+        1 .. 255 for the k-th kept segment, the smallest segment on top.  Candidates (outputs 1 .. 3 of every grid prompt) are kept
+        whose predicted IoU is at least iou_permille / 1000 and whose stability at least stability_permille / 1000 (0: SAM's
+        defaults, 880 and 950), and that box NMS at 0.7 leaves (dlimgedit.h, DLIMG_GRID_MARK)."""
+        return Segmentation.compute_mask_batch([self], grid=[(side, iou_permille, stability_permille)],
+                                               out=None if out is None else [out])[0]
+
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
                             clean=None) -> np.ndarray:
@@ -638,7 +726,7 @@ class Segmentation:
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
-                           clean=None) -> list:
+                           clean=None, grid=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -647,7 +735,10 @@ class Segmentation:
         refine_after (with `clicks`): per prompt None, "each" or click counts, or one "each" for all -- refinement marks, see
         compute_mask_clicks.
         clean (either form): None, one (max_hole, max_island) pair for all prompts, or per prompt None / a pair -- clean-up
-        marks, see compute_mask_clicks; a box-only call may carry them too."""
+        marks, see compute_mask_clicks; a box-only call may carry them too.
+        grid (either form): None, or per prompt None / (side, iou_permille, stability_permille) -- prompt i is a grid prompt,
+        whose result is a label map (segment_everything); its point, clicks and region are not used (None will do), and with
+        grid prompts alone neither `points` nor `regions` nor `clicks` is needed."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -657,7 +748,7 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
-            entries = click_entries(clicks, labels, regions, refine_after, clean)
+            entries = click_entries(clicks, labels, regions, refine_after, clean, grid)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
@@ -668,10 +759,11 @@ class Segmentation:
         outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
         assert len(outs) == n and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
         marks = _checked_clean(clean, n)
-        if any(m is not None for m in marks):
-            if points is None and regions is None:
+        grids = _checked_grid(grid, n)
+        if any(m is not None for m in marks) or any(g is not None for g in grids):
+            if points is None and regions is None and any(g is None for g in grids):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             ptrs = (C.c_void_p * m)(*[None if h is None else outs[h].ctypes.data for h in heads])
             _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
@@ -982,10 +1074,11 @@ class ext:
 
     @classmethod
     def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0, clicks=None,
-                                  labels=None, refine_after=None, clean=None) -> list:
+                                  labels=None, refine_after=None, clean=None, grid=None) -> list:
         """Device-output form of Segmentation.compute_mask_batch (points, regions or both, or clicks / labels / regions, as
         there): masks land tightly packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their
-        embeddings live; returns the byte offset of every mask.  refine_after, clean: as there."""
+        embeddings live; returns the byte offset of every mask.  refine_after, clean, grid: as there (a grid prompt's
+        label map is delivered as a mask is)."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch_device: refine_after goes with `clicks`")
         if clicks is not None:
@@ -993,7 +1086,7 @@ class ext:
                 raise Error("compute_mask_batch_device: `points` or `clicks`, not both")
             if len(clicks) != len(segs):
                 raise Error("compute_mask_batch_device: one list of clicks per segmentation")
-            entries = click_entries(clicks, labels, regions, refine_after, clean)
+            entries = click_entries(clicks, labels, regions, refine_after, clean, grid)
             calls = _entry_calls(entries)
             if len(calls) > 1:      # one-click prompts with and without a box: a call each, so that the masks stay in order
                 calls = [([i], entries.regions[i] != EMPTY_REGION) for i in range(len(entries.heads))]
@@ -1008,10 +1101,11 @@ class ext:
             return result
         n = len(segs)
         marks = _checked_clean(clean, n)
-        if any(m is not None for m in marks):
-            if points is None and regions is None:
+        grids = _checked_grid(grid, n)
+        if any(m is not None for m in marks) or any(g is not None for g in grids):
+            if points is None and regions is None and any(g is None for g in grids):
                 raise Error("compute_mask_batch_device: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             offsets = (C.c_size_t * m)()
             _check(cls._l().dlimg_amd_get_segmentation_masks_device(handles, m, p, r, root_device, dev_out, offsets))
@@ -1176,6 +1270,41 @@ class ext:
             msg = cleanup_hooks_library().dlimg_init().contents.last_error()
             raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
         return outs
+
+    @classmethod
+    def test_grid_kernels(cls, planes4: np.ndarray, out_w: int, out_h: int, pre_w: int, pre_h: int, kept=None, iou4=None,
+                          iou_permille: int = 0, stability_permille: int = 0, cull: bool = True, want_store: bool = False,
+                          time_iters: int = 0):
+        """The label-map kernels alone (the hook of grid_hooks_library()): planes4 [P, 4, 256, 256] fp32 as a decode leaves them,
+        harvested in chunks of 16 prompts; then the candidates `kept` (label order; candidate c = 3 * prompt + plane - 1) are
+        painted into an (out_h, out_w) map for an image encoded at pre_w x pre_h -- or, with kept None, the candidates the
+        library's own selection keeps from the records and iou4 [P, 4] with the two thresholds.
+        -> (records int32 [3 P, 8], map uint8, kept list, guard bytes intact, store [3 P, 256, 256] or None); with time_iters > 0
+        the last element is instead (ms of one harvest of all candidates, ms of one paint launch), each the mean of time_iters
+        repetitions between two events."""
+        planes4 = np.ascontiguousarray(planes4, np.float32)
+        P = planes4.shape[0]
+        assert planes4.shape == (P, 4, 256, 256)
+        fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int)
+        iou = None if iou4 is None else np.ascontiguousarray(iou4, np.float32)
+        assert iou is None or iou.shape == (P, 4)
+        kin = None if kept is None else np.ascontiguousarray(kept, np.int32)
+        records = np.zeros((3 * P, 8), np.int32)
+        store = np.zeros((3 * P, 256, 256), np.float32) if want_store else None
+        out = np.zeros((out_h, out_w), np.uint8)
+        kout = np.zeros(255, np.int32)
+        nk, ok = C.c_int(0), C.c_int(0)
+        ms = (C.c_float * 2)(0.0, 0.0)
+        lib = grid_hooks_library()
+        rc = lib.dlimg_amd_test_grid_kernels(
+            planes4.ctypes.data_as(fp), P, None if iou is None else iou.ctypes.data_as(fp), out_w, out_h, pre_w, pre_h,
+            iou_permille, stability_permille, None if kin is None else kin.ctypes.data_as(ip), -1 if kin is None else len(kin),
+            int(cull), records.ctypes.data_as(C.POINTER(C.c_int32)), None if store is None else store.ctypes.data_as(fp),
+            out.ctypes.data, kout.ctypes.data_as(ip), C.byref(nk), C.byref(ok), int(time_iters), ms)
+        if rc != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        return records, out, [int(v) for v in kout[:nk.value]], bool(ok.value), (store if time_iters <= 0 else (ms[0], ms[1]))
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

@@ -346,5 +346,34 @@ size_t mask_cleanup_workspace_bytes(const CleanJob* jobs, int count);
 int mask_cleanup_launches(const CleanJob* jobs, int count);          // kernel launches mask_cleanup makes for these jobs
 void mask_cleanup(const CleanJob* jobs_host, int count, void* workspace, hipStream_t);
 
+// ---- label maps of a point grid (K18, kernels/mask_grid.hip) ----------------------------------
+// "Segment everything": the candidates of a grid of one-click prompts are planes 1..3 of every prompt, candidate
+// c = 3 * prompt + (plane - 1).  grid_harvest scores the candidates of one decode chunk and keeps their planes; the host
+// selects (csrc/grid_plan.hpp); grid_paint writes the label map of the kept ones.
+//
+// A record is 8 int32 (32 bytes), csrc/grid_plan.hpp: GridRecord -- n_hi, n_mid, n_lo: logits > +1, > 0, > -1 (strict) over the
+// SCORED region, low-res pixels x < ceil(pre_w / 4), y < ceil(pre_h / 4); x0, y0, x1, y1: the inclusive box of the logits > 0
+// there ({0, 0, -1, -1} when there is none); cull: the inclusive box of the logits > 0 over the REACH region, one low-res
+// column and row more (x <= min(ceil(pre_w / 4), 255), likewise y), as four bytes x0 | y0 << 8 | x1 << 16 | y1 << 24
+// (kGridCullEmpty when there is none).  The reach region is what the taps of the post-processing can read: the pixels at the
+// crop's edge sample row / column ceil(pre / 4) when pre mod 4 is 3 or 0, and never anything beyond it, so a pixel whose taps
+// miss the cull box cannot be positive (its sample is a combination of non-positive logits with weights >= 0).
+constexpr int kGridMaxKept = 255;
+constexpr int kGridRecordInts = 8;
+constexpr uint32_t kGridCullEmpty = 0x0000ffffu;
+constexpr size_t kGridPlaneFloats = 256 * 256;
+// logits [P][4][256][256] as a decode leaves them -> records[first_candidate + 3 p + plane - 1] and the same plane, bit for bit,
+// at store + (first_candidate + 3 p + plane - 1) * 65536; store and records hold `candidates` entries (checked).  One
+// workgroup per candidate, no atomics.
+void grid_harvest(const float* logits, int P, int first_candidate, int pre_w, int pre_h, float* store, int candidates, int32_t* records,
+                  hipStream_t);
+// The kept candidates in label order (label k = entry k - 1) with their cull words; travels as kernel arguments.
+struct GridKept { int count; int candidate[kGridMaxKept]; uint32_t cull[kGridMaxKept]; };
+// dst [out_h][out_w] bytes: per pixel the largest label whose mask (what postprocess_masks delivers for the plane) is 255 there,
+// 0 where none is.  candidates: planes the store holds (every kept candidate is checked against it before the launch).
+// cull = false: every label is sampled at every pixel (measurements; same map).
+void grid_paint(const float* store, int candidates, const GridKept& kept, uint8_t* dst, int out_w, int out_h, int pre_w, int pre_h,
+                bool cull, hipStream_t);
+
 }  // namespace k
 }  // namespace dlimg

@@ -89,8 +89,10 @@ hipEvent_t MaskTransport::piece_event(MaskSlot& slot, int i) {
 }
 
 // The plan of the slot, step by step, on the lane's stream; slot.done behind the last of them.
-void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean) {
+void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
+                        GridPaint const* paint) {
     MaskTransportPlan const& p = slot.plan;
+    DLIMG_ASSERT(!paint || (count == 1 && !clean));
     // the slot is ours, and its previous user waited for the slot's event before letting go of it
     slot.dev.reserve(p.reserve_device);
     slot.pin.reserve(p.reserve_pinned);
@@ -112,6 +114,14 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
     for (MaskStep const& s : p.steps) {
         if (s.kind == MaskStep::launch) {
             double bytes = 0;
+            if (paint) {
+                // a label map: the planes of the kept segments read (at most once each, where their boxes lie), the map written
+                k::PostJob const& j = slot.kernel_jobs[s.first];
+                clock_.timed(ST_POST, kLogitBytes * paint->kept.count + (double)slot.input.sizes[s.first], [&] {
+                    k::grid_paint(paint->store, paint->candidates, paint->kept, j.dst, j.out_w, j.out_h, j.pre_w, j.pre_h, /*cull*/ true, stream_);
+                });
+                continue;
+            }
             for (int i = s.first; i < s.first + s.count; ++i) bytes += kLogitBytes + (double)slot.input.sizes[i];
             clock_.timed(ST_POST, bytes, [&] { k::postprocess_masks(&slot.kernel_jobs[s.first], s.count, stream_); });
             if (!clean) continue;
@@ -145,7 +155,8 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
     HIP_CHECK(hipEventRecord(slot.done, stream_));
 }
 
-void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean) {
+void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean,
+                            GridPaint const* paint) {
     if (count <= 0) return;
     // DLIMGEDIT_DIRECT_MASKS=0: measurement aid (always the copy path)
     static const bool direct_allowed = [] { const char* e = std::getenv("DLIMGEDIT_DIRECT_MASKS"); return !e || std::atoi(e) != 0; }();
@@ -165,7 +176,7 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
         if (!in.dst_pinned[i] && !every) break;
     }
     plan_mask_transport(in, slot.plan);
-    run(slot, jobs, count, iou, device_, clean);
+    run(slot, jobs, count, iou, device_, clean, paint);
     if (board_) board_->mark(lane_index_, stream_);
 }
 
@@ -195,7 +206,8 @@ void MaskTransport::finish(MaskSlot& slot, k::PostJob const* jobs, int count, fl
                      std::chrono::duration<double, std::micro>(t1 - t0).count(), waited_us, p.piece_end.size(), p.iou_offset);
 }
 
-void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean) {
+void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean,
+                                   GridPaint const* paint) {
     if (count <= 0) return;
     // test hook: take the staging + peer-copy path even when the destination is this lane's own GPU (a one-GPU box
     // has no second device to copy to; the path is the same code, the copy degenerates to device-to-device)
@@ -203,7 +215,7 @@ void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int c
     const bool force_peer = fp && std::atoi(fp) != 0;
     fill_sizes(slot.input.sizes, jobs, count);
     plan_mask_transport_device(slot.input.sizes, dst_device == device_ && !force_peer, slot.plan);
-    run(slot, jobs, count, nullptr, dst_device, any_cleanup(clean, count) ? clean : nullptr);
+    run(slot, jobs, count, nullptr, dst_device, any_cleanup(clean, count) ? clean : nullptr, paint);
 }
 
 void MaskTransport::wait(MaskSlot& slot) { HIP_CHECK(hipEventSynchronize(slot.done)); }

@@ -11,6 +11,10 @@
 //                                            mode: k::mask_cleanup runs right behind the post-processing launch, in place
 //                                            where that launch wrote -- the slot's device buffer, or the destination itself
 //                                            when that is memory of the lane's own GPU -- before any copy or event
+//   paint (enqueue, enqueue_device)          optional: the request is ONE job whose bytes are a label map (grid_plan.hpp,
+//                                            kernels.hpp K18) -- the launch step runs k::grid_paint over the lane's grid store
+//                                            in place of the post-processing kernel; planning, staging, copies and events are
+//                                            those of a mask of the same size
 // Contract: acquire / release are thread-safe (a mutex of the component's own around the free list, nothing else); a slot
 // has one user at a time, who waits for slot.done before letting go of it, so its buffers and its plan need no lock.  The
 // lane hands in what is the lane's: its stream and stage clock (used under the lane's mutex, as by the lane itself), its
@@ -24,6 +28,13 @@
 #include "stage_clock.hpp"
 
 namespace dlimg {
+
+// What the launch step of a label-map request paints from: the lane's grid store and the kept list (SamModel::segment_grid).
+struct GridPaint {
+    float const* store = nullptr;
+    int candidates = 0;
+    k::GridKept kept{};
+};
 
 struct MaskSlot {
     DeviceBuffer<uint8_t> dev;
@@ -47,14 +58,17 @@ class MaskTransport {
 
     MaskSlot& acquire();
     void release(MaskSlot& s);
-    void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean = nullptr);
+    void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean = nullptr,
+                 GridPaint const* paint = nullptr);
     void finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
-    void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr);
+    void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
+                        GridPaint const* paint = nullptr);
     void wait(MaskSlot& slot);
 
   private:
     hipEvent_t piece_event(MaskSlot& slot, int i);
-    void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean);
+    void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
+             GridPaint const* paint);
 
     int device_;
     hipStream_t stream_;

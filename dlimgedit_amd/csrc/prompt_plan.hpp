@@ -29,6 +29,9 @@
 // without its clean-up marks is an ordinary call, which plan_staged_prompts reads -- with one thing kept: a call that holds
 // any continuation entry, a clean-up mark included, reads an empty head region as "no box", and the mark itself needs
 // `regions` but not `points` (a box-only call may clean its masks).  A call without clean-up marks is plan_staged_prompts.
+//
+// Grid marks ({7, side, iou_permille, stability_permille}: "segment everything") are read one layer further out, in
+// grid_plan.hpp (plan_grid_prompts), which hands the call without its grid prompts to plan_cleaned_prompts.
 #pragma once
 
 #include "prompt_geometry.hpp"
@@ -203,12 +206,15 @@ struct CleanedPrompts {
 
 // plan_staged_prompts for a call that may hold clean-up marks; without one it is plan_staged_prompts (same prompts, same
 // refusals).  Every refusal about a clean-up mark says "mark" and names the caller's entry.
-inline CleanedPrompts plan_cleaned_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
+// had_continuation: as for plan_prompts -- the caller's list held continuation entries that are not in this one (the marks of
+// grid prompts, grid_plan.hpp).
+inline CleanedPrompts plan_cleaned_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch,
+                                           bool had_continuation = false) {
     const int count = (int)has_handle.size();
     CleanedPrompts out;
     for (int i = 0; i < count; ++i) out.any_clean |= !has_handle[i] && is_clean_mark_entry(regions, i);
     if (!out.any_clean) {
-        out.staged = plan_staged_prompts(has_handle, points_given, regions, mask_branch);
+        out.staged = plan_staged_prompts(has_handle, points_given, regions, mask_branch, had_continuation);
         out.clean.resize(out.staged.prompts.size());
         return out;
     }

@@ -1,6 +1,8 @@
 #include "sam_model.hpp"
 #include "gemm_plan.hpp"
+#include "grid_plan.hpp"
 #include "image_memory.hpp"
+#include "roctx.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -824,6 +826,51 @@ void SamModel::decode_chunk(float const* const* emb, float const* coords, float 
     };
     clock_.timed(ST_DECODER, (hq ? 3.62e9 + 4.83e9 : 3.62e9) * P, body);
     HIP_CHECK(hipGetLastError());
+}
+
+GridPaint const& SamModel::segment_grid(float const* emb, float const* coords, float const* labels, int side, int pre_w, int pre_h,
+                                        int iou_permille, int stability_permille) {
+    DLIMG_ASSERT(side >= 1 && side <= kGridMaxSide && emb && coords && labels);
+    static_assert(kGridMaxSegments == k::kGridMaxKept && sizeof(GridRecord) == k::kGridRecordInts * sizeof(int32_t), "one record, one cap");
+    const int prompts = side * side, candidates = 3 * prompts;
+    const int chunk = k::decoder_max_prompts(kDecTokens + (has_hq() ? 1 : 0));       // 16 prompts of 7 token rows, 14 of 8
+    const size_t store_floats = (size_t)candidates * k::kGridPlaneFloats;
+    if (store_floats > grid_store_.capacity() || (size_t)candidates * k::kGridRecordInts > grid_records_.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));              // a label map queued earlier may still read the old store
+        grid_store_.reserve(store_floats);
+        grid_records_.reserve((size_t)candidates * k::kGridRecordInts);
+    }
+    const size_t record_bytes = (size_t)candidates * sizeof(GridRecord);
+    grid_host_.reserve(record_bytes + (size_t)prompts * 4 * sizeof(float));
+    GridRecord* const records = static_cast<GridRecord*>(grid_host_.get());
+    float* const iou4 = reinterpret_cast<float*>(static_cast<uint8_t*>(grid_host_.get()) + record_bytes);
+    const std::vector<float const*> embs((size_t)chunk, emb);
+    for (int p0 = 0; p0 < prompts; p0 += chunk) {
+        const int n = std::min(chunk, prompts - p0);
+        {
+            roctx::Range rd("dlimg.decode");
+            decode(embs.data(), coords + (size_t)p0 * 4, labels + (size_t)p0 * 2, n, 2, nullptr, /*handles*/ true);
+        }
+        roctx::Range rh("dlimg.grid_harvest");
+        // every candidate plane read once and written once
+        clock_.timed(ST_POST, 3.0 * n * 2 * k::kGridPlaneFloats * sizeof(float), [&] {
+            k::grid_harvest(logits_.get(), n, 3 * p0, pre_w, pre_h, grid_store_.get(), candidates, grid_records_.get(), stream_);
+        });
+        HIP_CHECK(hipMemcpyAsync(iou4 + (size_t)p0 * 4, iou_.get(), (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    }
+    HIP_CHECK(hipMemcpyAsync(records, grid_records_.get(), record_bytes, hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));                  // the one host round trip of a label map
+    std::vector<float> iou((size_t)candidates);
+    for (int c = 0; c < candidates; ++c) iou[c] = iou4[4 * (c / 3) + 1 + c % 3];
+    const GridSelection chosen = select_grid_segments(records, iou.data(), candidates, iou_permille, stability_permille);
+    grid_paint_.store = grid_store_.get();
+    grid_paint_.candidates = candidates;
+    grid_paint_.kept.count = (int)chosen.kept.size();
+    for (int i = 0; i < grid_paint_.kept.count; ++i) {
+        grid_paint_.kept.candidate[i] = chosen.kept[i];
+        grid_paint_.kept.cull[i] = records[chosen.kept[i]].cull;
+    }
+    return grid_paint_;
 }
 
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }

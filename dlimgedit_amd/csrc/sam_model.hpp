@@ -199,6 +199,18 @@ class SamModel {
     // pseudo-point to every prompt itself (5 + points + 1 token rows), so its prompts hold at most kHqMaxPoints points.
     void decode(float const* const* emb, float const* coords, float const* labels, int count, int points = 2,
                 k::MaskSource const* mask_input = nullptr, bool handles = false);
+    // "Segment everything" (grid_plan.hpp; kernels.hpp K18): the side * side one-click prompts of a grid over the image whose
+    // embedding is `emb` (a Segmentation handle's buffer), coords [side * side][2][2] / labels [side * side][2] packed as
+    // one-click prompts are (click, padding point).  Decoded in chunks of k::decoder_max_prompts(token rows) prompts, one
+    // decode() per chunk -- never one decode() for the whole grid, which would size every per-prompt workspace for it (about
+    // 10 MB per prompt) -- each chunk harvested into the lane's grid store before the next one overwrites logits().  Behind the
+    // last chunk the records and IoU predictions (44 bytes per candidate) go to pinned host memory, the call WAITS for the
+    // stream (the one host round trip of a label map), and the segments are selected on the host (select_grid_segments).
+    // Returns what the launch step of the label map's mask request paints from (enqueue_masks / enqueue_masks_device, `paint`);
+    // valid until the next segment_grid of this lane, so the request is enqueued under the same hold of mutex().
+    // pre_w, pre_h: the extent the image was encoded at.
+    GridPaint const& segment_grid(float const* emb, float const* coords, float const* labels, int side, int pre_w, int pre_h,
+                                  int iou_permille, int stability_permille);
     // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
     std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
@@ -222,12 +234,14 @@ class SamModel {
     using MaskSlot = dlimg::MaskSlot;
     MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
     void release_mask_slot(MaskSlot& s) { masks_.release(s); }
-    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count, CleanSpec const* clean = nullptr) {
-        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean);
+    void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count, CleanSpec const* clean = nullptr,
+                       GridPaint const* paint = nullptr) {
+        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean, paint);
     }
     void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) { masks_.finish(slot, jobs, count, iou_out, iou_count); }
-    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr) {
-        masks_.enqueue_device(slot, jobs, count, dst_device, clean);
+    void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
+                              GridPaint const* paint = nullptr) {
+        masks_.enqueue_device(slot, jobs, count, dst_device, clean, paint);
     }
     void wait_masks(MaskSlot& slot) { masks_.wait(slot); }
     // Blocking convenience form of the three calls above (mutex() held throughout).
@@ -358,6 +372,13 @@ class SamModel {
     DeviceBuffer<half_t> hq_u_, hq_mid_; // ... the up-scaled embedding [.][256][256][32] and the 3x3 path's intermediate [.][256][256][64]
     DeviceBuffer<float> mask_h_;         // [launch's prompts][4096][16]: the mask branch in front of its last convolution (first masked decode)
     DeviceBuffer<half_t> keys_h_, kqv_h_;
+    // label maps: the grid store [3 * side * side][256][256] fp32 (768 KB per prompt: 12 MiB at side 4, 192 MiB at side 16,
+    // 768 MiB at side 32), reserved on first use, sized by the largest side seen, kept for the life of the lane; the records
+    // (32 bytes per candidate) and their pinned host copy with the IoU predictions behind them
+    DeviceBuffer<float> grid_store_;
+    DeviceBuffer<int32_t> grid_records_;
+    PinnedBuffer grid_host_;
+    GridPaint grid_paint_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
 
     // ---- pass flags

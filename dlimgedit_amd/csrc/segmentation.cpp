@@ -1,5 +1,6 @@
 #include "segmentation.hpp"
 
+#include "grid_plan.hpp"
 #include "prompt_plan.hpp"
 #include "roctx.hpp"
 
@@ -38,6 +39,7 @@ struct BatchPrompts {
     std::vector<PromptStages> stages;
     std::vector<CleanSpec> clean;      // [prompt]: what its clean-up mark asks for (nothing without one)
     bool any_clean = false;
+    std::vector<GridSpec> grid;        // [prompt]: side > 0: a grid prompt (grid_plan.hpp); its packed points are not used
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -56,7 +58,9 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        CleanedPrompts plan = plan_cleaned_prompts(has_handle, points != nullptr, regions, mask_branch);
+        GridPlannedPrompts planned = plan_grid_prompts(has_handle, points != nullptr, regions, mask_branch);
+        CleanedPrompts& plan = planned.cleaned;
+        b.grid = std::move(planned.grid);
         b.prompts = std::move(plan.staged.prompts);
         b.stages = std::move(plan.staged.stages);
         b.clean = std::move(plan.clean);
@@ -76,22 +80,42 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     b.coords.resize(total * 2);
     b.labels.resize(total);
     for (size_t j = 0; j < b.prompts.size(); ++j)
-        pack_points(segs[b.prompts[j].head]->geometry(), b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions,
-                    &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
+        if (!b.grid[j].any())              // (a grid prompt's points are its grid's: pack_grid)
+            pack_points(segs[b.prompts[j].head]->geometry(), b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions,
+                        &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
     return b;
 }
 // What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
 // of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).
-struct BatchWork { PromptChunk part; bool staged; };
+// A grid prompt is a chunk of its own too, behind those: its side * side decodes and its label map run on one lane.
+struct BatchWork { PromptChunk part; bool staged; bool grid = false; };
 std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
     std::vector<int> plain;
     for (int j : mine)
-        if (!b.stages[j].staged()) plain.push_back(j);
+        if (!b.stages[j].staged() && !b.grid[j].any()) plain.push_back(j);
     std::vector<BatchWork> work;
     for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
     for (int j : mine)
         if (b.stages[j].staged()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+    for (int j : mine)
+        if (b.grid[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, false, true});
     return work;
+}
+// The side * side prompts of a grid over an image, each packed exactly as a one-click prompt at its pixel is (click, padding
+// point): coords [side * side][2][2], labels [side * side][2].
+void pack_grid(ResizeLongestSide const& rs, int side, std::vector<float>& coords, std::vector<float>& labels) {
+    PromptSpec spec;
+    spec.clicks = 1;
+    const PromptStages stages = unmarked_stages(spec);
+    coords.resize((size_t)side * side * 4);
+    labels.resize((size_t)side * side * 2);
+    for (int j = 0; j < side; ++j)
+        for (int i = 0; i < side; ++i) {
+            const Point at = grid_pixel(rs.original.width, rs.original.height, side, i, j);
+            const int click[2] = {at.x, at.y};
+            const size_t p = (size_t)j * side + i;
+            pack_points(rs, spec, stages, 1, click, nullptr, &coords[p * 4], &labels[p * 2]);
+        }
 }
 // The stages of staged prompt j in front of its last one, decoded on `model` (mutex held) one after the other; returns the
 // mask input of the last stage: the plane the stage before it would deliver, where that decode left it.
@@ -496,8 +520,9 @@ struct HostMasks {
     static constexpr size_t kFinishBehind = 3;
     uint8_t* const* out_masks;
     uint8_t* dst(int head) const { return out_masks[head]; }
-    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean) const {
-        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean);
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
+                 GridPaint const* paint = nullptr) const {
+        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean, paint);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
         model.finish_masks(slot, jobs.data(), (int)jobs.size(), nullptr, 0);
@@ -510,8 +535,9 @@ struct DeviceMasks {
     std::vector<size_t> const& offsets;          // [entry]
     int root_device;
     uint8_t* dst(int head) const { return dev_out + offsets[head]; }
-    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean) const {
-        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean);
+    void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
+                 GridPaint const* paint = nullptr) const {
+        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean, paint);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const&) const { model.wait_masks(slot); }
 };
@@ -554,6 +580,21 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
             Chunk& cur = chunks.back();
             roctx::Range range(Sink::kRange);
             std::lock_guard<std::mutex> lock(model.mutex());
+            if (work.grid) {
+                // a label map: the grid's prompts decoded and harvested chunk by chunk, the segments selected on the host (the
+                // call waits for the lane's stream once), and the map painted where a mask of this prompt would be written
+                const int j = part.prompts[0], i = prompts[j].head;
+                GridSpec const& g = batch.grid[j];
+                ResizeLongestSide const& rs = segs[i]->image_size_;
+                pack_grid(rs, g.side, cc, ll);
+                GridPaint const& paint = model.segment_grid(emb[0], cc.data(), ll.data(), g.side, rs.resized.width, rs.resized.height,
+                                                            g.iou_permille, g.stability_permille);
+                cur.jobs[0] = k::PostJob{paint.store, nullptr, sink.dst(i), rs.original.width, rs.original.height, rs.resized.width,
+                                         rs.resized.height};
+                roctx::Range rp("dlimg.grid_paint");
+                sink.enqueue(model, cur.lease.slot(), cur.jobs, nullptr, &paint);
+                continue;
+            }
             if (work.staged) {
                 const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
                 model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);

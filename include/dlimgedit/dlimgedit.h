@@ -158,6 +158,25 @@ typedef struct dlimg_Api {
 /* regions[4 i] of a clean-up mark in get_segmentation_masks (slot 14): {DLIMG_CLEAN_MARK, max_hole, max_island, 0}.
  * 5 stays what it was, a refused label. */
 #define DLIMG_CLEAN_MARK 6
+/* regions[4 i] of a grid mark in get_segmentation_masks (slot 14): {DLIMG_GRID_MARK, side, iou_permille,
+ * stability_permille} turns its prompt into a grid prompt ("segment everything", SAM's automatic mask generator in a
+ * narrow form).  A grid prompt is exactly two entries: the head (handle, out_masks of width * height bytes, an EMPTY region,
+ * x1 < x0) and the mark; neither entry's point is read, and `points` may be NULL.  side is 1 .. 32; the two thresholds may
+ * be any int, 0 meaning SAM's defaults 880 and 950.  out_masks[head] receives a LABEL MAP: 0 where no segment lies, k in
+ * 1 .. 255 for the k-th kept segment.  The side * side points (i, j) at pixel (floor((2 i + 1) W / (2 side)),
+ * floor((2 j + 1) H / (2 side))) are decoded as one-click prompts; the candidates are outputs 1 .. 3 of every prompt.  A
+ * candidate is scored on its 256 x 256 low-resolution logits over the part that lies inside the image (x < ceil(pre_w / 4),
+ * y < ceil(pre_h / 4), pre: the extent the image was encoded at; SAM scores at the original resolution): n_hi, n_mid, n_lo
+ * logits > +1, > 0, > -1 and the box of the logits > 0.  It passes when n_mid > 0, n_lo > 0, its IoU prediction >=
+ * iou_permille / 1000 (fp32) and n_hi * 1000 >= stability_permille * n_lo.  The passing candidates go through box NMS by IoU
+ * prediction (ties: lower candidate index first; suppressed when inter * 10 > 7 * union with torchvision's box area on the
+ * inclusive corners; at most 255 kept), the kept ones are labelled by n_mid descending (ties: NMS order), and a pixel
+ * carries the largest label whose mask -- exactly the mask a single query would deliver for that output -- is 255 there:
+ * the smallest segment lies on top.  Other prompts of the call may be anything the call takes.  Refused before anything is
+ * launched (the message says "mark" and names the entry): side out of range, a non-empty head region, any further
+ * continuation entry in the prompt (click, refinement mark, clean-up mark), a mark in front of any head.  A call without
+ * grid marks is read as it always was. */
+#define DLIMG_GRID_MARK 7
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

@@ -210,6 +210,13 @@ struct MaskCleanup {
     int max_hole = 0, max_island = 0;
 };
 
+// "Segment everything": a side x side grid of point prompts (1 .. 32), the candidates kept whose predicted IoU is at least
+// iou_permille / 1000 and whose stability is at least stability_permille / 1000 (0: SAM's defaults, 880 and 950).  Travels
+// as a grid mark of table slot 14.
+struct GridOptions {
+    int side = 32, iou_permille = 0, stability_permille = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -291,6 +298,21 @@ class Segmentation {
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), points.empty() ? nullptr : &points.data()->x,
                                                    regions.empty() ? nullptr : &regions.data()->top_left.x, ptrs.data()));
         return out;
+    }
+
+    // Segment everything (addition of this build): a label map of the image, 0 where no segment lies and k in 1 .. 255 for
+    // the k-th kept segment of a side x side point grid, the smallest segment on top (GridOptions; dlimgedit.h,
+    // DLIMG_GRID_MARK).  Travels as a grid prompt of table slot 14: the head with an empty region, then the mark.
+    void segment_everything(GridOptions const& grid, uint8_t* out_label_map) const {
+        dlimg_Segmentation hs[2] = {handle_.get(), nullptr};
+        const int regs[8] = {0, 0, -1, -1, DLIMG_GRID_MARK, grid.side, grid.iou_permille, grid.stability_permille};
+        uint8_t* ptrs[2] = {out_label_map, nullptr};
+        detail::check(api().get_segmentation_masks(hs, 2, nullptr, regs, ptrs));
+    }
+    Image segment_everything(GridOptions const& grid = {}) const {
+        Image m(extent(), Channels::mask);
+        segment_everything(grid, m.pixels());
+        return m;
     }
 
     // Click-to-refine (addition of this build): one mask from 1 .. 8 clicks -- the first one a foreground click -- and an
