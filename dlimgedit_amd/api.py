@@ -867,7 +867,8 @@ class ext:
                 "dlimg_amd_test_force_gemm_tile": ([ci], ci),
                 "dlimg_amd_test_force_gemm_consumer_tile": ([ci], ci),
                 "dlimg_amd_test_gemm": ([ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp], ci),
-                "dlimg_amd_test_gemm_ln": ([ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp], ci),
+                "dlimg_amd_test_gemm_ln": ([ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp, C.POINTER(ci)], ci),
+                "dlimg_amd_test_gemm_tile_shape": ([ci, C.POINTER(ci), C.POINTER(ci)], ci),
                 "dlimg_amd_test_lane_worker": ([ci, ci, vp], ci),
                 "dlimg_amd_test_gemm_stream": ([ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp], ci),
                 "dlimg_amd_test_layernorm": ([vp, vp, vp, cf, ci, ci, ci, vp, vp], ci),
@@ -903,7 +904,7 @@ class ext:
                "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_test_decode_prompts",
                "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
-               "dlimg_amd_bench_gemm_stamps")
+               "dlimg_amd_bench_gemm_stamps", "dlimg_amd_test_gemm_tile_shape")
 
     @staticmethod
     def _ptr(a: Optional[np.ndarray]):
@@ -1163,29 +1164,49 @@ class ext:
     @classmethod
     def force_gemm_tile(cls, tile: int = -1, consumer_tile: int = -1) -> None:
         """Tile configuration the GEMM test hooks use wherever it fits (-1: the product's own choice); consumer_tile: a
-        separate one for the LayerNorm-folded consumer of test_gemm_ln."""
+        separate one for the LayerNorm-folded consumer of test_gemm_ln.  One forced tile is not replaced where it does not fit: a
+        ping-pong tile (9, 10, 11) for an f16-only result with a residual, whose f16-rows epilogue would drop the residual --
+        that launch raises Error."""
         _check_hook(cls._h().dlimg_amd_test_force_gemm_tile(int(tile)))
         _check_hook(cls._h().dlimg_amd_test_force_gemm_consumer_tile(int(consumer_tile)))
 
     @classmethod
-    def test_gemm(cls, A: np.ndarray, W: np.ndarray, bias=None, resid=None, act: int = 0, want_f16: bool = False):
+    def gemm_tile_shape(cls, tile: int) -> Tuple[int, int]:
+        """(bm, bn) of tile configuration `tile`, from k::kGemmTiles (csrc/gemm_plan.hpp)."""
+        bm, bn = C.c_int(0), C.c_int(0)
+        _check_hook(cls._h().dlimg_amd_test_gemm_tile_shape(int(tile), C.byref(bm), C.byref(bn)))
+        return bm.value, bn.value
+
+    @classmethod
+    def test_gemm(cls, A: np.ndarray, W: np.ndarray, bias=None, resid=None, act: int = 0, want_f16: bool = False,
+                  want_f32: bool = True):
+        """want_f32=False with want_f16=True: the launch gets out_h only (the f16-only epilogues); returns the f16 result."""
+        assert want_f32 or want_f16, "no output asked for"
         A = np.ascontiguousarray(A, dtype=np.float16)
         W = np.ascontiguousarray(W, dtype=np.float16)
         M, K = A.shape
         N = W.shape[0]
         bias = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         resid = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
-        out32 = np.empty((M, N), dtype=np.float32)
+        out32 = np.empty((M, N), dtype=np.float32) if want_f32 else None
         out16 = np.empty((M, N), dtype=np.float16) if want_f16 else None
         _check_hook(cls._h().dlimg_amd_test_gemm(M, N, K, A.ctypes.data, W.ctypes.data, cls._ptr(bias), cls._ptr(resid),
-                                            0 if resid is None else resid.shape[0], act, out32.ctypes.data,
+                                            0 if resid is None else resid.shape[0], act, cls._ptr(out32),
                                             cls._ptr(out16)))
+        if not want_f32:
+            return out16
         return (out32, out16) if want_f16 else out32
 
     @classmethod
-    def test_gemm_ln(cls, A1, W1, bias1, resid, W2, gamma, beta, bias2, eps: float, act: int = 0):
+    def test_gemm_ln(cls, A1, W1, bias1, resid, W2, gamma, beta, bias2, eps: float, act: int = 0, consumer_out: str = "f32",
+                     operands: bool = False):
         """x = A1.W1^T + bias1 + resid; y = act(LayerNorm(x; gamma, beta).W2^T + bias2), with the LayerNorm folded into
-        the second GEMM the way SamWeights does it (csrc/sam_model.cpp, Loader::linear_ln_h).  Returns (x, x as f16, y)."""
+        the second GEMM the way SamWeights does it (csrc/sam_model.cpp, Loader::linear_ln_h).  Returns (x, x as f16, y).
+        consumer_out: "f32" (y fp32), "f16" (the consumer gets out_h only, as qkv and fc1 do in the product; y f16) or "both"
+        (y = (fp32, f16)).  Then additionally returns the producer's row statistics [D / block, M, 2] = (sum, sum of squared
+        deviations from the block mean) per block of `block` columns, and with operands=True the consumer's own operands
+        {"wg": f16 scaled weight, "colsum": fp32, "bias": fp32} as passed to the kernel."""
+        assert consumer_out in ("f32", "f16", "both"), consumer_out
         A1 = np.ascontiguousarray(A1, dtype=np.float16)
         W1 = np.ascontiguousarray(W1, dtype=np.float16)
         M, K1 = A1.shape
@@ -1200,11 +1221,21 @@ class ext:
         resid = None if resid is None else np.ascontiguousarray(resid, dtype=np.float32)
         x = np.empty((M, D), dtype=np.float32)
         xh = np.empty((M, D), dtype=np.float16)
-        y = np.empty((M, N), dtype=np.float32)
+        y = np.empty((M, N), dtype=np.float32) if consumer_out != "f16" else None
+        yh = np.empty((M, N), dtype=np.float16) if consumer_out != "f32" else None
+        stats = np.empty((M * 48,), dtype=np.float32)
+        block = C.c_int(0)
         _check_hook(cls._h().dlimg_amd_test_gemm_ln(M, D, K1, N, A1.ctypes.data, W1.ctypes.data, cls._ptr(bias1),
                                                cls._ptr(resid), wg.ctypes.data, colsum.ctypes.data, b2.ctypes.data,
-                                               eps, act, x.ctypes.data, xh.ctypes.data, y.ctypes.data))
-        return x, xh, y
+                                               eps, act, x.ctypes.data, xh.ctypes.data, cls._ptr(y), cls._ptr(yh),
+                                               stats.ctypes.data, C.byref(block)))
+        if consumer_out == "f32" and not operands:
+            return x, xh, y
+        out = y if consumer_out == "f32" else yh if consumer_out == "f16" else (y, yh)
+        st = stats[:(D // block.value) * M * 2].reshape(D // block.value, M, 2).copy()
+        if operands:
+            return x, xh, out, st, {"wg": wg, "colsum": colsum, "bias": b2}
+        return x, xh, out, st
 
     @classmethod
     def test_lane_worker(cls, tasks: int, sleep_us: int = 0):

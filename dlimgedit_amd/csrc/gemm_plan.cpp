@@ -4,6 +4,13 @@
 namespace dlimg {
 namespace k {
 
+namespace {
+// out_h alone: the ping-pong tiles then run their f16-rows epilogue (qkv, fc1), which takes bias, the folded LayerNorm and
+// GELU in registers and nothing else
+bool f16_rows_only(const GemmArgs& a) { return !a.out_f32 && !a.out_l; }
+bool pingpong_drops(const GemmArgs& a) { return f16_rows_only(a) && (a.resid || a.resid_h || a.stats_out); }
+}  // namespace
+
 const char* gemm_check(const GemmArgs& a) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0) return "gemm: empty problem";
     if (a.M % 64 || a.N % 64 || a.K % kGemmKStep) return "gemm: M, N must be multiples of 64 and K of 64";
@@ -27,6 +34,9 @@ const char* gemm_check(const GemmArgs& a) {
         return "gemm: folded LayerNorm needs aligned column sums and 1..24 statistic groups that divide K";
     if (a.stats_out && (a.ln_stats || a.act != ACT_NONE))
         return "gemm: row statistics cannot be combined with an activation or a folded LayerNorm";
+    // an f16-pair residual runs on the ping-pong tiles only, and their f16-rows epilogue adds no residual (gemm_tile_fits)
+    if (a.resid_h && f16_rows_only(a))
+        return "gemm: an f16-pair residual needs an fp32 or f16-pair result (the f16-only epilogue of the ping-pong tiles adds no residual)";
     return nullptr;
 }
 
@@ -39,6 +49,9 @@ bool gemm_tile_fits(const GemmArgs& a, int tile) {
     const GemmTile& t = kGemmTiles[tile];
     if ((a.out_l || a.resid_h) && !t.pair_stream) return false;          // f16-pair stream: ping-pong epilogue only
     if (a.ln_stats && a.ln_groups > t.stat_groups) return false;         // registers / LDS room for the raw partials
+    // the f16-rows epilogue of the ping-pong kernels reads no residual and computes no row statistics: such problems
+    // (the decoder's final_kv: fp32 residual, f16 result) belong to the ring tiles, which handle both
+    if (t.family == TileFamily::pingpong && pingpong_drops(a)) return false;
     return a.M % t.bm == 0 && a.N % t.bn == 0 && !((a.resid || a.resid_h) && a.resid_mod % t.bm != 0);
 }
 
@@ -115,6 +128,8 @@ int gemm_choose_tile(GemmArgs& a) {
 }
 
 void gemm_no_tile(const GemmArgs& a) {
+    if (a.tile >= 0 && a.tile < kGemmNumTiles && kGemmTiles[a.tile].family == TileFamily::pingpong && pingpong_drops(a))
+        throw_error("gemm: a ping-pong tile with an f16-only result takes no residual and writes no row statistics");
     if (a.out_l || a.resid_h) throw_error("gemm: the f16-pair stream needs a ping-pong tile (N % 256 == 0, shared GPU)");
     throw_error("gemm: no tile configuration fits this shape");
 }

@@ -74,8 +74,9 @@ DLIMG_DEVICE float2_t gelu_pair_erf(float2_t x) {
     return pos - (ax * 0.5f) * q;
 }
 // The fc1 epilogue's form (r05): GELU(x) = x * Phi(x) with Phi(x) ~ sigmoid(x (a + b x^2 + c x^4)), the three constants
-// fitted to the exact erf form (max |error| 2.5e-5 over all x, at |x| ~ 2-3; the result is rounded to f16 right after,
-// whose spacing at those values is 1e-3).  x is clamped to +-8 inside the polynomial (c < 0: the argument would turn
+// fitted to the exact erf form (max |error| 2.519e-5 over all x: an equal-ripple fit with that error at |x| = 0.5645,
+// 1.2928, 2.0703 and 3.0756, the largest by a hair at -0.5645 -- float64 evaluation of these constants,
+// tests/test_gemm_ref.py; the result is rounded to f16 right after, whose spacing at a GELU of 2-3 is 2e-3).  x is clamped to +-8 inside the polynomial (c < 0: the argument would turn
 // round beyond |x| ~ 11; at 8 the sigmoid is 1 - 1e-12 / e^-27 already); the final product takes the unclamped x.
 // Per value 3.5 packed instructions + v_exp_f32 + v_rcp_f32 against 8.5 + v_rcp_f32 above.
 DLIMG_DEVICE float2_t gelu_pair(float2_t x) {

@@ -32,7 +32,14 @@ void apply_forced_tile(k::GemmArgs& g) {
     const int consumer = g_forced_consumer_tile.load(std::memory_order_relaxed);
     const int t = (g.ln_stats && consumer >= 0) ? consumer : g_forced_test_tile.load(std::memory_order_relaxed);
     if (t < 0 || g.tile >= 0) return;
-    if (k::gemm_tile_fits(g, t)) g.tile = t;
+    if (k::gemm_tile_fits(g, t)) { g.tile = t; return; }
+    // A ping-pong tile that would run the shape but whose f16-only epilogue takes no residual and writes no statistics is
+    // NOT replaced by the planner's choice: the launch refuses it (k::gemm_no_tile), so a test sees the refusal.
+    k::GemmArgs bare = g;
+    bare.resid = nullptr; bare.resid_h = bare.resid_l = nullptr; bare.stats_out = nullptr;
+    if (!g.out_f32 && !g.out_l && t < k::kGemmNumTiles && k::kGemmTiles[t].family == k::TileFamily::pingpong &&
+        k::gemm_tile_fits(bare, t))
+        g.tile = t;
 }
 
 }  // namespace
@@ -212,11 +219,19 @@ DLIMG_API int dlimg_amd_test_force_gemm_consumer_tile(int tile) {
     return 0;
 }
 
+DLIMG_API int dlimg_amd_test_gemm_tile_shape(int tile, int* out_bm, int* out_bn) {
+    return guarded([&] {
+        DLIMG_ASSERT(tile >= 0 && tile < k::kGemmNumTiles && out_bm && out_bn);
+        *out_bm = k::kGemmTiles[tile].bm;
+        *out_bn = k::kGemmTiles[tile].bn;
+    });
+}
+
 DLIMG_API int dlimg_amd_test_gemm(int M, int N, int K, uint16_t const* A, uint16_t const* W, float const* bias,
                                   float const* resid, int resid_rows, int act, float* out_f32, uint16_t* out_f16) {
     return guarded([&] {
         require_gpu();
-        DLIMG_ASSERT(M > 0 && N > 0 && K > 0 && A != nullptr && W != nullptr);
+        DLIMG_ASSERT(M > 0 && N > 0 && K > 0 && A != nullptr && W != nullptr && (out_f32 || out_f16));
         Upload<half_t> a(reinterpret_cast<half_t const*>(A), (size_t)M * K);
         Upload<half_t> w(reinterpret_cast<half_t const*>(W), (size_t)N * K);
         Upload<float> b(bias, N);
@@ -240,35 +255,40 @@ DLIMG_API int dlimg_amd_test_gemm(int M, int N, int K, uint16_t const* A, uint16
 DLIMG_API int dlimg_amd_test_gemm_ln(int M, int D, int K1, int N, uint16_t const* A1, uint16_t const* W1,
                                      float const* bias1, float const* resid, uint16_t const* Wg, float const* colsum,
                                      float const* bias2, float eps, int act, float* out_x, uint16_t* out_xh,
-                                     float* out_y) {
+                                     float* out_y, uint16_t* out_yh, float* out_stats, int* out_block) {
     return guarded([&] {
         require_gpu();
         DLIMG_ASSERT(M > 0 && D > 0 && K1 > 0 && N > 0);
-        DLIMG_ASSERT(A1 && W1 && Wg && colsum && out_x && out_xh && out_y);
+        DLIMG_ASSERT(A1 && W1 && Wg && colsum && out_x && out_xh && (out_y || out_yh));
         Upload<half_t> a1(reinterpret_cast<half_t const*>(A1), (size_t)M * K1);
         Upload<half_t> w1(reinterpret_cast<half_t const*>(W1), (size_t)D * K1);
         Upload<half_t> wg(reinterpret_cast<half_t const*>(Wg), (size_t)N * D);
         Upload<float> b1(bias1, bias1 ? D : 0), r(resid, resid ? (size_t)M * D : 0), cs(colsum, N), b2(bias2, bias2 ? N : 0);
-        DeviceBuffer<float> x((size_t)M * D), y((size_t)M * N), stats((size_t)M * k::kGemmMaxStatGroups * 2);
-        DeviceBuffer<half_t> xh((size_t)M * D);
+        DeviceBuffer<float> x((size_t)M * D), y(out_y ? (size_t)M * N : 0), stats((size_t)M * k::kGemmMaxStatGroups * 2);
+        DeviceBuffer<half_t> xh((size_t)M * D), yh(out_yh ? (size_t)M * N : 0);
+        HIP_CHECK(hipMemset(stats.get(), 0, (size_t)M * k::kGemmMaxStatGroups * 2 * sizeof(float)));
         k::GemmArgs g;      // producer: writes the stream, its f16 copy and the per-tile row statistics
         g.A = a1.get(); g.lda = K1; g.W = w1.get(); g.ldw = K1; g.bias = bias1 ? b1.get() : nullptr;
         g.resid = resid ? r.get() : nullptr; g.ldr = D; g.resid_mod = M;
         g.out_f32 = x.get(); g.ldc32 = D; g.out_h = xh.get(); g.ldc16 = D; g.stats_out = stats.get();
         g.M = M; g.N = D; g.K = K1;
         apply_forced_tile(g);
-        const int groups = D / k::gemm_choose_tile(g);
+        const int block = k::gemm_choose_tile(g), groups = D / block;
         k::gemm(g, nullptr);
-        g = k::GemmArgs{};  // consumer: LayerNorm folded in
+        g = k::GemmArgs{};  // consumer: LayerNorm folded in; fp32 result, f16 only (what qkv and fc1 run) or both
         g.A = xh.get(); g.lda = D; g.W = wg.get(); g.ldw = D; g.bias = bias2 ? b2.get() : nullptr;
         g.ln_stats = stats.get(); g.ln_groups = groups; g.ln_colsum = cs.get(); g.ln_eps = eps;
-        g.out_f32 = y.get(); g.ldc32 = N; g.M = M; g.N = N; g.K = D; g.act = act;
+        g.out_f32 = out_y ? y.get() : nullptr; g.ldc32 = N; g.out_h = out_yh ? yh.get() : nullptr; g.ldc16 = N;
+        g.M = M; g.N = N; g.K = D; g.act = act;
         apply_forced_tile(g);
         k::gemm(g, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
         download(out_x, x.get(), (size_t)M * D);
         download(reinterpret_cast<half_t*>(out_xh), xh.get(), (size_t)M * D);
-        download(out_y, y.get(), (size_t)M * N);
+        download(out_y, y.get(), out_y ? (size_t)M * N : 0);
+        download(reinterpret_cast<half_t*>(out_yh), yh.get(), out_yh ? (size_t)M * N : 0);
+        download(out_stats, stats.get(), out_stats ? (size_t)M * k::kGemmMaxStatGroups * 2 : 0);
+        if (out_block) *out_block = block;
     });
 }
 

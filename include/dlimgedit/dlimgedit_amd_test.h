@@ -52,7 +52,10 @@ DLIMG_API int dlimg_amd_test_force_gemm_tile(int tile);
 /* A separate tile for the LayerNorm-folded consumer GEMM of dlimg_amd_test_gemm_ln (< 0: the one forced above); reset by
  * every dlimg_amd_test_force_gemm_tile call. */
 DLIMG_API int dlimg_amd_test_force_gemm_consumer_tile(int tile);
-/* C = epilogue(A[M,K] . W[N,K]^T): bias[N], resid[resid_rows][N] (row m % resid_rows), act 0/1(GELU). */
+/* Rows x columns of tile configuration `tile` (k::kGemmTiles, csrc/gemm_plan.hpp).  No GPU needed. */
+DLIMG_API int dlimg_amd_test_gemm_tile_shape(int tile, int* out_bm, int* out_bn);
+/* C = epilogue(A[M,K] . W[N,K]^T): bias[N], resid[resid_rows][N] (row m % resid_rows), act 0/1(GELU).  out_f32 or out_f16
+ * may be NULL: the launch then gets the other result only (out_f16 alone: the f16-only epilogues). */
 DLIMG_API int dlimg_amd_test_gemm(int M, int N, int K, uint16_t const* A, uint16_t const* W, float const* bias,
                                   float const* resid, int resid_rows, int act, float* out_f32, uint16_t* out_f16);
 /* One stream-writing GEMM of the encoder, x = A[M,K] . W[D,K]^T + bias + (resid_hi + resid_lo), with its per-tile row
@@ -66,11 +69,14 @@ DLIMG_API int dlimg_amd_test_gemm_stream(int M, int D, int K, uint16_t const* A,
  *   x = A1[M,K1] . W1[D,K1]^T + bias1 + resid[M,D]        -> out_x [M,D] fp32 and out_xh [M,D] f16
  *   y = act(rstd * (xh . Wg[N,D]^T - mean * colsum[N]) + bias2[N])   -> out_y [M,N]; mean / rstd of the rows of x,
  *       merged from the per-tile statistics the first GEMM leaves
- * Wg = W * diag(gamma) in f16, colsum = row sums of Wg, bias2 = b + W.beta: prepared by the caller. */
+ * Wg = W * diag(gamma) in f16, colsum = row sums of Wg, bias2 = b + W.beta: prepared by the caller.
+ * The consumer writes out_y (fp32), out_yh (f16) or both, whichever is not NULL: out_yh alone is the launch qkv and fc1 are in
+ * the product.  out_stats (may be NULL): the producer's row statistics, M * 24 * 2 floats laid out [D / block][M][2] =
+ * (sum, sum of squared deviations from the block mean), with *out_block the producer's tile width. */
 DLIMG_API int dlimg_amd_test_gemm_ln(int M, int D, int K1, int N, uint16_t const* A1, uint16_t const* W1,
                                      float const* bias1, float const* resid, uint16_t const* Wg, float const* colsum,
                                      float const* bias2, float eps, int act, float* out_x, uint16_t* out_xh,
-                                     float* out_y);
+                                     float* out_y, uint16_t* out_yh, float* out_stats, int* out_block);
 /* ---- single-kernel hooks (host buffers in and out; device memory handled inside) ------------- */
 DLIMG_API int dlimg_amd_test_layernorm(float const* x, float const* w, float const* b, float eps, int rows, int dim,
                                        int act, float* out_f32, uint16_t* out_f16);

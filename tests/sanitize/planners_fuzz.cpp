@@ -78,6 +78,8 @@ static const char* fuzz_gemm_plan_once(int* valid) {
         if (a.M % row.bm || a.N % row.bn || ((a.resid || a.resid_h) && a.resid_mod % row.bm)) return "a tile that fits does not divide the problem";
         if ((a.out_l || a.resid_h) && !(row.pair_stream && is_pingpong(t))) return "f16-pair stream on a tile without the ping-pong epilogue";
         if (a.ln_stats && a.ln_groups > row.stat_groups) return "more statistic groups than the tile merges";
+        if (is_pingpong(t) && !a.out_f32 && !a.out_l && (a.resid || a.resid_h || a.stats_out))
+            return "a residual or row statistics on a ping-pong tile's f16-rows epilogue, which has neither";
     }
     k::GemmArgs once = a;
     try {
