@@ -876,6 +876,8 @@ class ext:
                 "dlimg_amd_test_resize": ([vp, ci, ci, ci, ci, ci, ci, vp], ci),
                 "dlimg_amd_test_decode": ([vp, ci, vp, ci, vp, vp, vp, vp, vp], ci),
                 "dlimg_amd_test_decode_prompts": ([vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.c_char_p, ci], ci),
+                "dlimg_amd_test_encoder_state": ([vp, C.POINTER(_ImageView), ci, ci, vp, C.c_longlong, C.c_char_p, ci, ci, vp,
+                                                  C.c_longlong, C.c_char_p, ci], ci),
                 "dlimg_amd_bench_attention": ([ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_prepost": ([ci, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], ci),
                 "dlimg_amd_bench_gemm": ([ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
@@ -902,6 +904,7 @@ class ext:
                "dlimg_amd_test_force_gemm_consumer_tile", "dlimg_amd_test_gemm", "dlimg_amd_test_gemm_ln",
                "dlimg_amd_test_lane_worker", "dlimg_amd_test_gemm_stream", "dlimg_amd_test_layernorm",
                "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_test_decode_prompts",
+               "dlimg_amd_test_encoder_state",
                "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps", "dlimg_amd_test_gemm_tile_shape")
@@ -1463,6 +1466,37 @@ class ext:
             res[n] = state[off:off + cnt].copy()
             off += cnt
         return logits, iou, res
+
+    @staticmethod
+    def _named_parts(layout: bytes, flat: np.ndarray) -> dict:
+        res, off = {}, 0
+        for n, cnt in ((n, int(cnt)) for n, cnt in (item.split(":") for item in layout.decode().strip(",").split(","))):
+            res[n] = flat[off:off + cnt].copy()
+            off += cnt
+        return res
+
+    @classmethod
+    def test_encoder_state(cls, env: Environment, images, image: int = 0, layer: Optional[int] = None):
+        """The product's encoder (upload + one SamModel::encode on lane 0) on `images` (1 to 4 RGBA uint8 arrays or ImageViews
+        whose longest side is 1024) and what it left for image `image` of that pass, {name: float32 array}: patches, stream_hi,
+        stream_lo, stats ([groups][4096][2] flat), qkv and hidden of the last block, embedding, groups, split, nonfinite.
+        layer (None: not asked for): additionally the loader's device operands of that block (-1: patch embed, pos_embed and
+        neck) as a second dict; images may then be empty, and the first result is None."""
+        views = [v if isinstance(v, ImageView) else ImageView(np.ascontiguousarray(v)) for v in images]
+        D, depth, heads, mlp = cls.model_geometry(env)
+        state = np.empty(4096 * (768 + 5 * D + mlp + 256 + 48) + 3, dtype=np.float32) if views else None
+        operands = None
+        if layer is not None:
+            block = 3 * D * D + D * D + 2 * mlp * D + 12 * D + 2 * mlp + 2 * 127 * (D // heads) + 1
+            other = D * 768 + D + 4096 * D + 256 * D + 256 * 2304 + 4 * 256
+            operands = np.empty(other if layer < 0 else block, dtype=np.float32)
+        arr = (_ImageView * max(1, len(views)))(*[v._c() for v in views])
+        layout, op_layout = C.create_string_buffer(1024), C.create_string_buffer(1024)
+        _check_hook(cls._h().dlimg_amd_test_encoder_state(
+            env.handle(), arr, len(views), int(image), cls._ptr(state), 0 if state is None else state.size, layout, 1024,
+            -2 if layer is None else int(layer), cls._ptr(operands), 0 if operands is None else operands.size, op_layout, 1024))
+        taps = cls._named_parts(layout.value, state) if views else None
+        return taps if layer is None else (taps, cls._named_parts(op_layout.value, operands))
 
     @classmethod
     def test_resize(cls, pixels: np.ndarray, channels: Channels, out_w: int, out_h: int) -> np.ndarray:

@@ -10,7 +10,7 @@ Five libraries (and the tuning build) come out of the same sources:
                               dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h) the parity tests and the
                               kernels-alone timing loops call; built by default next to the product
   lib/libdlimgedit_neck_test.so  the product's OBJECTS plus csrc/neck_test_hooks.cpp: the hooks of the two encoder-neck launches
-                              (tests/test_gpu_neck.py), in a library of their own because the set of hooks the test library
+                              (tests/test_gpu_neck.py) in a library of their own because the set of hooks the test library
                               exports is pinned (tests/test_abi.py); built by default next to the other two
   lib/libdlimgedit_cleanup_test.so  the product's OBJECTS plus csrc/cleanup_test_hooks.cpp: the hook of the mask clean-up
                               kernels alone (tests/test_gpu_cleanup.py), a library of its own for the same reason; built by default

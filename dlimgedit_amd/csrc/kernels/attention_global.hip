@@ -341,8 +341,14 @@ __global__ __launch_bounds__(512, 2) void attention_global_kernel(const half_t* 
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float p = (ABL & 1) ? s[jt][st * 8 + e] : __builtin_amdgcn_exp2f(s[jt][st * 8 + e]);
-                    ps[e & 3] += p;
                     pf[jt][st][e] = (half_t)p;
+                    // the row sum is that of the ROUNDED probabilities, the ones V is multiplied by: numerator and denominator
+                    // err alike, which cancels in what the keys' values have in common; v_dot2_f32_f16 with (1, 1) adds two.
+                    // (f16-subnormal probabilities count in the sum as they do in the MFMA: tests/test_gpu_attention.py,
+                    // test_global_p_at_the_edge_of_f16, puts 1.8 % of the mass there and still measures 1.000)
+                    if (e & 1)
+                        ps[e >> 1] = __builtin_amdgcn_fdot2(half2_t{pf[jt][st][e - 1], pf[jt][st][e]}, half2_t{(half_t)1.f, (half_t)1.f},
+                                                            ps[e >> 1], false);
                 }
         return (ps[0] + ps[1]) + (ps[2] + ps[3]);
     };

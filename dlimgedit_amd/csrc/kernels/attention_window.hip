@@ -322,13 +322,19 @@ __global__ __launch_bounds__(448, 4) void attention_window_kernel(const half_t* 
         for (int r = 0; r < 16; ++r) {
             const float pv = __builtin_amdgcn_exp2f(__builtin_fmaf(t[r], c, mc));
             t[r] = pv;
-            l += pv;
         }
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
             half8_t pf;
 #pragma unroll
             for (int e = 0; e < 8; ++e) pf[e] = (half_t)t[st * 8 + e];
+            // The row sum is that of the ROUNDED probabilities, the ones V is multiplied by: numerator and denominator then err
+            // alike and the error cancels in whatever the keys' values have in common (tests/test_gpu_encoder.py, S2).  One
+            // v_dot2_f32_f16 with (1, 1) adds two of them to the fp32 sum: half the instructions of adding the fp32 values.
+            // (f16-subnormal inputs are kept by it as by the MFMA: test_global_p_at_the_edge_of_f16 holds the global kernel, which
+            // sums the same way, to that.)
+#pragma unroll
+            for (int e = 0; e < 8; e += 2) l = __builtin_amdgcn_fdot2(half2_t{pf[e], pf[e + 1]}, half2_t{(half_t)1.f, (half_t)1.f}, l, false);
             const int key0 = jt * 32 + st * 16;         // element e <-> key0 + 4*hi + 8*(e>>2) + (e&3)
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {

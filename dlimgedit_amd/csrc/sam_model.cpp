@@ -395,6 +395,8 @@ void SamModel::run_staged_resizes(int batch) {
     if (!now.empty()) resize_into_patches(now.data(), (int)now.size());
 }
 
+// (Diagnostics: encoder_stat_groups() below restates the arguments writes_stream / stream_residual give the LAST fc2 launch in
+// order to ask the planner for its tile again.  Whoever changes those arguments here changes them there.)
 void SamModel::encode(int batch, float* const* emb_dst) {
     SamWeights const& W = *weights_;
     DLIMG_ASSERT(batch > 0 && batch <= enc_batch_);
@@ -904,6 +906,117 @@ void SamModel::decoder_state(float* out, int tokens, bool with_mask_h, bool with
     for (auto const& part : decoder_state_layout(tokens, with_mask_h, with_hq)) {
         HIP_CHECK(hipMemcpy(out + off, src[i++], part.second * sizeof(float), hipMemcpyDeviceToHost));
         off += part.second;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// encoder diagnostics: read-only views of the workspaces and of the loaded operands
+
+namespace {
+
+void download_widened(float* out, half_t const* h, float const* f, size_t n, std::vector<half_t>& tmp) {
+    if (!n) return;
+    if (f) {
+        HIP_CHECK(hipMemcpy(out, f, n * sizeof(float), hipMemcpyDeviceToHost));
+        return;
+    }
+    tmp.resize(n);
+    HIP_CHECK(hipMemcpy(tmp.data(), h, n * sizeof(half_t), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = (float)tmp[i];
+}
+
+}  // namespace
+
+// The tile column blocks of the pass's last stream writer (fc2 of the last block): the arguments encode() gives that launch,
+// through the same planner call.  A RECOMPUTATION, not a record of what the launch used (encode() keeps the number in a local):
+// it follows encode() only as long as the arguments below restate writes_stream / stream_residual there.  What holds the
+// statistics' layout to the launch itself is the comparison of their values (gemm_ref.check_statistics at bn = 256).
+int SamModel::encoder_stat_groups(int batch) const {
+    SamWeights const& W = *weights_;
+    if (!W.fused_ln_) return 0;
+    const int D = W.geom_.embed_dim, mlp = W.geom_.mlp_dim, M = batch * kTokens;
+    LinearH const& fc2 = W.layers_.back().fc2;
+    k::GemmArgs a;
+    a.A = hid_.get(); a.lda = mlp; a.W = fc2.w.get(); a.ldw = mlp; a.bias = fc2.b.get(); a.K = mlp;
+    if (split_stream_) { a.resid_h = xn_.get(); a.resid_l = xlo_.get(); a.ldrs = D; a.out_l = xlo_.get(); }
+    else { a.resid = x_.get(); a.ldr = D; a.out_f32 = x_.get(); a.ldc32 = D; }
+    a.resid_mod = M; a.M = M; a.N = D;
+    a.out_h = xn_.get(); a.ldc16 = D; a.stats_out = xstat_.get();
+    plan_inputs(a, shared_gpu_, alone_);
+    return D / k::gemm_choose_tile(a);
+}
+
+std::vector<std::pair<std::string, size_t>> SamModel::encoder_state_layout(int batch) const {
+    DLIMG_ASSERT(batch > 0 && batch <= enc_batch_);
+    const size_t T = kTokens, D = weights_->geom_.embed_dim, mlp = weights_->geom_.mlp_dim;
+    return {{"patches", T * kPatchK}, {"stream_hi", T * D}, {"stream_lo", T * D}, {"stats", (size_t)encoder_stat_groups(batch) * T * 2},
+            {"qkv", T * 3 * D}, {"hidden", T * mlp}, {"embedding", T * kEmbedDim}, {"groups", 1}, {"split", 1}, {"nonfinite", 1}};
+}
+
+void SamModel::encoder_state(float* out, int image, int batch) const {
+    DLIMG_ASSERT(out != nullptr && batch > 0 && batch <= enc_batch_ && image >= 0 && image < batch && pass_flag_ != nullptr);
+    const size_t T = kTokens, D = weights_->geom_.embed_dim, mlp = weights_->geom_.mlp_dim, M = (size_t)batch * T, row0 = (size_t)image * T;
+    const int groups = encoder_stat_groups(batch);
+    std::vector<half_t> tmp;
+    size_t off = 0;
+    auto take = [&](half_t const* h, float const* f, size_t n) { download_widened(out + off, h, f, n, tmp); off += n; };
+    take(patches_.get() + row0 * kPatchK, nullptr, T * kPatchK);
+    float* const hi = out + off;
+    take(xn_.get() + row0 * D, nullptr, T * D);
+    float* const lo = out + off;
+    if (split_stream_) {
+        take(xlo_.get() + row0 * D, nullptr, T * D);
+    } else {
+        take(nullptr, x_.get() + row0 * D, T * D);
+        for (size_t i = 0; i < T * D; ++i) lo[i] -= hi[i];
+    }
+    for (int g = 0; g < groups; ++g) take(nullptr, xstat_.get() + ((size_t)g * M + row0) * 2, T * 2);
+    take(qkv_.get() + row0 * 3 * D, nullptr, T * 3 * D);
+    take(hid_.get() + row0 * mlp, nullptr, T * mlp);
+    take(nullptr, emb_.get() + row0 * kEmbedDim, T * kEmbedDim);
+    out[off++] = (float)groups;
+    out[off++] = split_stream_ ? 1.f : 0.f;
+    out[off++] = (float)*pass_flag_;
+}
+
+std::vector<SamModel::DeviceTap> SamModel::encoder_operand_taps(int layer) const {
+    SamWeights const& W = *weights_;
+    DLIMG_ASSERT(layer >= -1 && layer < (int)W.layers_.size());
+    const size_t D = W.geom_.embed_dim, mlp = W.geom_.mlp_dim, hd = W.geom_.head_dim();
+    const size_t folded = W.fused_ln_ ? 1 : 0;
+    if (layer < 0)
+        return {{"patch.w", W.patch_.w.get(), nullptr, D * kPatchK}, {"patch.b", nullptr, W.patch_.b.get(), D},
+                {"pos_embed", nullptr, W.pos_embed_.get(), (size_t)kTokens * D},
+                {"neck1.w", W.neck1_.w.get(), nullptr, (size_t)kEmbedDim * D},
+                {"neck_ln1.w", nullptr, W.neck_ln1_.w.get(), kEmbedDim}, {"neck_ln1.b", nullptr, W.neck_ln1_.b.get(), kEmbedDim},
+                {"neck2.w", W.neck2_.w.get(), nullptr, (size_t)kEmbedDim * 9 * kEmbedDim},
+                {"neck_ln2.w", nullptr, W.neck_ln2_.w.get(), kEmbedDim}, {"neck_ln2.b", nullptr, W.neck_ln2_.b.get(), kEmbedDim}};
+    EncoderLayer const& L = W.layers_[layer];
+    const size_t rel = (size_t)(2 * (L.global ? 64 : 14) - 1) * hd;
+    return {{"qkv.w", L.qkv.w.get(), nullptr, 3 * D * D}, {"qkv.b", nullptr, L.qkv.b.get(), 3 * D},
+            {"qkv.colsum", nullptr, L.qkv.colsum.get(), folded * 3 * D},
+            {"fc1.w", L.fc1.w.get(), nullptr, mlp * D}, {"fc1.b", nullptr, L.fc1.b.get(), mlp},
+            {"fc1.colsum", nullptr, L.fc1.colsum.get(), folded * mlp},
+            {"proj.w", L.proj.w.get(), nullptr, D * D}, {"proj.b", nullptr, L.proj.b.get(), D},
+            {"fc2.w", L.fc2.w.get(), nullptr, D * mlp}, {"fc2.b", nullptr, L.fc2.b.get(), D},
+            {"rel_h16", L.rel_h16.get(), nullptr, rel}, {"rel_w16", L.rel_w16.get(), nullptr, rel},
+            {"qkv_pad", L.qkv_pad.get(), nullptr, L.global ? 0 : 3 * D}, {"global", nullptr, nullptr, 1}};
+}
+
+std::vector<std::pair<std::string, size_t>> SamModel::encoder_operands_layout(int layer) const {
+    std::vector<std::pair<std::string, size_t>> parts;
+    for (DeviceTap const& t : encoder_operand_taps(layer)) parts.emplace_back(t.name, t.n);
+    return parts;
+}
+
+void SamModel::encoder_operands(float* out, int layer) const {
+    DLIMG_ASSERT(out != nullptr);
+    std::vector<half_t> tmp;
+    size_t off = 0;
+    for (DeviceTap const& t : encoder_operand_taps(layer)) {
+        if (t.name == "global") out[off] = weights_->layers_[layer].global ? 1.f : 0.f;
+        else download_widened(out + off, t.h, t.f, t.n, tmp);
+        off += t.n;
     }
 }
 

@@ -225,6 +225,22 @@ class SamModel {
     static std::vector<std::pair<const char*, size_t>> decoder_state_layout(int tokens, bool with_mask_h = false, bool with_hq = false);
     void decoder_state(float* out, int tokens, bool with_mask_h = false, bool with_hq = false) const;
     float const* iou() const { return iou_.get(); }
+    // Diagnostic, the encoder's counterpart: what the last encode() of `batch` images left in this lane's workspaces for
+    // image `image` of that pass (after synchronize()), one after the other as floats (f16 tensors widened, which is exact);
+    // names/sizes in encoder_state_layout().  "patches" [4096][768]; "stream_hi" / "stream_lo" [4096][D]: the residual stream
+    // behind the last block as the pair xn_ + xlo_ (fp32 stream: hi its f16 copy, lo = x - hi in fp32); "stats"
+    // [groups][4096][2]: the row statistics the last stream writer left for these rows; "qkv" [4096][3 D] and "hidden"
+    // [4096][mlp] of the last block; "embedding" [4096][256]; then one float each: "groups" (tile column blocks of the last
+    // stream writer, from the same planner call encode() makes), "split" (1: the f16-pair stream) and "nonfinite" (the pass's
+    // overflow report).  Reads only: encode() and its launches know nothing of it.
+    std::vector<std::pair<std::string, size_t>> encoder_state_layout(int batch) const;
+    void encoder_state(float* out, int image, int batch) const;
+    // The device operands of encoder layer `layer` as the loader left them (folded, scaled, rounded), widened to floats:
+    // qkv.w / .b / .colsum, fc1.w / .b / .colsum, proj.w / .b, fc2.w / .b, rel_h16, rel_w16, qkv_pad (windowed layers; empty
+    // for global ones), "global" (one float).  layer == -1: patch.w / .b, pos_embed, neck1.w, neck_ln1.w / .b, neck2.w,
+    // neck_ln2.w / .b.  colsum entries are empty when the LayerNorms are not folded.
+    std::vector<std::pair<std::string, size_t>> encoder_operands_layout(int layer) const;
+    void encoder_operands(float* out, int layer) const;
 
     // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):
     // acquire_mask_slot (no mutex needed; callers hold the slot as a MaskSlotLease, below), enqueue_masks with the first
@@ -293,6 +309,9 @@ class SamModel {
     void hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
     template <typename F> void neck_launch(double flops, F&& launch);     // launch(start, stop): one of k::neck_conv*_ln
+    struct DeviceTap { std::string name; half_t const* h; float const* f; size_t n; };      // one of h / f; n elements
+    std::vector<DeviceTap> encoder_operand_taps(int layer) const;
+    int encoder_stat_groups(int batch) const;
 
     int device_ = 0;
     bool shared_gpu_ = false;            // other lanes run on this device too (GEMM tile choice, gemm_plan.cpp)

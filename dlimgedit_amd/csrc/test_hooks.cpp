@@ -10,6 +10,7 @@
 
 #include <dlimgedit/dlimgedit_amd_test.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -485,6 +486,59 @@ DLIMG_API int dlimg_amd_test_decode_prompts(dlimg_Environment env, int n_emb, fl
         download(out_logits, m.logits(), (size_t)count * planes);
         download(out_iou, m.iou(), (size_t)count * 4);
         if (out_state) m.decoder_state(out_state, tokens, masked);
+    });
+}
+
+DLIMG_API int dlimg_amd_test_encoder_state(dlimg_Environment env, dlimg_ImageView const* images, int count, int image,
+                                           float* out_state, long long state_capacity, char* out_layout, int layout_capacity,
+                                           int layer, float* out_operands, long long operands_capacity,
+                                           char* out_operands_layout, int operands_layout_capacity) {
+    return guarded([&] {
+        // every refusal is a host check in front of the first launch
+        if (count < 0 || count > 4) throw Exception("test_encoder_state: a pass takes 1 to 4 images (0: the operands only)");
+        if (count > 0 && (!images || !out_state || image < 0 || image >= count))
+            throw Exception("test_encoder_state: a pass needs its images, the index of one of them and a state buffer");
+        if (count == 0 && out_state) throw Exception("test_encoder_state: a state without a pass");
+        for (int i = 0; i < count; ++i) {
+            dlimg_ImageView const& v = images[i];
+            if (!v.pixels || v.channels != 4 || v.width < 1 || v.height < 1 || v.width > kImageSize || v.height > kImageSize ||
+                std::max(v.width, v.height) != kImageSize || v.stride < v.width * 4)
+                throw Exception("test_encoder_state: RGBA images whose longest side is 1024 (no resize in front of this pass)");
+        }
+        if (layer < -2) throw Exception("test_encoder_state: layer is -2 (no operands), -1 (patch embed and neck) or a block's index");
+        if (layer > -2 && !out_operands) throw Exception("test_encoder_state: operands asked for without a buffer");
+        auto describe = [](std::vector<std::pair<std::string, size_t>> const& parts, float const* buffer, long long capacity,
+                           char* text, int text_capacity, const char* what) {
+            std::string layout;
+            size_t floats = 0;
+            for (auto const& part : parts) {
+                layout += part.first + ":" + std::to_string(part.second) + ",";
+                floats += part.second;
+            }
+            if (text && text_capacity > 0) {
+                if (layout.size() + 1 > (size_t)text_capacity) throw Exception(std::string("test_encoder_state: the layout text of the ") + what + " does not fit");
+                std::snprintf(text, (size_t)text_capacity, "%s", layout.c_str());
+            }
+            if (buffer && (capacity < 0 || (size_t)capacity < floats))
+                throw Exception(std::string("test_encoder_state: the buffer of the ") + what + " is too small");
+        };
+        // the product's encoder on lane 0 of replica 0, as a synchronous caller runs it: upload, one encode() for the pass
+        SamModel& m = impl(env).lane(0, 0);
+        std::lock_guard<std::mutex> lock(m.mutex());
+        HIP_CHECK(hipSetDevice(m.device()));
+        if (layer > -2) {
+            if (layer >= m.geometry().depth) throw Exception("test_encoder_state: the model has no such block");
+            describe(m.encoder_operands_layout(layer), out_operands, operands_capacity, out_operands_layout, operands_layout_capacity, "operands");
+            m.encoder_operands(out_operands, layer);
+        }
+        if (count == 0) return;
+        for (int i = 0; i < count; ++i)
+            m.upload_image(i, count, images[i].pixels, images[i].width, images[i].height, images[i].stride, images[i].channels);
+        m.encode(count, nullptr);
+        m.synchronize();
+        m.wait_caller_copies();
+        describe(m.encoder_state_layout(count), out_state, state_capacity, out_layout, layout_capacity, "state");
+        m.encoder_state(out_state, image, count);
     });
 }
 

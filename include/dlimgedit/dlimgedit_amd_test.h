@@ -103,6 +103,20 @@ DLIMG_API int dlimg_amd_test_decode_prompts(dlimg_Environment env, int n_emb, fl
                                             int points, float const* coords, float const* labels, float const* mask_planes,
                                             float const* mask_iou, float* out_logits, float* out_iou, float* out_state,
                                             int state_capacity, char* out_layout, int layout_capacity);
+/* The product's image encoder on lane 0 of env's first replica, and a read-only view of what it left: upload + ONE
+ * SamModel::encode for `count` (1 .. 4) RGBA images whose longest side is 1024, then the workspaces' contents for image
+ * `image` of the pass as floats (f16 tensors widened) in out_state, names and sizes in out_layout ("name:floats,..."):
+ * patches [4096][768], stream_hi / stream_lo [4096][D] (the residual stream behind the last block), stats [groups][4096][2]
+ * (as the last stream writer left them), qkv [4096][3 D] and hidden [4096][mlp] of the last block, embedding [4096][256],
+ * then one float each: groups, split (1: the f16-pair stream), nonfinite (the pass's overflow report).
+ * layer > -2: additionally (count == 0: only) the device operands the loader left, in out_operands / out_operands_layout:
+ * of block `layer` qkv.w / .b / .colsum, fc1.w / .b / .colsum, proj.w / .b, fc2.w / .b, rel_h16, rel_w16, qkv_pad (empty for a
+ * global block), global; of layer -1 patch.w / .b, pos_embed, neck1.w, neck_ln1.w / .b, neck2.w, neck_ln2.w / .b.
+ * Refused: counts and indices out of range, other image formats or sizes, null pointers, buffers too small. */
+DLIMG_API int dlimg_amd_test_encoder_state(dlimg_Environment env, dlimg_ImageView const* images, int count, int image,
+                                           float* out_state, long long state_capacity, char* out_layout, int layout_capacity,
+                                           int layer, float* out_operands, long long operands_capacity,
+                                           char* out_operands_layout, int operands_layout_capacity);
 /* K17: the stb_image_resize-equivalent longest-side resampler (default filter, sRGB, clamp):
  * pixels [height][stride] -> out_pixels [out_h][out_w * bytes_per_pixel] packed. */
 DLIMG_API int dlimg_amd_test_resize(uint8_t const* pixels, int width, int height, int stride, int channels, int out_w,

@@ -159,7 +159,11 @@ def consumer(A16, Wg16, colsum32, bias32, x32, eps: float = EPS, act: int = 0) -
 
 
 def output_model(ref, fmt: str = "f32") -> np.ndarray:
-    """The rounding model: the reference rounded once to the output's format."""
+    """The rounding model: the reference rounded once to the output's format.  "pair": the residual stream as an f16 pair
+    (kernels.hpp, GemmArgs::out_l), hi = f16(v), lo = f16(v - hi), value hi + lo."""
+    if fmt == "pair":
+        hi = round_f16(ref)
+        return hi + round_f16(np.asarray(ref, f64) - hi)
     return round_f16(ref) if fmt == "f16" else round_f32(ref)
 
 

@@ -64,7 +64,8 @@ def test_only_declared_dlimg_symbols_are_exported(api):
     # 22 hooks: the 20 first ones plus dlimg_amd_test_decode (the decoder on given embeddings, tests/test_gpu_decoder.py) and
     # dlimg_amd_test_decode_prompts (any number of points, mask input, state: tests/test_gpu_decoder_prompts.py)
     # ... and dlimg_amd_test_gemm_tile_shape (the tile table for tests/test_gpu_gemm.py, so that no test restates it)
-    assert len(api.ext.HOOK_EXPORTS) == 23 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
+    # ... and dlimg_amd_test_encoder_state (the encoder's buffers and loaded operands, read only: tests/test_gpu_encoder.py)
+    assert len(api.ext.HOOK_EXPORTS) == 24 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
 
 
 def test_hooks_come_from_the_test_library_not_the_product(api):

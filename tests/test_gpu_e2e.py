@@ -6,6 +6,8 @@ import pytest
 from conftest import (EMB_TOL, IOU_BAR, IOU_PRED_TOL, LOGIT_TOL, at_least, iou, single_mask_index, synthetic_image,
                       within)
 
+from encoder_cases import hard_edged_image as _hard_edged_image
+
 pytestmark = pytest.mark.gpu
 
 
@@ -483,29 +485,6 @@ def test_trained_like_activation_statistics(api, tmp_path_factory, monkeypatch, 
         env.close()
     # folding the LayerNorm in must not cost more than a small multiple of the separate kernels' own f16 error
     assert errs["1"] <= 3.0 * errs["0"] + 5e-3, errs
-
-
-def _hard_edged_image(seed: int, width: int = 1024, height: int = 1024) -> np.ndarray:
-    """A second family of synthetic inputs (every other test uses low-frequency sinusoids + noise): flat-coloured rectangles
-    and discs with hard edges on a gradient, saturated regions (0 and 255), a one-pixel checkerboard patch -- step
-    edges, clipping and the highest spatial frequency a patch embedding can see."""
-    rng = np.random.default_rng(5000 + seed)
-    yy, xx = np.mgrid[0:height, 0:width]
-    img = np.zeros((height, width, 4), np.uint8)
-    for c in range(3):
-        img[:, :, c] = (xx * (c + 1) * 255 // (3 * max(1, width - 1)) + yy * 40 // max(1, height - 1)).astype(np.uint8)
-    for _ in range(14):
-        x0, y0 = rng.integers(0, width - 40), rng.integers(0, height - 40)
-        w, h = rng.integers(30, 400), rng.integers(30, 400)
-        img[y0:y0 + h, x0:x0 + w, :3] = rng.integers(0, 256, 3)
-    for _ in range(8):
-        cx, cy, r = rng.integers(0, width), rng.integers(0, height), rng.integers(20, 180)
-        img[(xx - cx) ** 2 + (yy - cy) ** 2 < r * r, :3] = rng.integers(0, 256, 3)
-    img[100:260, 700:900, :3] = 255
-    img[800:960, 80:300, :3] = 0
-    img[400:528, 400:528, :3] = (((xx[400:528, 400:528] + yy[400:528, 400:528]) & 1) * 255)[:, :, None]
-    img[:, :, 3] = 255
-    return img
 
 
 @pytest.mark.parametrize("seed", [0, 1])
