@@ -226,6 +226,30 @@ def grid_hooks_library() -> C.CDLL:
     return _grid_hooks_lib
 
 
+_prior_hooks_lib = None
+PRIOR_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_prior_test.so")
+# the hook of the prior-plane kernel alone (csrc/prior_test_hooks.cpp): bound by name, no header declares it
+PRIOR_HOOK_EXPORTS = ("dlimg_amd_test_prior_plane",)
+
+
+def prior_hooks_library() -> C.CDLL:
+    """Loads lib/libdlimgedit_prior_test.so: the product's objects plus the hook of the prior-plane kernel.  Raises if it has
+    not been built; there is no fallback."""
+    global _prior_hooks_lib
+    if _prior_hooks_lib is None:
+        if not PRIOR_HOOKS_LIB_PATH.exists():
+            raise Error(f"{PRIOR_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+        lib = C.CDLL(str(PRIOR_HOOKS_LIB_PATH))
+        lib.dlimg_init.restype = C.POINTER(_Api)
+        lib.dlimg_init.argtypes = []
+        ci = C.c_int
+        lib.dlimg_amd_test_prior_plane.argtypes = [C.c_void_p, ci, ci, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(ci), ci,
+                                                   C.POINTER(C.c_float)]
+        lib.dlimg_amd_test_prior_plane.restype = ci
+        _prior_hooks_lib = lib
+    return _prior_hooks_lib
+
+
 def _check_neck_hook(result: int) -> None:
     if result != 0:
         msg = neck_hooks_library().dlimg_init().contents.last_error()
@@ -386,6 +410,8 @@ REFINE_MARK = 4              # regions[4 i] of a refinement mark (dlimgedit.h: D
 CLEAN_MARK = 6               # regions[4 i] of a clean-up mark (dlimgedit.h: DLIMG_CLEAN_MARK; csrc/prompt_plan.hpp: kCleanMark)
 GRID_MARK = 7                # regions[4 i] of a grid mark (dlimgedit.h: DLIMG_GRID_MARK; csrc/grid_plan.hpp: kGridMark)
 GRID_MAX_SIDE = 32
+PRIOR_MARK = 8               # regions[4 i] of a prior mark (dlimgedit.h: DLIMG_PRIOR_MARK; csrc/prior_plan.hpp: kPriorMark)
+PRIOR_MAX_STRENGTH = 100000  # strength_milli of a prior mark, at most; 0: the library's default (8000)
 
 
 @dataclass
@@ -405,7 +431,11 @@ class ClickEntries:
     A grid prompt is two entries: a head with EMPTY_REGION and a continuation entry (GRID_MARK, side, iou_permille,
     stability_permille); neither point is read.  grid_sides[j]: the side of prompt j's grid, 0 for any other prompt.  It is
     decoded behind the others in launches of its own (side * side one-click prompts, 16 per launch), which `launches` does
-    not list; token_rows[j] are those of one of its prompts."""
+    not list; token_rows[j] are those of one of its prompts.
+    A prior mark is a continuation entry (PRIOR_MARK, strength_milli, 0, 0) directly behind its head, whose point is not read
+    and whose out_masks pointer is READ: priors[j] is the (h, w) uint8 mask prompt j hands in as SAM's mask input of its first
+    stage, None for a prompt without one.  A prompt with a prior is decoded behind the others like a prompt with marks, its
+    first stage masked too; token_rows and stage_clicks are unchanged."""
     heads: list
     points: list
     regions: list
@@ -413,9 +443,10 @@ class ClickEntries:
     token_rows: list
     stage_clicks: list = field(default_factory=list)
     grid_sides: list = field(default_factory=list)
+    priors: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
-        return j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1
+        return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None)
 
     def _grid(self, j) -> bool:
         return j < len(self.grid_sides) and self.grid_sides[j] > 0
@@ -530,10 +561,53 @@ def _checked_grid(grid, n: int) -> list:
     return [None if g is None else triple(g) for g in grid]
 
 
-def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None):
-    """The `points` / `regions` form of a batch call with clean-up or grid marks as entry lists: entry i of the caller's, then
-    its mark.  -> (index into segs or None per entry, [(x, y)] or None, [(4 ints)]).  A point prompt gets the empty region (no
-    box); a grid prompt is its head with the empty region and its mark (its point and region, if any were given, are not used)."""
+def _checked_prior(prior, prior_strength, n: int) -> list:
+    """`prior` / `prior_strength` of a call of n prompts -> per prompt None or ((h, w) uint8 array, strength_milli): prior is
+    None or one entry (None or an array) per prompt; prior_strength one int for all or one per prompt, 0 .. 100000 (0: the
+    library's default)."""
+    if prior is None:
+        return [None] * n
+    prior = list(prior)
+    if len(prior) != n:
+        raise Error("prior: None, or one entry (None or an (h, w) uint8 array) per prompt")
+    strengths = [prior_strength] * n if isinstance(prior_strength, (int, np.integer)) else list(prior_strength)
+    if len(strengths) != n or not all(isinstance(v, (int, np.integer)) for v in strengths):
+        raise Error("prior_strength: one int for all prompts or one per prompt")
+    out = []
+    for m, v in zip(prior, strengths):
+        if m is None:
+            out.append(None)
+            continue
+        if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.ndim != 2 or not m.flags.c_contiguous:
+            raise Error("prior: a prior is a C-contiguous (h, w) uint8 array of the image's extent")
+        if not 0 <= int(v) <= PRIOR_MAX_STRENGTH:
+            raise Error(f"prior_strength: 0 (the default) .. {PRIOR_MAX_STRENGTH}")
+        out.append((m, int(v)))
+    return out
+
+
+def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list) -> list:
+    """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), None otherwise."""
+    ptrs, head = [], None
+    for e, h in enumerate(heads):
+        if h is not None:
+            head = h
+            ptrs.append(outs_by_head[e].ctypes.data)
+        elif regs[e][0] == PRIOR_MARK and head is not None and priors[head] is not None:
+            m, ext = priors[head][0], segs[head].extent()
+            if m.shape != (ext.height, ext.width):
+                raise Error(f"prior: the prior of prompt {head} is {m.shape[1]} x {m.shape[0]}, its image {ext.width} x {ext.height}")
+            ptrs.append(m.ctypes.data)
+        else:
+            ptrs.append(None)
+    return ptrs
+
+
+def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None):
+    """The `points` / `regions` form of a batch call with clean-up, grid or prior marks as entry lists: entry i of the caller's,
+    then its marks (the prior mark first: it stands directly behind its head).  -> (index into segs or None per entry, [(x, y)]
+    or None, [(4 ints)]).  A point prompt gets the empty region (no box); a grid prompt is its head with the empty region and
+    its mark (its point and region, if any were given, are not used)."""
     heads, pts, regs = [], ([] if points is not None else None), []
     for i in range(n):
         heads.append(i)
@@ -542,6 +616,8 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
         if grid is not None and grid[i] is not None:
             if clean[i] is not None:
                 raise Error("a grid prompt takes no clean-up mark")
+            if prior is not None and prior[i] is not None:
+                raise Error("a grid prompt takes no prior")
             regs.append(EMPTY_REGION)
             heads.append(None)
             if pts is not None:
@@ -550,6 +626,11 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
             continue
         q = None if regions is None else regions[i]
         regs.append(EMPTY_REGION if q is None else (q.top_left.x, q.top_left.y, q.bottom_right.x, q.bottom_right.y))
+        if prior is not None and prior[i] is not None:
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((PRIOR_MARK, prior[i][1], 0, 0))
         if clean[i] is not None:
             heads.append(None)
             if pts is not None:
@@ -566,7 +647,8 @@ def _marked_arrays(segs, heads, pts, regs):
     return n, handles, p, r
 
 
-def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None) -> ClickEntries:
+def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
+                  prior_strength=0) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -574,10 +656,15 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     (max_hole, max_island) pair for every prompt, or per prompt None / a pair -- a clean-up mark behind the prompt's last click.
     grid: None, or per prompt None / (side, iou_permille, stability_permille) -- prompt j is a grid prompt ("segment
     everything"): clicks[j] is None or empty, and it takes no labels, region, refinement or clean-up marks.
+    prior: None, or per prompt None / an (h, w) uint8 mask of the prompt's image -- a prior mark directly behind the head, with
+    prior_strength (one int for all or one per prompt; 0: the library's default) as its strength_milli.  Entry lists without
+    priors are what they were.
     Pure host code."""
     n = len(clicks)
     clean = _checked_clean(clean, n)
     grid = _checked_grid(grid, n)
+    prior = _checked_prior(prior, prior_strength, n)
+    any_prior = any(p is not None for p in prior)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -586,9 +673,12 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     out = ClickEntries([], [], [], [], [])
     for j in range(n):
         out.grid_sides.append(0 if grid[j] is None else grid[j][0])
+        if any_prior:
+            out.priors.append(None if prior[j] is None else prior[j][0])
         if grid[j] is not None:
-            if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None:
-                raise Error("a grid prompt is its grid mark alone: no clicks, labels, region, refinement or clean-up marks")
+            if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None \
+                    or prior[j] is not None:
+                raise Error("a grid prompt is its grid mark alone: no clicks, labels, region, refinement or clean-up marks, no prior")
             out.prompt_heads.append(len(out.heads))
             out.token_rows.append(7)
             out.stage_clicks.append([1])
@@ -613,6 +703,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
                 out.regions.append((lab, 0, 0, 0))
             else:
                 out.regions.append(EMPTY_REGION if r is None else (r.top_left.x, r.top_left.y, r.bottom_right.x, r.bottom_right.y))
+                if prior[j] is not None:     # the prior mark stands directly behind its head
+                    out.heads.append(None)
+                    out.points.append((0, 0))
+                    out.regions.append((PRIOR_MARK, prior[j][1], 0, 0))
         if clean[j] is not None:
             out.heads.append(None)
             out.points.append((0, 0))
@@ -709,24 +803,29 @@ class Segmentation:
 
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
-                            clean=None) -> np.ndarray:
+                            clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
         them: the first k clicks give a mask whose low-res logits are the mask input of the next stage (on the GPU), and so on;
         the mask of the last stage is returned.  Needs a model with the mask branch (pe.mask.*).
         clean: (max_hole, max_island) -- the mask is delivered with background components below max_hole pixels filled and then
-        foreground components below max_island pixels dropped (8-connectivity; the largest island stays when all are below)."""
+        foreground components below max_island pixels dropped (8-connectivity; the largest island stays when all are below).
+        prior: an (h, w) uint8 mask the caller already holds (a selection, the mask of the last query; 0 .. 255 read as
+        coverage) as SAM's mask input of the first stage; it may be `out` itself, a mask refined in place.  prior_strength: the
+        logit a fully covered pixel stands for, in thousandths, 1 .. 100000; 0: the library's default, 8000.  Needs a model
+        with the mask branch."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
                                                out=None if out is None else [out],
                                                refine_after=None if refine_after is None else [refine_after],
-                                               clean=None if clean is None else [tuple(clean)])[0]
+                                               clean=None if clean is None else [tuple(clean)],
+                                               prior=None if prior is None else [prior], prior_strength=prior_strength)[0]
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
-                           clean=None, grid=None) -> list:
+                           clean=None, grid=None, prior=None, prior_strength=0) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -738,7 +837,9 @@ class Segmentation:
         marks, see compute_mask_clicks; a box-only call may carry them too.
         grid (either form): None, or per prompt None / (side, iou_permille, stability_permille) -- prompt i is a grid prompt,
         whose result is a label map (segment_everything); its point, clicks and region are not used (None will do), and with
-        grid prompts alone neither `points` nor `regions` nor `clicks` is needed."""
+        grid prompts alone neither `points` nor `regions` nor `clicks` is needed.
+        prior (either form): None, or per prompt None / an (h, w) uint8 mask of the prompt's image -- prior marks, see
+        compute_mask_clicks; prior_strength one int for all or one per prompt.  A box-only call may carry them too."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -748,11 +849,13 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
-            entries = click_entries(clicks, labels, regions, refine_after, clean, grid)
+            entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
+            priors = _checked_prior(prior, prior_strength, len(segs))
+            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors)
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
-                ptrs = (C.c_void_p * n)(*[out_of[i].ctypes.data if i in out_of else None for i in sel])
+                ptrs = (C.c_void_p * n)(*[all_ptrs[i] for i in sel])
                 _check(api().get_segmentation_masks(handles, n, p, r, ptrs))
             return outs
         n = len(segs)
@@ -760,12 +863,13 @@ class Segmentation:
         assert len(outs) == n and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
         marks = _checked_clean(clean, n)
         grids = _checked_grid(grid, n)
-        if any(m is not None for m in marks) or any(g is not None for g in grids):
+        priors = _checked_prior(prior, prior_strength, n)
+        if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors):
             if points is None and regions is None and any(g is None for g in grids):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
-            ptrs = (C.c_void_p * m)(*[None if h is None else outs[h].ctypes.data for h in heads])
+            ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors))
             _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
             return outs
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
@@ -1339,6 +1443,26 @@ class ext:
             msg = lib.dlimg_init().contents.last_error()
             raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
         return records, out, [int(v) for v in kout[:nk.value]], bool(ok.value), (store if time_iters <= 0 else (ms[0], ms[1]))
+
+    @classmethod
+    def test_prior_plane(cls, mask: np.ndarray, pre_w: int, pre_h: int, strength_milli: int, time_iters: int = 0):
+        """The prior-plane kernel alone (the hook of prior_hooks_library()): mask (h, w) uint8, of an image that was encoded at
+        pre_w x pre_h, through ONE k::mask_prior launch on the default device, with guard bytes around the plane and around the
+        mask's device copy.  -> (plane float32 [256, 256], guard bytes intact); with time_iters > 0 a third element, the
+        milliseconds of one launch (the mean of time_iters repetitions between two events).  A refusal of the launcher raises
+        Error."""
+        mask = np.ascontiguousarray(mask, np.uint8)
+        assert mask.ndim == 2
+        h, w = mask.shape
+        plane = np.zeros((256, 256), np.float32)
+        ok, ms = C.c_int(0), C.c_float(0.0)
+        lib = prior_hooks_library()
+        rc = lib.dlimg_amd_test_prior_plane(mask.ctypes.data, w, h, int(pre_w), int(pre_h), int(strength_milli),
+                                            plane.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ok), int(time_iters), C.byref(ms))
+        if rc != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        return (plane, bool(ok.value)) if time_iters <= 0 else (plane, bool(ok.value), float(ms.value))
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

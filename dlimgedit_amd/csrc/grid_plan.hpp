@@ -51,12 +51,15 @@ inline Point grid_pixel(int width, int height, int side, int i, int j) {
     return Point{int((int64_t)(2 * i + 1) * width / (2 * side)), int((int64_t)(2 * j + 1) * height / (2 * side))};
 }
 
-inline GridPlannedPrompts plan_grid_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch) {
+// had_continuation: as for plan_prompts -- the caller's list held continuation entries that are not in this one (prior marks,
+// prior_plan.hpp).
+inline GridPlannedPrompts plan_grid_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch,
+                                            bool had_continuation = false) {
     const int count = (int)has_handle.size();
     GridPlannedPrompts out;
     for (int i = 0; i < count; ++i) out.any_grid |= !has_handle[i] && is_grid_mark_entry(regions, i);
     if (!out.any_grid) {
-        out.cleaned = plan_cleaned_prompts(has_handle, points_given, regions, mask_branch);
+        out.cleaned = plan_cleaned_prompts(has_handle, points_given, regions, mask_branch, had_continuation);
         out.grid.resize(out.cleaned.staged.prompts.size());
         return out;
     }

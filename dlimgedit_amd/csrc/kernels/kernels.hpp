@@ -375,5 +375,20 @@ struct GridKept { int count; int candidate[kGridMaxKept]; uint32_t cull[kGridMax
 void grid_paint(const float* store, int candidates, const GridKept& kept, uint8_t* dst, int out_w, int out_h, int pre_w, int pre_h,
                 bool cull, hipStream_t);
 
+// ---- prior marks (K19, kernels/mask_prior.hip) ------------------------------------------------
+// A caller's mask as the mask input of a prompt: mask [H][W] u8, tightly packed, values 0 .. 255 read as coverage, of an image
+// that was encoded at pre_w x pre_h -> plane [256][256] fp32 (16-byte aligned), which MaskSource{plane, nullptr} feeds to
+// mask_embed.  With sw = ceil(pre_w / 4), sh = ceil(pre_h / 4), all products in 64 bits:
+//   x < sw:  c0 = floor(4 x W / pre_w),  c1 = ceil(min(4 x + 4, pre_w) W / pre_w)          (c0 < c1 <= W)
+//   y < sh:  r0 = floor(4 y H / pre_h),  r1 = ceil(min(4 y + 4, pre_h) H / pre_h)
+//   sum = sum of mask[r0 .. r1)[c0 .. c1),  area = (r1 - r0) (c1 - c0),  s = float(strength_milli) / 1000.f
+//   plane[y][x] = (float(2 sum - 255 area) / float(255 area)) * s      inside the scored region (x < sw and y < sh)
+//   plane[y][x] = -1.f * s                                             elsewhere: padding is background
+// one correctly rounded fp32 division and one fp32 multiply; both numerators stay below 2^24, so the conversions are exact --
+// a mask so much larger than pre_w x pre_h that 255 area reaches 2^24 is refused, as is one whose 64 low-res columns span more
+// than 8192 source columns.  strength_milli: 1 .. kPriorMaxStrength.  One launch, no atomics.
+constexpr int kPriorMaxStrength = 100000;
+void mask_prior(const uint8_t* mask, int W, int H, int pre_w, int pre_h, int strength_milli, float* plane, hipStream_t);
+
 }  // namespace k
 }  // namespace dlimg

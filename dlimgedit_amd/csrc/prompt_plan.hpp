@@ -32,6 +32,10 @@
 //
 // Grid marks ({7, side, iou_permille, stability_permille}: "segment everything") are read one layer further out, in
 // grid_plan.hpp (plan_grid_prompts), which hands the call without its grid prompts to plan_cleaned_prompts.
+//
+// Prior marks ({8, strength_milli, 0, 0} directly behind a head: the caller's own mask as the mask input of the prompt's first
+// stage) are read one layer further out again, in prior_plan.hpp (plan_prior_prompts), which hands the call without its prior
+// marks to plan_grid_prompts.
 #pragma once
 
 #include "prompt_geometry.hpp"

@@ -875,6 +875,35 @@ GridPaint const& SamModel::segment_grid(float const* emb, float const* coords, f
     return grid_paint_;
 }
 
+k::MaskSource SamModel::prior_plane(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli) {
+    DLIMG_ASSERT(mask != nullptr && w > 0 && h > 0);
+    roctx::Range range("dlimg.mask_prior");
+    const size_t bytes = (size_t)w * h;
+    // the lane's buffer is re-used by the next prior in stream order; growing it frees memory a queued kernel may still read
+    if (bytes > prior_bytes_.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        prior_bytes_.reserve(bytes);
+    }
+    prior_plane_.reserve((size_t)kLowRes * kLowRes);
+    if (image_memory_is_pinned(mask, bytes)) {
+        HIP_CHECK(hipMemcpyAsync(prior_bytes_.get(), mask, bytes, hipMemcpyHostToDevice, stream_));     // as upload_image
+        HIP_CHECK(hipEventRecord(caller_copied_, stream_));
+        caller_copy_pending_ = true;
+    } else {
+        // packed into pinned staging here and now: the caller's bytes are not read again, so they may be the memory the
+        // prompt's mask is delivered to
+        hipEvent_t copied = nullptr;
+        uint8_t* pin = stage_rows(mask, (size_t)w, h, w, &copied);
+        HIP_CHECK(hipMemcpyAsync(prior_bytes_.get(), pin, bytes, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipEventRecord(copied, stream_));
+    }
+    clock_.timed(ST_POST, (double)bytes + (double)kLowRes * kLowRes * sizeof(float), [&] {
+        k::mask_prior(prior_bytes_.get(), w, h, pre_w, pre_h, strength_milli, prior_plane_.get(), stream_);
+    });
+    HIP_CHECK(hipGetLastError());
+    return k::MaskSource{prior_plane_.get(), nullptr};
+}
+
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }
 
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout(int tokens, bool with_mask_h, bool with_hq) {

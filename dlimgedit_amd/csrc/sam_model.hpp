@@ -211,6 +211,13 @@ class SamModel {
     // pre_w, pre_h: the extent the image was encoded at.
     GridPaint const& segment_grid(float const* emb, float const* coords, float const* labels, int side, int pre_w, int pre_h,
                                   int iou_permille, int stability_permille);
+    // Prior marks (prior_plan.hpp; kernels.hpp K19): the caller's mask [h][w] u8 (HOST memory, tightly packed) of an image that
+    // was encoded at pre_w x pre_h -> the lane's prior plane, as the mask input of the decode enqueued next.  The bytes travel
+    // through the pinned staging ring, packed before this returns (they may be the memory the prompt's mask goes to); a prior
+    // in pinned image memory of the library is copied from where it lies, and the caller waits for that copy
+    // (wait_caller_copies) as for image pixels.  One buffer for the bytes and one plane per lane, grown to the largest prior
+    // seen and kept: the plane is valid until the next prior_plane of this lane, in stream order.
+    k::MaskSource prior_plane(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli);
     // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
     std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
@@ -398,6 +405,8 @@ class SamModel {
     DeviceBuffer<int32_t> grid_records_;
     PinnedBuffer grid_host_;
     GridPaint grid_paint_;
+    DeviceBuffer<uint8_t> prior_bytes_;  // prior marks: the caller's mask at its own size (grow-only) and its plane [256][256]
+    DeviceBuffer<float> prior_plane_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
 
     // ---- pass flags

@@ -1,6 +1,7 @@
 #include "segmentation.hpp"
 
 #include "grid_plan.hpp"
+#include "prior_plan.hpp"
 #include "prompt_plan.hpp"
 #include "roctx.hpp"
 
@@ -40,6 +41,8 @@ struct BatchPrompts {
     std::vector<CleanSpec> clean;      // [prompt]: what its clean-up mark asks for (nothing without one)
     bool any_clean = false;
     std::vector<GridSpec> grid;        // [prompt]: side > 0: a grid prompt (grid_plan.hpp); its packed points are not used
+    std::vector<PriorSpec> prior;      // [prompt]: what its prior mark says (prior_plan.hpp; nothing without one)
+    std::vector<uint8_t const*> prior_mask;    // [prompt]: the prior itself, out_masks[] of the mark's entry (null without one)
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -47,19 +50,26 @@ struct BatchPrompts {
 namespace {
 constexpr int kPromptChunk = 8;          // prompts of one decode of a batch call, at most (prompt_plan.hpp)
 
-BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions) {
-    std::vector<char> has_handle(count);
+// out_masks: the call's per-entry pointers, which a prior mark's prior is read from; null: the device form, which has none
+BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions,
+                                uint8_t* const* out_masks) {
+    std::vector<char> has_handle(count), has_pointer(count);
     SegmentationImpl const* any = nullptr;
     for (int i = 0; i < count; ++i) {
         has_handle[i] = segs[i] != nullptr;
+        has_pointer[i] = out_masks && out_masks[i] != nullptr;
         if (!any) any = segs[i];
     }
     BatchPrompts b;
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        GridPlannedPrompts planned = plan_grid_prompts(has_handle, points != nullptr, regions, mask_branch);
+        PriorPlannedPrompts with_priors = plan_prior_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+                                                             /*device_form*/ out_masks == nullptr);
+        GridPlannedPrompts& planned = with_priors.planned;
         CleanedPrompts& plan = planned.cleaned;
+        b.prior = std::move(with_priors.prior);
+        for (PriorSpec const& p : b.prior) b.prior_mask.push_back(p.any() ? out_masks[p.entry] : nullptr);
         b.grid = std::move(planned.grid);
         b.prompts = std::move(plan.staged.prompts);
         b.stages = std::move(plan.staged.stages);
@@ -86,17 +96,18 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     return b;
 }
 // What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
-// of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).
+// of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).  A prompt with
+// a prior is decoded the way a staged prompt is, whether it has refinement marks or not: its first stage takes a mask input.
 // A grid prompt is a chunk of its own too, behind those: its side * side decodes and its label map run on one lane.
 struct BatchWork { PromptChunk part; bool staged; bool grid = false; };
 std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
     std::vector<int> plain;
     for (int j : mine)
-        if (!b.stages[j].staged() && !b.grid[j].any()) plain.push_back(j);
+        if (!b.stages[j].staged() && !b.prior[j].any() && !b.grid[j].any()) plain.push_back(j);
     std::vector<BatchWork> work;
     for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
     for (int j : mine)
-        if (b.stages[j].staged()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+        if (b.stages[j].staged() || b.prior[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
     for (int j : mine)
         if (b.grid[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, false, true});
     return work;
@@ -118,15 +129,17 @@ void pack_grid(ResizeLongestSide const& rs, int side, std::vector<float>& coords
         }
 }
 // The stages of staged prompt j in front of its last one, decoded on `model` (mutex held) one after the other; returns the
-// mask input of the last stage: the plane the stage before it would deliver, where that decode left it.
+// mask input of the last stage: the plane the stage before it would deliver, where that decode left it.  first: the mask input
+// of the first stage -- the plane of the prompt's prior, or {nullptr, nullptr} when it has none -- which is what comes back
+// when the prompt has one stage only.
 k::MaskSource run_early_stages(SamModel& model, BatchPrompts const& b, int j, float const* emb, ResizeLongestSide const& rs,
-                               int const* points, int const* regions) {
+                               int const* points, int const* regions, k::MaskSource first) {
     PromptStages const& st = b.stages[j];
     float coords[2 * k::kDecoderMaxPoints], labels[k::kDecoderMaxPoints];
-    k::MaskSource src{nullptr, nullptr};
+    k::MaskSource src = first;
     for (size_t s = 0; s + 1 < st.stage_clicks.size(); ++s) {
         const int npts = pack_points(rs, b.prompts[j], st, st.stage_clicks[s], points, regions, coords, labels);
-        model.decode(&emb, coords, labels, 1, npts, s ? &src : nullptr, /*handles*/ true);
+        model.decode(&emb, coords, labels, 1, npts, src.logits4 ? &src : nullptr, /*handles*/ true);
         // single_mask_job's rule: the best of planes 1..3 for a two-point stage, plane 0 otherwise
         src = k::MaskSource{model.logits(), npts > 2 ? nullptr : model.iou()};
     }
@@ -596,8 +609,16 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 continue;
             }
             if (work.staged) {
-                const k::MaskSource src = run_early_stages(model, batch, part.prompts[0], emb[0], segs[prompts[part.prompts[0]].head]->image_size_, points, regions);
+                const int j = part.prompts[0];
+                ResizeLongestSide const& rs = segs[prompts[j].head]->image_size_;
+                // a prior: its bytes and its plane are enqueued here, in front of the decode on the lane's stream
+                k::MaskSource first{nullptr, nullptr};
+                if (batch.prior[j].any())
+                    first = model.prior_plane(batch.prior_mask[j], rs.original.width, rs.original.height, rs.resized.width, rs.resized.height,
+                                              batch.prior[j].strength_milli);
+                const k::MaskSource src = run_early_stages(model, batch, j, emb[0], rs, points, regions, first);
                 model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
+                model.wait_caller_copies();        // a prior read in place (pinned image memory): the caller's again
             } else {
                 model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
             }
@@ -631,7 +652,7 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
                                           int const* regions, uint8_t* const* out_masks) {
     if (count <= 0) return;
     DLIMG_ASSERT(points != nullptr || regions != nullptr);
-    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
+    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions, out_masks);
     std::vector<PromptSpec> const& prompts = batch.prompts;
     EnvironmentImpl& env = segs[prompts[0].head]->env_;
     std::vector<int> used;
@@ -660,7 +681,7 @@ void SegmentationImpl::compute_mask_batch_device(SegmentationImpl const* const* 
     if (root_device < 0 || root_device >= EnvironmentImpl::device_count())
         throw Exception("root device " + std::to_string(root_device) + " is out of range: " +
                         std::to_string(EnvironmentImpl::device_count()) + " device(s) visible");
-    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions);
+    const BatchPrompts batch = read_batch_prompts(segs, count, points, regions, /*out_masks*/ nullptr);
     std::vector<PromptSpec> const& prompts = batch.prompts;
     EnvironmentImpl& env = segs[prompts[0].head]->env_;
     // one mask and one offset per prompt, in head order; the continuation entries of a prompt repeat its offset

@@ -147,7 +147,10 @@ typedef struct dlimg_Api {
      * the entry): a clean-up mark that is not the last entry of its prompt (so at most one per prompt; a refinement mark
      * directly in front of it is still that prompt's last click-side entry and refused as such), one in front of any
      * head, a negative threshold, both thresholds 0, a non-zero fourth int, and a prompt left with neither a click nor a
-     * box.  A call without clean-up marks is read as it always was. */
+     * box.  A call without clean-up marks is read as it always was.
+     * Prior marks (a mask input supplied by the caller): a continuation entry whose four ints are {DLIMG_PRIOR_MARK,
+     * strength_milli, 0, 0} DIRECTLY BEHIND ITS HEAD -- see DLIMG_PRIOR_MARK below.  It is the one continuation entry whose
+     * out_masks[i] is READ: width * height bytes of the head's image, the prior. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -177,6 +180,25 @@ typedef struct dlimg_Api {
  * continuation entry in the prompt (click, refinement mark, clean-up mark), a mark in front of any head.  A call without
  * grid marks is read as it always was. */
 #define DLIMG_GRID_MARK 7
+/* regions[4 i] of a prior mark in get_segmentation_masks (slot 14): {DLIMG_PRIOR_MARK, strength_milli, 0, 0} directly behind
+ * its head hands the prompt a mask the caller already holds -- a lasso or brush selection, the mask of the last query -- as
+ * SAM's mask input.  The mark is neither a click nor a stage; points[i] is not read and it does not count towards the 8
+ * clicks.  out_masks[i] OF THE MARK IS READ AS THE PRIOR: width * height bytes of the head's image, tightly packed, values
+ * 0 .. 255 read as coverage (soft selections count).  It may be the same memory as out_masks[head] -- a mask refined in
+ * place: the prior is taken before anything is delivered.  A prior in memory from create_image is sent from where it lies.
+ * On the GPU the prior becomes the 256 x 256 plane of the prompt encoder's mask branch: a low-res pixel is the mean coverage
+ * of the source pixels it stands for, mapped from 0 .. 255 to -1 .. +1 and multiplied by strength_milli / 1000; what lies
+ * outside the image is background (-strength).  strength_milli is 1 .. 100000; 0 means 8000, a choice and not a
+ * measurement: this library was built and tested with synthetic weights, and SAM's own logits of a confident mask are of
+ * that order.  The plane is the mask input of the prompt's FIRST stage; a prompt with refinement marks feeds its later
+ * stages as before, a clean-up mark cleans the delivered mask as before, and the prompt-size limits are unchanged.  Like
+ * every call with continuation entries the call needs `regions`, an empty head region means "no box", and the prompt must
+ * still hold a click or a box (a box alone, without `points`, will do).  Refused before anything is launched (the message
+ * says "mark" and names the entry): a mark that is not directly behind a head, a NULL prior, a negative strength or one
+ * above 100000, non-zero trailing ints, a second prior mark on the same prompt, a model whose file has no mask branch
+ * (pe.mask.*), a grid prompt, and dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a prior
+ * from.  A call without prior marks is read as it always was. */
+#define DLIMG_PRIOR_MARK 8
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

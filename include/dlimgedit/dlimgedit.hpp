@@ -217,6 +217,16 @@ struct GridOptions {
     int side = 32, iou_permille = 0, stability_permille = 0;
 };
 
+// A prior: a mask the caller already holds (a lasso or brush selection, the mask of the last query) as SAM's mask input of a
+// click-to-refine prompt.  mask: width * height bytes of the segmentation's image, tightly packed, 0 .. 255 read as coverage
+// (soft selections count); it may be the memory the result goes to.  strength_milli: 1 .. 100000, the logit a fully covered
+// pixel stands for, in thousandths; 0: the library's default, 8000.  Travels as a prior mark of table slot 14 (dlimgedit.h,
+// DLIMG_PRIOR_MARK).  Needs a model with the mask branch.
+struct Prior {
+    uint8_t const* mask = nullptr;
+    int strength_milli = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -322,10 +332,13 @@ class Segmentation {
     // logits of the one before it as its mask input (on the GPU); the mask of the last stage is returned.  refine_each(n):
     // a mark after every click but the last.  Needs a model with the mask branch.
     // clean: the mask is delivered cleaned (MaskCleanup).
+    // prior: the caller's own mask as the mask input of the first stage (Prior).
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
-                       std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt) const {
+                       std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
+                       std::optional<Prior> prior = std::nullopt) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
-                                            clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{})[0]);
+                                            clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
+                                            prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{})[0]);
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -335,15 +348,20 @@ class Segmentation {
 
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
     // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
-    // optional clean-up per prompt.
+    // optional clean-up per prompt; prior: empty, or one optional prior per prompt.
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
                                                  std::vector<std::vector<int>> const& refine_after = {},
-                                                 std::vector<std::optional<MaskCleanup>> const& clean = {}) {
+                                                 std::vector<std::optional<MaskCleanup>> const& clean = {},
+                                                 std::vector<std::optional<Prior>> const& prior = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
-            (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()))
+            (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
+            (!prior.empty() && prior.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
+        for (auto const& p : prior)
+            if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
+                throw Exception("compute_mask_batch: a prior has a mask and a strength_milli of 0 (the default) .. 100000");
         for (auto const& c : clean)
             if (c && (c->max_hole < 0 || c->max_island < 0 || (c->max_hole == 0 && c->max_island == 0)))
                 throw Exception("compute_mask_batch: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
@@ -356,7 +374,8 @@ class Segmentation {
         for (size_t j = 0; j < segs.size(); ++j) {
             if (clicks[j].empty() || clicks[j].size() > 8) throw Exception("compute_mask_batch: a prompt takes 1 to 8 clicks");
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
-            refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value());     // any continuation entry
+            refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value()) ||
+                      (!prior.empty() && prior[j].has_value());                                        // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -383,6 +402,12 @@ class Segmentation {
                     ptrs.push_back(c == 0 ? out[j].pixels() : nullptr);
                     if (c == 0) regs.push_back(box ? *regions[j] : Region(Point{0, 0}, Point{-1, -1}));
                     else regs.push_back(Region(Point{clicks[j][c].foreground ? 1 : 0, 0}, Point{0, 0}));
+                    if (c == 0 && !prior.empty() && prior[j]) {
+                        hs.push_back(nullptr);           // the prior mark, directly behind its head: its point is not read and
+                        pts.push_back(Point{0, 0});      // its out_masks pointer is the prior, which the call only reads
+                        ptrs.push_back(const_cast<uint8_t*>(prior[j]->mask));
+                        regs.push_back(Region(Point{DLIMG_PRIOR_MARK, prior[j]->strength_milli}, Point{0, 0}));
+                    }
                 }
                 if (!clean.empty() && clean[j]) {
                     hs.push_back(nullptr);               // the clean-up mark, the last entry of its prompt: its point is not read
