@@ -250,6 +250,30 @@ def prior_hooks_library() -> C.CDLL:
     return _prior_hooks_lib
 
 
+_lasso_hooks_lib = None
+LASSO_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_lasso_test.so")
+# the hook of the lasso derivation alone (csrc/lasso_test_hooks.cpp): bound by name, no header declares it
+LASSO_HOOK_EXPORTS = ("dlimg_amd_test_lasso_derive",)
+
+
+def lasso_hooks_library() -> C.CDLL:
+    """Loads lib/libdlimgedit_lasso_test.so: the product's objects plus the hook of the lasso derivation.  Raises if it has not
+    been built; there is no fallback."""
+    global _lasso_hooks_lib
+    if _lasso_hooks_lib is None:
+        if not LASSO_HOOKS_LIB_PATH.exists():
+            raise Error(f"{LASSO_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+        lib = C.CDLL(str(LASSO_HOOKS_LIB_PATH))
+        lib.dlimg_init.restype = C.POINTER(_Api)
+        lib.dlimg_init.argtypes = []
+        ci = C.c_int
+        lib.dlimg_amd_test_lasso_derive.argtypes = [C.c_void_p, ci, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(ci), ci,
+                                                    C.POINTER(C.c_float)]
+        lib.dlimg_amd_test_lasso_derive.restype = ci
+        _lasso_hooks_lib = lib
+    return _lasso_hooks_lib
+
+
 def _check_neck_hook(result: int) -> None:
     if result != 0:
         msg = neck_hooks_library().dlimg_init().contents.last_error()
@@ -412,6 +436,8 @@ GRID_MARK = 7                # regions[4 i] of a grid mark (dlimgedit.h: DLIMG_G
 GRID_MAX_SIDE = 32
 PRIOR_MARK = 8               # regions[4 i] of a prior mark (dlimgedit.h: DLIMG_PRIOR_MARK; csrc/prior_plan.hpp: kPriorMark)
 PRIOR_MAX_STRENGTH = 100000  # strength_milli of a prior mark, at most; 0: the library's default (8000)
+LASSO_MARK = 10              # regions[4 i] of a lasso mark (dlimgedit.h: DLIMG_LASSO_MARK; csrc/lasso_plan.hpp: kLassoMark)
+LASSO_BOX, LASSO_CLICK, LASSO_MASK = 1, 2, 4     # the bits of a lasso mark's `what`; 0: all three
 
 
 @dataclass
@@ -435,7 +461,11 @@ class ClickEntries:
     A prior mark is a continuation entry (PRIOR_MARK, strength_milli, 0, 0) directly behind its head, whose point is not read
     and whose out_masks pointer is READ: priors[j] is the (h, w) uint8 mask prompt j hands in as SAM's mask input of its first
     stage, None for a prompt without one.  A prompt with a prior is decoded behind the others like a prompt with marks, its
-    first stage masked too; token_rows and stage_clicks are unchanged."""
+    first stage masked too; token_rows and stage_clicks are unchanged.
+    A lasso mark is a continuation entry (LASSO_MARK, strength_milli, what, 0) directly behind its head, whose out_masks pointer is
+    READ likewise: lassos[j] is the (h, w) uint8 selection of prompt j, None without one.  Its box and / or first click are
+    derived on the GPU: token_rows and stage_clicks count the derived click (it belongs to the first stage) and the derived
+    box.  Such a prompt is decoded behind the others like a prompt with marks."""
     heads: list
     points: list
     regions: list
@@ -444,9 +474,11 @@ class ClickEntries:
     stage_clicks: list = field(default_factory=list)
     grid_sides: list = field(default_factory=list)
     priors: list = field(default_factory=list)
+    lassos: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
-        return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None)
+        return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None) \
+            or (j < len(self.lassos) and self.lassos[j] is not None)
 
     def _grid(self, j) -> bool:
         return j < len(self.grid_sides) and self.grid_sides[j] > 0
@@ -586,8 +618,40 @@ def _checked_prior(prior, prior_strength, n: int) -> list:
     return out
 
 
-def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list) -> list:
-    """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), None otherwise."""
+def _checked_lasso(lasso, lasso_what, lasso_strength, n: int) -> list:
+    """`lasso` / `lasso_what` / `lasso_strength` of a call of n prompts -> per prompt None or ((h, w) uint8 array, what,
+    strength_milli): lasso is None or one entry (None or an array) per prompt; lasso_what and lasso_strength one int for all or
+    one per prompt.  what: a bit set of LASSO_BOX, LASSO_CLICK, LASSO_MASK, 0 (all) .. 7 other than 4; strength 0 .. 100000, 0
+    without LASSO_MASK."""
+    if lasso is None:
+        return [None] * n
+    lasso = list(lasso)
+    if len(lasso) != n:
+        raise Error("lasso: None, or one entry (None or an (h, w) uint8 array) per prompt")
+    def per_prompt(v, name):
+        vs = [v] * n if isinstance(v, (int, np.integer)) else list(v)
+        if len(vs) != n or not all(isinstance(x, (int, np.integer)) for x in vs):
+            raise Error(f"{name}: one int for all prompts or one per prompt")
+        return [int(x) for x in vs]
+    whats, strengths = per_prompt(lasso_what, "lasso_what"), per_prompt(lasso_strength, "lasso_strength")
+    out = []
+    for m, what, v in zip(lasso, whats, strengths):
+        if m is None:
+            out.append(None)
+            continue
+        if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.ndim != 2 or not m.flags.c_contiguous:
+            raise Error("lasso: a selection is a C-contiguous (h, w) uint8 array of the image's extent")
+        if not 0 <= what <= 7 or what == LASSO_MASK:
+            raise Error("lasso_what: a bit set of LASSO_BOX, LASSO_CLICK and LASSO_MASK, 0 (all) .. 7; 4 alone derives nothing")
+        if not 0 <= v <= PRIOR_MAX_STRENGTH or (v and what and not what & LASSO_MASK):
+            raise Error(f"lasso_strength: 0 (the default) .. {PRIOR_MAX_STRENGTH}, and 0 without LASSO_MASK")
+        out.append((m, what, v))
+    return out
+
+
+def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos: Optional[list] = None) -> list:
+    """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), the selection of
+    a lasso mark (lassos likewise), None otherwise."""
     ptrs, head = [], None
     for e, h in enumerate(heads):
         if h is not None:
@@ -598,12 +662,18 @@ def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list) -> list
             if m.shape != (ext.height, ext.width):
                 raise Error(f"prior: the prior of prompt {head} is {m.shape[1]} x {m.shape[0]}, its image {ext.width} x {ext.height}")
             ptrs.append(m.ctypes.data)
+        elif regs[e][0] == LASSO_MARK and head is not None and lassos is not None and lassos[head] is not None:
+            m, ext = lassos[head][0], segs[head].extent()
+            if m.shape != (ext.height, ext.width):
+                raise Error(f"lasso: the selection of prompt {head} is {m.shape[1]} x {m.shape[0]}, its image {ext.width} x {ext.height}")
+            ptrs.append(m.ctypes.data)
         else:
             ptrs.append(None)
     return ptrs
 
 
-def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None):
+def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None,
+                    lasso: Optional[list] = None):
     """The `points` / `regions` form of a batch call with clean-up, grid or prior marks as entry lists: entry i of the caller's,
     then its marks (the prior mark first: it stands directly behind its head).  -> (index into segs or None per entry, [(x, y)]
     or None, [(4 ints)]).  A point prompt gets the empty region (no box); a grid prompt is its head with the empty region and
@@ -618,6 +688,8 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
                 raise Error("a grid prompt takes no clean-up mark")
             if prior is not None and prior[i] is not None:
                 raise Error("a grid prompt takes no prior")
+            if lasso is not None and lasso[i] is not None:
+                raise Error("a grid prompt takes no lasso")
             regs.append(EMPTY_REGION)
             heads.append(None)
             if pts is not None:
@@ -631,6 +703,11 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
             if pts is not None:
                 pts.append((0, 0))
             regs.append((PRIOR_MARK, prior[i][1], 0, 0))
+        if lasso is not None and lasso[i] is not None:
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((LASSO_MARK, lasso[i][2], lasso[i][1], 0))
         if clean[i] is not None:
             heads.append(None)
             if pts is not None:
@@ -648,7 +725,7 @@ def _marked_arrays(segs, heads, pts, regs):
 
 
 def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
-                  prior_strength=0) -> ClickEntries:
+                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -659,12 +736,19 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     prior: None, or per prompt None / an (h, w) uint8 mask of the prompt's image -- a prior mark directly behind the head, with
     prior_strength (one int for all or one per prompt; 0: the library's default) as its strength_milli.  Entry lists without
     priors are what they were.
+    lasso: None, or per prompt None / an (h, w) uint8 selection of the prompt's image -- a lasso mark directly behind the head,
+    with lasso_what (bits LASSO_BOX, LASSO_CLICK, LASSO_MASK; 0: all) and lasso_strength (0 without LASSO_MASK), one int for
+    all or one per prompt.  clicks[j] are then the clicks BEHIND the derived one (the entry lists always carry `points`, so
+    there is at least one; a lasso alone is Segmentation.snap_selection), and refine_after counts the clicks given.  Entry
+    lists without lasso marks are what they were.
     Pure host code."""
     n = len(clicks)
     clean = _checked_clean(clean, n)
     grid = _checked_grid(grid, n)
     prior = _checked_prior(prior, prior_strength, n)
     any_prior = any(p is not None for p in prior)
+    lasso = _checked_lasso(lasso, lasso_what, lasso_strength, n)
+    any_lasso = any(q is not None for q in lasso)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -675,6 +759,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
         out.grid_sides.append(0 if grid[j] is None else grid[j][0])
         if any_prior:
             out.priors.append(None if prior[j] is None else prior[j][0])
+        if any_lasso:
+            out.lassos.append(None if lasso[j] is None else lasso[j][0])
+        if grid[j] is not None and lasso[j] is not None:
+            raise Error("a grid prompt takes no lasso")
         if grid[j] is not None:
             if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None \
                     or prior[j] is not None:
@@ -690,8 +778,14 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
         marks = _checked_marks(len(cs), refine_after[j])
         r = regions[j]
         out.prompt_heads.append(len(out.heads))
-        out.token_rows.append(5 + len(cs) + (2 if r is not None else 1))
-        out.stage_clicks.append(marks + [len(cs)])
+        what = 0 if lasso[j] is None else (lasso[j][1] or 7)
+        if what and prior[j] is not None:
+            raise Error("a prompt takes a prior or a lasso, not both")
+        if what & LASSO_BOX and r is not None:
+            raise Error("lasso: with LASSO_BOX the prompt's box is the selection's: no region")
+        derived = 1 if what & LASSO_CLICK else 0
+        out.token_rows.append(5 + derived + len(cs) + (2 if r is not None or what & LASSO_BOX else 1))
+        out.stage_clicks.append([k + derived for k in marks + [len(cs)]])
         for k, (c, lab) in enumerate(zip(cs, ls)):
             if k in marks:               # a mark behind the first k clicks: in front of click k (0-based)
                 out.heads.append(None)
@@ -707,6 +801,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
                     out.heads.append(None)
                     out.points.append((0, 0))
                     out.regions.append((PRIOR_MARK, prior[j][1], 0, 0))
+                if lasso[j] is not None:     # so does the lasso mark
+                    out.heads.append(None)
+                    out.points.append((0, 0))
+                    out.regions.append((LASSO_MARK, lasso[j][2], lasso[j][1], 0))
         if clean[j] is not None:
             out.heads.append(None)
             out.points.append((0, 0))
@@ -803,7 +901,8 @@ class Segmentation:
 
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
-                            clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0) -> np.ndarray:
+                            clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0,
+                            lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
@@ -814,18 +913,42 @@ class Segmentation:
         prior: an (h, w) uint8 mask the caller already holds (a selection, the mask of the last query; 0 .. 255 read as
         coverage) as SAM's mask input of the first stage; it may be `out` itself, a mask refined in place.  prior_strength: the
         logit a fully covered pixel stands for, in thousandths, 1 .. 100000; 0: the library's default, 8000.  Needs a model
-        with the mask branch."""
+        with the mask branch.
+        lasso: an (h, w) uint8 selection from which the prompt's box (LASSO_BOX), its first click (LASSO_CLICK: the most interior
+        point, in front of `clicks`) and its first mask input (LASSO_MASK, at lasso_strength) are derived on the GPU;
+        lasso_what 0: all three.  See snap_selection."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
                                                out=None if out is None else [out],
                                                refine_after=None if refine_after is None else [refine_after],
                                                clean=None if clean is None else [tuple(clean)],
-                                               prior=None if prior is None else [prior], prior_strength=prior_strength)[0]
+                                               prior=None if prior is None else [prior], prior_strength=prior_strength,
+                                               lasso=None if lasso is None else [lasso], lasso_what=lasso_what,
+                                               lasso_strength=lasso_strength)[0]
+
+    def snap_selection(self, mask: np.ndarray, what: int = 0, strength: int = 0, clicks: Optional[Sequence[Point]] = None,
+                       labels: Optional[Sequence[int]] = None, refine_after=None, clean=None,
+                       out: Optional[np.ndarray] = None) -> np.ndarray:
+        """Snap a selection to the object: mask, an (h, w) uint8 selection of this image (a dragged lasso, a painted blob; 0 ..
+        255 read as coverage), is the prompt -- its box (LASSO_BOX), its most interior point as a foreground click
+        (LASSO_CLICK) and the selection itself as SAM's mask input (LASSO_MASK, at `strength` thousandths, 0: the default
+        8000; needs a model with the mask branch), whichever bits `what` holds, 0: all three.  Box and click are derived on
+        the GPU from the 256 x 256 low-res grid (dlimgedit.h, DLIMG_LASSO_MARK).  clicks / labels: further clicks behind the
+        derived one (the first of them foreground); refine_after counts these; clean as for compute_mask_clicks.  `out` may be
+        `mask` itself: a selection snapped in place.  An empty selection (no low-res cell above half coverage) raises Error."""
+        if clicks:
+            return self.compute_mask_clicks(clicks, labels, None, out, refine_after, clean, lasso=mask, lasso_what=what,
+                                            lasso_strength=strength)
+        if labels or refine_after is not None:
+            raise Error("snap_selection: labels and refine_after go with `clicks`")
+        return Segmentation.compute_mask_batch([self], out=None if out is None else [out], clean=None if clean is None else [tuple(clean)],
+                                               lasso=[mask], lasso_what=what, lasso_strength=strength)[0]
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
-                           clean=None, grid=None, prior=None, prior_strength=0) -> list:
+                           clean=None, grid=None, prior=None, prior_strength=0, lasso=None, lasso_what=0,
+                           lasso_strength=0) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -839,7 +962,11 @@ class Segmentation:
         whose result is a label map (segment_everything); its point, clicks and region are not used (None will do), and with
         grid prompts alone neither `points` nor `regions` nor `clicks` is needed.
         prior (either form): None, or per prompt None / an (h, w) uint8 mask of the prompt's image -- prior marks, see
-        compute_mask_clicks; prior_strength one int for all or one per prompt.  A box-only call may carry them too."""
+        compute_mask_clicks; prior_strength one int for all or one per prompt.  A box-only call may carry them too.
+        lasso (either form): None, or per prompt None / an (h, w) uint8 selection -- lasso marks, see snap_selection; lasso_what
+        and lasso_strength one int for all or one per prompt.  In a call with `points` or `clicks` those follow the derived
+        click; a call without `points` may hold lasso-only prompts (regions[i] None) beside box-only ones, and with lasso
+        prompts alone neither `points` nor `regions` is needed."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -849,10 +976,12 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
-            entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength)
+            entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength, lasso, lasso_what,
+                                    lasso_strength)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             priors = _checked_prior(prior, prior_strength, len(segs))
-            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors)
+            lassos = _checked_lasso(lasso, lasso_what, lasso_strength, len(segs))
+            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos)
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
                 ptrs = (C.c_void_p * n)(*[all_ptrs[i] for i in sel])
@@ -864,12 +993,15 @@ class Segmentation:
         marks = _checked_clean(clean, n)
         grids = _checked_grid(grid, n)
         priors = _checked_prior(prior, prior_strength, n)
-        if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors):
-            if points is None and regions is None and any(g is None for g in grids):
+        lassos = _checked_lasso(lasso, lasso_what, lasso_strength, n)
+        if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors) \
+                or any(q is not None for q in lassos):
+            if points is None and regions is None and any(g is None and q is None for g, q in zip(grids, lassos)):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
-            ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors))
+            ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors,
+                                                     lassos))
             _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
             return outs
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
@@ -1463,6 +1595,26 @@ class ext:
             msg = lib.dlimg_init().contents.last_error()
             raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
         return (plane, bool(ok.value)) if time_iters <= 0 else (plane, bool(ok.value), float(ms.value))
+
+    @classmethod
+    def test_lasso_derive(cls, mask: np.ndarray, pre_w: int, pre_h: int, time_iters: int = 0):
+        """The lasso derivation alone (the hook of lasso_hooks_library()): mask (h, w) uint8, of an image that was encoded at
+        pre_w x pre_h, through k::mask_prior, the two launches of k::lasso_derive and the host's fold, with guard bytes around
+        every device buffer.  -> (record int32 [8] = inside cells, box x0, y0, x1, y1, click x, click y, d2; guard bytes
+        intact); with time_iters > 0 a third element, the milliseconds of one derivation (both launches; the mean of
+        time_iters repetitions between two events).  A refusal of a launcher raises Error."""
+        mask = np.ascontiguousarray(mask, np.uint8)
+        assert mask.ndim == 2
+        h, w = mask.shape
+        record = np.zeros(8, np.int32)
+        ok, ms = C.c_int(0), C.c_float(0.0)
+        lib = lasso_hooks_library()
+        rc = lib.dlimg_amd_test_lasso_derive(mask.ctypes.data, w, h, int(pre_w), int(pre_h), record.ctypes.data_as(C.POINTER(C.c_int32)),
+                                             C.byref(ok), int(time_iters), C.byref(ms))
+        if rc != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        return (record, bool(ok.value)) if time_iters <= 0 else (record, bool(ok.value), float(ms.value))
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

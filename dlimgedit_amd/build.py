@@ -3,7 +3,7 @@
 In-tree, no cmake: `python -m dlimgedit_amd.build`.  hipcc cross-compiles without a GPU, so this also
 runs in the CPU-only build container.  Objects are cached by source mtime under csrc/_obj/.
 
-Six libraries (and the tuning build) come out of the same sources:
+Seven libraries (and the tuning build) come out of the same sources:
   lib/libdlimgedit.so         the product: dlimg_init + the extension entry points of include/dlimgedit/dlimgedit_amd.h,
                               named one by one in csrc/exports.map
   lib/libdlimgedit_test.so    the product's OBJECTS plus csrc/test_hooks.cpp: additionally exports the dlimg_amd_test_* /
@@ -18,6 +18,8 @@ Six libraries (and the tuning build) come out of the same sources:
                               (tests/test_gpu_grid_kernels.py), a library of its own for the same reason; built by default
   lib/libdlimgedit_prior_test.so  the product's OBJECTS plus csrc/prior_test_hooks.cpp: the hook of the prior-plane kernel alone
                               (tests/test_gpu_prior_kernel.py), a library of its own for the same reason; built by default
+  lib/libdlimgedit_lasso_test.so  the product's OBJECTS plus csrc/lasso_test_hooks.cpp: the hook of the lasso derivation alone
+                              (tests/test_gpu_lasso_kernel.py), a library of its own for the same reason; built by default
   lib/libdlimgedit_tuning.so  `--tuning`: everything compiled with -DDLIMG_TUNING -- additionally the ablated kernel variants
                               and in-kernel cycle stamps the scripts under tools/ use (DLIMGEDIT_*_ABLATE, GemmArgs::stamps);
                               tools select it with DLIMGEDIT_TUNING_LIB=1 (or the file name of a copy kept under lib/).
@@ -44,6 +46,7 @@ LIB_NECK_TEST = PKG / "lib" / "libdlimgedit_neck_test.so"
 LIB_CLEANUP_TEST = PKG / "lib" / "libdlimgedit_cleanup_test.so"
 LIB_GRID_TEST = PKG / "lib" / "libdlimgedit_grid_test.so"
 LIB_PRIOR_TEST = PKG / "lib" / "libdlimgedit_prior_test.so"
+LIB_LASSO_TEST = PKG / "lib" / "libdlimgedit_lasso_test.so"
 ARCH = "gfx950"
 SONAME = "libdlimgedit.so.1"
 EXPORTS_MAP = CSRC / "exports.map"
@@ -52,11 +55,13 @@ EXPORTS_NECK_TEST_MAP = CSRC / "exports_neck_test.map"
 EXPORTS_CLEANUP_TEST_MAP = CSRC / "exports_cleanup_test.map"
 EXPORTS_GRID_TEST_MAP = CSRC / "exports_grid_test.map"
 EXPORTS_PRIOR_TEST_MAP = CSRC / "exports_prior_test.map"
+EXPORTS_LASSO_TEST_MAP = CSRC / "exports_lasso_test.map"
 HOOK_SOURCES = ["test_hooks.cpp"]          # test and tuning libraries only
 NECK_HOOK_SOURCES = ["neck_test_hooks.cpp"]     # lib/libdlimgedit_neck_test.so only
 CLEANUP_HOOK_SOURCES = ["cleanup_test_hooks.cpp"]     # lib/libdlimgedit_cleanup_test.so only
 GRID_HOOK_SOURCES = ["grid_test_hooks.cpp"]           # lib/libdlimgedit_grid_test.so only
 PRIOR_HOOK_SOURCES = ["prior_test_hooks.cpp"]         # lib/libdlimgedit_prior_test.so only
+LASSO_HOOK_SOURCES = ["lasso_test_hooks.cpp"]         # lib/libdlimgedit_lasso_test.so only
 
 SOURCES = [
     "kernels/gemm.hip",
@@ -70,6 +75,7 @@ SOURCES = [
     "kernels/mask_cleanup.hip",
     "kernels/mask_grid.hip",
     "kernels/mask_prior.hip",
+    "kernels/mask_lasso.hip",
     "kernels/resize.hip",
     "kernels/objects.hip",
     "resize_tables.cpp",
@@ -96,6 +102,7 @@ EXTRA_FLAGS = {
     "kernels/postprocess.hip": ["-ffp-contract=off"],
     "kernels/mask_grid.hip": ["-ffp-contract=off"],        # the same sample, bit for bit (kernels/bilinear_taps.hpp)
     "kernels/mask_prior.hip": ["-ffp-contract=off"],       # one division, one multiply, bit for bit (tests/prior_ref.py)
+    "kernels/mask_lasso.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbour all the same (tests/lasso_ref.py)
     "kernels/resize.hip": ["-ffp-contract=off"],
     "kernels/objects.hip": ["-ffp-contract=off"],
     "resize_tables.cpp": ["-ffp-contract=off"],
@@ -218,6 +225,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
         cleanup_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), CLEANUP_HOOK_SOURCES))
         grid_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), GRID_HOOK_SOURCES))
         prior_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), PRIOR_HOOK_SOURCES))
+        lasso_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), LASSO_HOOK_SOURCES))
     if tuning:
         if _stale(LIB_TUNING, objs + hooks, force):
             _link(LIB_TUNING, objs + hooks, EXPORTS_TEST_MAP)
@@ -240,13 +248,15 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
         _link(LIB_GRID_TEST, objs + grid_hooks, EXPORTS_GRID_TEST_MAP)
     if _stale(LIB_PRIOR_TEST, objs + prior_hooks, force):
         _link(LIB_PRIOR_TEST, objs + prior_hooks, EXPORTS_PRIOR_TEST_MAP)
+    if _stale(LIB_LASSO_TEST, objs + lasso_hooks, force):
+        _link(LIB_LASSO_TEST, objs + lasso_hooks, EXPORTS_LASSO_TEST_MAP)
     # consumers linked against the reference's library resolve libdlimgedit.so.1 (SOVERSION 1,
     # /root/reference/src/CMakeLists.txt:20-23)
     link = LIB.parent / SONAME
     if not link.is_symlink() and not link.exists():
         link.symlink_to(LIB.name)
     if verbose:
-        print(f"built {LIB} ({LIB.stat().st_size / 1e6:.1f} MB), {LIB_TEST.name}, {LIB_NECK_TEST.name}, {LIB_CLEANUP_TEST.name}, {LIB_GRID_TEST.name} and {LIB_PRIOR_TEST.name}")
+        print(f"built {LIB} ({LIB.stat().st_size / 1e6:.1f} MB), {LIB_TEST.name}, {LIB_NECK_TEST.name}, {LIB_CLEANUP_TEST.name}, {LIB_GRID_TEST.name}, {LIB_PRIOR_TEST.name} and {LIB_LASSO_TEST.name}")
     return LIB
 
 

@@ -390,5 +390,18 @@ void grid_paint(const float* store, int candidates, const GridKept& kept, uint8_
 constexpr int kPriorMaxStrength = 100000;
 void mask_prior(const uint8_t* mask, int W, int H, int pre_w, int pre_h, int strength_milli, float* plane, hipStream_t);
 
+// ---- lasso marks (K20, kernels/mask_lasso.hip) ------------------------------------------------
+// The box of a selection and its most interior cell, on the low-res grid: plane [256][256] fp32 as mask_prior wrote it for an
+// image encoded at pre_w x pre_h.  With sw = ceil(pre_w / 4), sh = ceil(pre_h / 4): cell (x, y) is inside when x < sw, y < sh
+// and plane[y][x] > 0 (2 sum > 255 area); every other cell of Z^2 is background.  d2(x, y): the exact squared Euclidean
+// distance of an inside cell to the nearest background cell.
+//   g_scratch [256][256] int32   the vertical distance of every cell to the nearest background cell of its column (0 outside)
+//   rows [256][kLassoRowInts] int32, one record per low-res row y: {inside cells of the row, its first inside column, its last,
+//        the column of its cell with the largest d2 (ties: the smallest), that d2, 0, 0, 0}; all zero for a row without one
+// Integer arithmetic throughout.  Two launches, no atomics on global memory; lasso_plan.hpp (fold_lasso_rows) folds the rows into
+// the prompt's record on the host, which reads them anyway.
+constexpr int kLassoRowInts = 8;
+void lasso_derive(const float* plane, int pre_w, int pre_h, int* g_scratch, int* rows, hipStream_t);
+
 }  // namespace k
 }  // namespace dlimg

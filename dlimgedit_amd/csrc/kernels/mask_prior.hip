@@ -15,6 +15,7 @@
 // atomics, no waiting on other workgroups; the plane is written with plain (vector) stores, 256 bytes per wave.  Memory-bound
 // on paper: the mask is read once (a source row of a footprint border twice), 256 KB are written.
 #include "device_common.hpp"
+#include "footprint.hpp"
 #include "kernels.hpp"
 
 #pragma clang fp contract(off)
@@ -26,12 +27,7 @@ constexpr int LOW = 256;
 constexpr int kSeg = 64;             // low-res columns of one workgroup, one per lane
 constexpr int kSpanMax = 8192;       // source columns of one segment the LDS holds (a multiple of 16): 32 KB
 
-// first source index and one past the last of low-res index i along an axis of `size` source pixels encoded at `pre`
-__host__ __device__ inline int footprint_lo(int i, int size, int pre) { return (int)((int64_t)4 * i * size / pre); }
-__host__ __device__ inline int footprint_hi(int i, int size, int pre) {
-    const int64_t e = 4 * i + 4 < pre ? 4 * i + 4 : pre;
-    return (int)((e * size + pre - 1) / pre);
-}
+// footprint_lo / footprint_hi: footprint.hpp (shared with the lasso derivation)
 
 struct PriorArgs { const uint8_t* mask; float* plane; int W, H, pre_w, pre_h, sw, sh; float s; };
 

@@ -35,14 +35,16 @@ struct PriorPlannedPrompts {
 inline bool is_prior_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kPriorMark; }
 
 // has_pointer[i]: out_masks[i] of entry i is not NULL (read for prior marks only).  device_form: the call is
-// dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer a prior could be read from.
+// dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer a prior could be read from.  had_continuation: as
+// for plan_prompts -- the caller's list held continuation entries that are not in this one (lasso marks, lasso_plan.hpp).
 inline PriorPlannedPrompts plan_prior_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch,
-                                              std::vector<char> const& has_pointer, bool device_form = false) {
+                                              std::vector<char> const& has_pointer, bool device_form = false,
+                                              bool had_continuation = false) {
     const int count = (int)has_handle.size();
     PriorPlannedPrompts out;
     for (int i = 0; i < count; ++i) out.any_prior |= !has_handle[i] && is_prior_mark_entry(regions, i);
     if (!out.any_prior) {
-        out.planned = plan_grid_prompts(has_handle, points_given, regions, mask_branch);
+        out.planned = plan_grid_prompts(has_handle, points_given, regions, mask_branch, had_continuation);
         out.prior.resize(out.planned.cleaned.staged.prompts.size());
         return out;
     }

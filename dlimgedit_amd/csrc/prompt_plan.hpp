@@ -36,6 +36,10 @@
 // Prior marks ({8, strength_milli, 0, 0} directly behind a head: the caller's own mask as the mask input of the prompt's first
 // stage) are read one layer further out again, in prior_plan.hpp (plan_prior_prompts), which hands the call without its prior
 // marks to plan_grid_prompts.
+//
+// Lasso marks ({10, strength_milli, what, 0} directly behind a head: a selection whose box and first click are derived on the
+// GPU) are read by the outermost layer, lasso_plan.hpp (plan_lasso_prompts), which hands the call without its lasso marks to
+// plan_prior_prompts and reserves the derived click and box in the PromptSpec.
 #pragma once
 
 #include "prompt_geometry.hpp"

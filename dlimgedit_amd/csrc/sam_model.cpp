@@ -2,6 +2,7 @@
 #include "gemm_plan.hpp"
 #include "grid_plan.hpp"
 #include "image_memory.hpp"
+#include "lasso_plan.hpp"
 #include "roctx.hpp"
 
 #include <algorithm>
@@ -902,6 +903,26 @@ k::MaskSource SamModel::prior_plane(uint8_t const* mask, int w, int h, int pre_w
     });
     HIP_CHECK(hipGetLastError());
     return k::MaskSource{prior_plane_.get(), nullptr};
+}
+
+k::MaskSource SamModel::lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli,
+                                     int32_t record[kLassoRecordInts]) {
+    static_assert(kLassoRowRecordInts == k::kLassoRowInts && kLassoRows == kLowRes, "one row record, one grid");
+    // upload and plane as for a prior; without the mask bit the plane is scratch, at any valid strength
+    const k::MaskSource plane = prior_plane(mask, w, h, pre_w, pre_h, strength_milli > 0 ? strength_milli : kPriorDefaultStrength);
+    roctx::Range range("dlimg.lasso_derive");
+    constexpr size_t kCells = (size_t)kLowRes * kLowRes, kRowInts = (size_t)kLassoRows * kLassoRowRecordInts;
+    lasso_scratch_.reserve(kCells + kRowInts);         // allocated once: g [256][256], then the row records
+    lasso_host_.reserve(kRowInts * sizeof(int32_t));
+    int32_t* const rows_dev = lasso_scratch_.get() + kCells;
+    clock_.timed(ST_POST, (double)(2 * kCells + kRowInts) * sizeof(int32_t) + (double)kCells * sizeof(float), [&] {
+        k::lasso_derive(plane.logits4, pre_w, pre_h, lasso_scratch_.get(), rows_dev, stream_);
+    }, 2);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(lasso_host_.get(), rows_dev, kRowInts * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    HIP_CHECK(hipStreamSynchronize(stream_));          // the one host round trip of a lasso prompt
+    fold_lasso_rows(static_cast<int32_t const*>(lasso_host_.get()), w, h, pre_w, pre_h, record);
+    return plane;
 }
 
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }

@@ -218,6 +218,11 @@ class SamModel {
     // (wait_caller_copies) as for image pixels.  One buffer for the bytes and one plane per lane, grown to the largest prior
     // seen and kept: the plane is valid until the next prior_plane of this lane, in stream order.
     k::MaskSource prior_plane(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli);
+    // Lasso marks (lasso_plan.hpp; kernels.hpp K20): prior_plane of the selection, then the derivation behind it on the lane's
+    // stream, the row records copied to pinned memory, ONE wait for the stream, and the rows folded into `record` ({inside cells,
+    // box x0, y0, x1, y1, click x, click y, d2} in image pixels; all zero: the selection is empty).  Returns the plane, which is
+    // the first stage's mask input when the mark asks for it.  strength_milli 0: the plane is scratch.
+    k::MaskSource lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli, int32_t record[8]);
     // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
     std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
@@ -407,6 +412,8 @@ class SamModel {
     GridPaint grid_paint_;
     DeviceBuffer<uint8_t> prior_bytes_;  // prior marks: the caller's mask at its own size (grow-only) and its plane [256][256]
     DeviceBuffer<float> prior_plane_;
+    DeviceBuffer<int32_t> lasso_scratch_;    // lasso marks: g [256][256] and the row records [256][8] behind it
+    PinnedBuffer lasso_host_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
 
     // ---- pass flags

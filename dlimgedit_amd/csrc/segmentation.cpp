@@ -1,6 +1,7 @@
 #include "segmentation.hpp"
 
 #include "grid_plan.hpp"
+#include "lasso_plan.hpp"
 #include "prior_plan.hpp"
 #include "prompt_plan.hpp"
 #include "roctx.hpp"
@@ -43,6 +44,9 @@ struct BatchPrompts {
     std::vector<GridSpec> grid;        // [prompt]: side > 0: a grid prompt (grid_plan.hpp); its packed points are not used
     std::vector<PriorSpec> prior;      // [prompt]: what its prior mark says (prior_plan.hpp; nothing without one)
     std::vector<uint8_t const*> prior_mask;    // [prompt]: the prior itself, out_masks[] of the mark's entry (null without one)
+    std::vector<LassoSpec> lasso;      // [prompt]: what its lasso mark says (lasso_plan.hpp; nothing without one); its packed points
+                                       // are written once its click and box are derived (decode_batch_on)
+    std::vector<uint8_t const*> lasso_mask;    // [prompt]: the selection, out_masks[] of the mark's entry (null without one)
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -64,8 +68,11 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        PriorPlannedPrompts with_priors = plan_prior_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+        LassoPlannedPrompts with_lassos = plan_lasso_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
                                                              /*device_form*/ out_masks == nullptr);
+        PriorPlannedPrompts& with_priors = with_lassos.inner;
+        b.lasso = std::move(with_lassos.lasso);
+        for (LassoSpec const& l : b.lasso) b.lasso_mask.push_back(l.any() ? out_masks[l.entry] : nullptr);
         GridPlannedPrompts& planned = with_priors.planned;
         CleanedPrompts& plan = planned.cleaned;
         b.prior = std::move(with_priors.prior);
@@ -90,7 +97,7 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     b.coords.resize(total * 2);
     b.labels.resize(total);
     for (size_t j = 0; j < b.prompts.size(); ++j)
-        if (!b.grid[j].any())              // (a grid prompt's points are its grid's: pack_grid)
+        if (!b.grid[j].any() && !b.lasso[j].any())     // (a grid prompt's points are its grid's: pack_grid; a lasso prompt's are derived)
             pack_points(segs[b.prompts[j].head]->geometry(), b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions,
                         &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
     return b;
@@ -98,16 +105,17 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
 // What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
 // of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).  A prompt with
 // a prior is decoded the way a staged prompt is, whether it has refinement marks or not: its first stage takes a mask input.
+// So is a prompt with a lasso mark: its click and box are derived on the lane in front of its stages.
 // A grid prompt is a chunk of its own too, behind those: its side * side decodes and its label map run on one lane.
 struct BatchWork { PromptChunk part; bool staged; bool grid = false; };
 std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
     std::vector<int> plain;
     for (int j : mine)
-        if (!b.stages[j].staged() && !b.prior[j].any() && !b.grid[j].any()) plain.push_back(j);
+        if (!b.stages[j].staged() && !b.prior[j].any() && !b.lasso[j].any() && !b.grid[j].any()) plain.push_back(j);
     std::vector<BatchWork> work;
     for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
     for (int j : mine)
-        if (b.stages[j].staged() || b.prior[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+        if (b.stages[j].staged() || b.prior[j].any() || b.lasso[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
     for (int j : mine)
         if (b.grid[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, false, true});
     return work;
@@ -132,13 +140,14 @@ void pack_grid(ResizeLongestSide const& rs, int side, std::vector<float>& coords
 // mask input of the last stage: the plane the stage before it would deliver, where that decode left it.  first: the mask input
 // of the first stage -- the plane of the prompt's prior, or {nullptr, nullptr} when it has none -- which is what comes back
 // when the prompt has one stage only.
-k::MaskSource run_early_stages(SamModel& model, BatchPrompts const& b, int j, float const* emb, ResizeLongestSide const& rs,
-                               int const* points, int const* regions, k::MaskSource first) {
-    PromptStages const& st = b.stages[j];
+// spec, st, points, regions: the prompt and the arrays its clicks and box are read from -- the call's, or those of a lasso prompt
+// with its derived click and box written in (lasso_prompt_arrays).
+k::MaskSource run_early_stages(SamModel& model, PromptSpec const& spec, PromptStages const& st, float const* emb,
+                               ResizeLongestSide const& rs, int const* points, int const* regions, k::MaskSource first) {
     float coords[2 * k::kDecoderMaxPoints], labels[k::kDecoderMaxPoints];
     k::MaskSource src = first;
     for (size_t s = 0; s + 1 < st.stage_clicks.size(); ++s) {
-        const int npts = pack_points(rs, b.prompts[j], st, st.stage_clicks[s], points, regions, coords, labels);
+        const int npts = pack_points(rs, spec, st, st.stage_clicks[s], points, regions, coords, labels);
         model.decode(&emb, coords, labels, 1, npts, src.logits4 ? &src : nullptr, /*handles*/ true);
         // single_mask_job's rule: the best of planes 1..3 for a two-point stage, plane 0 otherwise
         src = k::MaskSource{model.logits(), npts > 2 ? nullptr : model.iou()};
@@ -616,8 +625,32 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 if (batch.prior[j].any())
                     first = model.prior_plane(batch.prior_mask[j], rs.original.width, rs.original.height, rs.resized.width, rs.resized.height,
                                               batch.prior[j].strength_milli);
-                const k::MaskSource src = run_early_stages(model, batch, j, emb[0], rs, points, regions, first);
-                model.decode(emb.data(), cc.data(), ll.data(), 1, npts, &src, /*handles*/ true);
+                k::MaskSource src;
+                if (batch.lasso[j].any()) {
+                    // a selection: uploaded and turned into the plane as a prior is, its box and click derived behind that; the
+                    // call waits for the lane's stream once, and the prompt is packed with what came back
+                    LassoSpec const& l = batch.lasso[j];
+                    int32_t record[kLassoRecordInts];
+                    const k::MaskSource plane = model.lasso_derive(batch.lasso_mask[j], rs.original.width, rs.original.height,
+                                                                   rs.resized.width, rs.resized.height, l.strength_milli, record);
+                    model.wait_caller_copies();
+                    if (record[0] == 0) {
+                        // nothing of this prompt is queued (lasso_derive waited for the stream): its slot goes back unused, so
+                        // that nothing is delivered to its out_masks
+                        cur.lease.release();
+                        throw Exception("mask batch: entry " + std::to_string(l.entry) + ": the lasso mark's selection is empty: no low-res "
+                                        "cell of it reaches half coverage, so there is no box and no click to derive");
+                    }
+                    const LassoPromptArrays own = lasso_prompt_arrays(prompts[j], batch.stages[j], l, points, regions, record);
+                    cc.resize((size_t)npts * 2);
+                    ll.resize((size_t)npts);
+                    pack_points(rs, own.spec, own.stages, own.spec.clicks, own.points.data(), own.regions.data(), cc.data(), ll.data());
+                    if (l.mask()) first = plane;
+                    src = run_early_stages(model, own.spec, own.stages, emb[0], rs, own.points.data(), own.regions.data(), first);
+                } else {
+                    src = run_early_stages(model, prompts[j], batch.stages[j], emb[0], rs, points, regions, first);
+                }
+                model.decode(emb.data(), cc.data(), ll.data(), 1, npts, src.logits4 ? &src : nullptr, /*handles*/ true);
                 model.wait_caller_copies();        // a prior read in place (pinned image memory): the caller's again
             } else {
                 model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);

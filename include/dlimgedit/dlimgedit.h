@@ -150,7 +150,10 @@ typedef struct dlimg_Api {
      * box.  A call without clean-up marks is read as it always was.
      * Prior marks (a mask input supplied by the caller): a continuation entry whose four ints are {DLIMG_PRIOR_MARK,
      * strength_milli, 0, 0} DIRECTLY BEHIND ITS HEAD -- see DLIMG_PRIOR_MARK below.  It is the one continuation entry whose
-     * out_masks[i] is READ: width * height bytes of the head's image, the prior. */
+     * out_masks[i] is READ: width * height bytes of the head's image, the prior.
+     * Lasso marks (a selection snapped to the object): a continuation entry whose four ints are {DLIMG_LASSO_MARK,
+     * strength_milli, what, 0} DIRECTLY BEHIND ITS HEAD -- see DLIMG_LASSO_MARK below.  Its out_masks[i] is READ likewise: the
+     * selection, from which the prompt's box and first click are derived on the GPU. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -199,6 +202,41 @@ typedef struct dlimg_Api {
  * (pe.mask.*), a grid prompt, and dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a prior
  * from.  A call without prior marks is read as it always was. */
 #define DLIMG_PRIOR_MARK 8
+/* regions[4 i] of a lasso mark in get_segmentation_masks (slot 14): {DLIMG_LASSO_MARK, strength_milli, what, 0} directly behind
+ * its head makes a prompt of a selection the caller already holds -- a dragged lasso, a painted blob -- so that it snaps to the
+ * object.  points[i] of the mark is not read.  out_masks[i] OF THE MARK IS READ AS THE SELECTION under the rules of a prior
+ * mark: width * height bytes of the head's image, tightly packed, 0 .. 255 read as coverage; it may be out_masks[head] itself
+ * (it is taken before anything is delivered); in memory from create_image it is sent from where it lies.
+ * what is a bit set, 0 meaning all three:
+ *   DLIMG_LASSO_BOX    the prompt's box is the selection's box; the head's region must be empty (x1 < x0)
+ *   DLIMG_LASSO_CLICK  the prompt's FIRST click is a foreground click at the selection's most interior point; it counts towards
+ *                      the 8 clicks and towards a SAM-HQ file's point limit
+ *   DLIMG_LASSO_MASK   the selection is also the mask input of the prompt's first stage, exactly as a prior mark with this
+ *                      strength_milli would make it (0 = 8000; needs pe.mask.*)
+ * strength_milli is 0 without DLIMG_LASSO_MASK.  what == 4 derives nothing and is refused: that is a prior mark.
+ * The derivation is integer arithmetic on the 256 x 256 low-res grid of the prior plane.  A cell is INSIDE when the mean
+ * coverage of the source pixels it stands for is above one half (where the prior plane is positive); everything else,
+ * everything outside the image included, is background.  The box is the union of the inside cells' source pixels, {x0, y0, x1,
+ * y1} with x1, y1 one past the last pixel.  The click is the middle pixel of the inside cell farthest (exact Euclidean distance
+ * on the grid) from any background cell, ties to the smallest y, then the smallest x.
+ * The packed order is SAM's: the derived click, the caller's clicks in the order given (the head's point is the first of them
+ * in a call with `points`), the box corners; the padding point only without a box.  Refinement marks, a clean-up mark and
+ * further clicks work as on any prompt: the derived click belongs to the first stage, the box to every stage.  A lasso-only
+ * prompt lives in a call without `points`, like a box-only call: head {0, 0, -1, -1}, then the mark.
+ * Refused before anything is launched (the message says "mark" and names the entry): a mark that is not directly behind a
+ * head, a second lasso mark or a prior mark on the same prompt, a NULL selection, what outside 0 .. 7, what == 4, a non-zero
+ * fourth int, strength_milli outside 0 .. 100000 or non-zero without DLIMG_LASSO_MASK, DLIMG_LASSO_BOX on a head whose region
+ * is not empty, DLIMG_LASSO_MASK on a model without the mask branch, a grid prompt, more than 8 clicks counting the derived
+ * one, and dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a selection from.
+ * ONE refusal arrives later: a selection with no inside cell (all of it below half coverage of every low-res cell) is
+ * reported after its derivation ran and before its prompt is decoded -- "entry i: the lasso mark's selection is empty ...".
+ * out_masks of that prompt is not written; what OTHER prompts of the same call have received by then is unspecified, as with
+ * the report of an encoder overflow.  The call waits for the GPU once per lasso prompt (the derived prompt comes back to the
+ * host).  A call without lasso marks is read as it always was. */
+#define DLIMG_LASSO_MARK 10
+#define DLIMG_LASSO_BOX 1
+#define DLIMG_LASSO_CLICK 2
+#define DLIMG_LASSO_MASK 4
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

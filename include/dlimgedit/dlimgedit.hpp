@@ -227,6 +227,18 @@ struct Prior {
     int strength_milli = 0;
 };
 
+// A lasso: a selection the caller already holds (a dragged lasso, a painted blob) that should SNAP to the object.  mask: as a
+// Prior's.  what: a bit set of DLIMG_LASSO_BOX (the prompt's box is the selection's), DLIMG_LASSO_CLICK (the prompt's first
+// click is a foreground click at the selection's most interior point) and DLIMG_LASSO_MASK (the selection is the mask input of
+// the first stage as well, at strength_milli as a Prior's; needs a model with the mask branch); 0: all three.  Box and click
+// are derived on the GPU.  strength_milli is 0 without DLIMG_LASSO_MASK.  Travels as a lasso mark of table slot 14
+// (dlimgedit.h, DLIMG_LASSO_MARK).
+struct Lasso {
+    uint8_t const* mask = nullptr;
+    int what = 0;
+    int strength_milli = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -333,12 +345,57 @@ class Segmentation {
     // a mark after every click but the last.  Needs a model with the mask branch.
     // clean: the mask is delivered cleaned (MaskCleanup).
     // prior: the caller's own mask as the mask input of the first stage (Prior).
+    // lasso: the caller's selection, from which the box and / or the first click are derived (Lasso); the clicks given here
+    // follow the derived one, and refine_after counts the clicks given here.  With DLIMG_LASSO_BOX there is no `region`.
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
                        std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
-                       std::optional<Prior> prior = std::nullopt) const {
+                       std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
                                             clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
-                                            prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{})[0]);
+                                            prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{},
+                                            lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{})[0]);
+    }
+
+    // Snap a selection to the object (addition of this build): the lasso alone is the prompt -- its box, its most interior
+    // point as a foreground click, and the selection itself as the mask input, whichever `what` names (Lasso) -- or the lasso
+    // and further clicks behind the derived one.  refine_after and cleanup as for compute_mask.  out_mask may be lasso.mask
+    // itself: a selection snapped in place.
+    void snap(Lasso const& lasso, uint8_t* out_mask, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
+              std::optional<MaskCleanup> cleanup = std::nullopt) const {
+        if (!lasso.mask || !out_mask) throw Exception("snap: a lasso has a mask, and the result a place to go");
+        if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
+            throw Exception("snap: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
+        if (clicks.size() > 8) throw Exception("snap: a prompt takes at most 8 clicks");
+        for (size_t m = 0; m < refine_after.size(); ++m)
+            if (refine_after[m] < 1 || refine_after[m] >= int(clicks.size()) || (m && refine_after[m] <= refine_after[m - 1]))
+                throw Exception("snap: refine_after holds click counts k, strictly increasing, 1 <= k < the clicks given");
+        // the head with an empty region, the lasso mark directly behind it, then the further clicks and marks; without clicks
+        // the call has no `points`, like a box-only call
+        std::vector<dlimg_Segmentation> hs{handle_.get(), nullptr};
+        std::vector<Point> pts{clicks.empty() ? Point{0, 0} : clicks[0].point, Point{0, 0}};
+        std::vector<Region> regs{Region(Point{0, 0}, Point{-1, -1}), Region(Point{DLIMG_LASSO_MARK, lasso.strength_milli}, Point{lasso.what, 0})};
+        std::vector<uint8_t*> ptrs{out_mask, const_cast<uint8_t*>(lasso.mask)};
+        auto entry = [&](Point p, Region r) {
+            hs.push_back(nullptr);
+            pts.push_back(p);
+            regs.push_back(r);
+            ptrs.push_back(nullptr);
+        };
+        for (size_t c = 1; c < clicks.size(); ++c) {
+            if (std::find(refine_after.begin(), refine_after.end(), int(c)) != refine_after.end())
+                entry(Point{0, 0}, Region(Point{DLIMG_REFINE_MARK, 0}, Point{0, 0}));
+            entry(clicks[c].point, Region(Point{clicks[c].foreground ? 1 : 0, 0}, Point{0, 0}));
+        }
+        if (!clicks.empty() && !clicks[0].foreground) throw Exception("snap: the first click given is a foreground click");
+        if (cleanup) entry(Point{0, 0}, Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}));
+        detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), clicks.empty() ? nullptr : &pts.data()->x,
+                                                   &regs.data()->top_left.x, ptrs.data()));
+    }
+    Image snap(Lasso const& lasso, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
+               std::optional<MaskCleanup> cleanup = std::nullopt) const {
+        Image m(extent(), Channels::mask);
+        snap(lasso, m.pixels(), clicks, refine_after, cleanup);
+        return m;
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -348,20 +405,25 @@ class Segmentation {
 
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
     // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
-    // optional clean-up per prompt; prior: empty, or one optional prior per prompt.
+    // optional clean-up per prompt; prior: empty, or one optional prior per prompt; lasso: empty, or one optional lasso per
+    // prompt (a prompt takes a prior or a lasso, not both).
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
                                                  std::vector<std::vector<int>> const& refine_after = {},
                                                  std::vector<std::optional<MaskCleanup>> const& clean = {},
-                                                 std::vector<std::optional<Prior>> const& prior = {}) {
+                                                 std::vector<std::optional<Prior>> const& prior = {},
+                                                 std::vector<std::optional<Lasso>> const& lasso = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
             (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
-            (!prior.empty() && prior.size() != segs.size()))
+            (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
         for (auto const& p : prior)
             if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
                 throw Exception("compute_mask_batch: a prior has a mask and a strength_milli of 0 (the default) .. 100000");
+        for (auto const& l : lasso)
+            if (l && (!l->mask || l->what < 0 || l->what > 7 || l->what == DLIMG_LASSO_MASK || l->strength_milli < 0 || l->strength_milli > 100000))
+                throw Exception("compute_mask_batch: a lasso has a mask, a `what` of 0 (all) .. 7 other than 4, and a strength_milli of 0 .. 100000");
         for (auto const& c : clean)
             if (c && (c->max_hole < 0 || c->max_island < 0 || (c->max_hole == 0 && c->max_island == 0)))
                 throw Exception("compute_mask_batch: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
@@ -375,7 +437,7 @@ class Segmentation {
             if (clicks[j].empty() || clicks[j].size() > 8) throw Exception("compute_mask_batch: a prompt takes 1 to 8 clicks");
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
             refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value()) ||
-                      (!prior.empty() && prior[j].has_value());                                        // any continuation entry
+                      (!prior.empty() && prior[j].has_value()) || (!lasso.empty() && lasso[j].has_value());     // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -407,6 +469,12 @@ class Segmentation {
                         pts.push_back(Point{0, 0});      // its out_masks pointer is the prior, which the call only reads
                         ptrs.push_back(const_cast<uint8_t*>(prior[j]->mask));
                         regs.push_back(Region(Point{DLIMG_PRIOR_MARK, prior[j]->strength_milli}, Point{0, 0}));
+                    }
+                    if (c == 0 && !lasso.empty() && lasso[j]) {
+                        hs.push_back(nullptr);           // the lasso mark, directly behind its head, likewise: its out_masks pointer
+                        pts.push_back(Point{0, 0});      // is the selection
+                        ptrs.push_back(const_cast<uint8_t*>(lasso[j]->mask));
+                        regs.push_back(Region(Point{DLIMG_LASSO_MARK, lasso[j]->strength_milli}, Point{lasso[j]->what, 0}));
                     }
                 }
                 if (!clean.empty() && clean[j]) {
