@@ -23,7 +23,7 @@ import numpy as np
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libdlimgedit.so"
 # The test and benchmark hooks (include/dlimgedit/dlimgedit_amd_test.h: ext.test_*, ext.bench_*, ext.force_gemm_tile,
 # ext.mask_pieces, ext.plan_steps) are not in the product library: they come from lib/libdlimgedit_test.so, the product's own
-# objects plus csrc/test_hooks.cpp, loaded next to the product the first time a hook is called.
+# objects plus the hook sources csrc/*test_hooks.cpp, loaded next to the product the first time a hook is called.
 HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_test.so")
 # tools/ only: the -DDLIMG_TUNING build with ablated kernel variants and in-kernel stamps (python -m dlimgedit_amd.build --tuning);
 # it exports the hooks too, so one library serves both roles
@@ -153,131 +153,6 @@ def hooks_library() -> C.CDLL:
             _hooks_lib.dlimg_init.restype = C.POINTER(_Api)
             _hooks_lib.dlimg_init.argtypes = []
     return _hooks_lib
-
-
-_neck_hooks_lib = None
-NECK_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_neck_test.so")
-# the hooks of the two encoder-neck launches (csrc/neck_test_hooks.cpp): bound by name, no header declares them
-NECK_HOOK_EXPORTS = ("dlimg_amd_test_neck_conv1x1_ln", "dlimg_amd_test_neck_conv3x3_ln")
-
-
-def neck_hooks_library() -> C.CDLL:
-    """Loads lib/libdlimgedit_neck_test.so: the product's objects plus the hooks of the two encoder-neck launches.  Raises if
-    it has not been built; there is no fallback."""
-    global _neck_hooks_lib
-    if _neck_hooks_lib is None:
-        if not NECK_HOOKS_LIB_PATH.exists():
-            raise Error(f"{NECK_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
-        lib = C.CDLL(str(NECK_HOOKS_LIB_PATH))
-        lib.dlimg_init.restype = C.POINTER(_Api)
-        lib.dlimg_init.argtypes = []
-        vp, ci, cf = C.c_void_p, C.c_int, C.c_float
-        lib.dlimg_amd_test_neck_conv1x1_ln.argtypes = [vp, ci, ci, vp, vp, vp, cf, vp, vp, vp, C.POINTER(ci)]
-        lib.dlimg_amd_test_neck_conv3x3_ln.argtypes = [vp, ci, vp, vp, vp, cf, vp, vp, vp, C.POINTER(ci)]
-        lib.dlimg_amd_test_neck_conv1x1_ln.restype = lib.dlimg_amd_test_neck_conv3x3_ln.restype = ci
-        _neck_hooks_lib = lib
-    return _neck_hooks_lib
-
-
-_cleanup_hooks_lib = None
-CLEANUP_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_cleanup_test.so")
-# the hook of the mask clean-up kernels alone (csrc/cleanup_test_hooks.cpp): bound by name, no header declares it
-CLEANUP_HOOK_EXPORTS = ("dlimg_amd_test_mask_cleanup",)
-
-
-def cleanup_hooks_library() -> C.CDLL:
-    """Loads lib/libdlimgedit_cleanup_test.so: the product's objects plus the hook of the mask clean-up kernels.  Raises if it
-    has not been built; there is no fallback."""
-    global _cleanup_hooks_lib
-    if _cleanup_hooks_lib is None:
-        if not CLEANUP_HOOKS_LIB_PATH.exists():
-            raise Error(f"{CLEANUP_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
-        lib = C.CDLL(str(CLEANUP_HOOKS_LIB_PATH))
-        lib.dlimg_init.restype = C.POINTER(_Api)
-        lib.dlimg_init.argtypes = []
-        ip = C.POINTER(C.c_int)
-        lib.dlimg_amd_test_mask_cleanup.argtypes = [C.POINTER(C.c_void_p), ip, ip, ip, ip, C.c_int]
-        lib.dlimg_amd_test_mask_cleanup.restype = C.c_int
-        _cleanup_hooks_lib = lib
-    return _cleanup_hooks_lib
-
-
-_grid_hooks_lib = None
-GRID_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_grid_test.so")
-# the hook of the label-map kernels alone (csrc/grid_test_hooks.cpp): bound by name, no header declares it
-GRID_HOOK_EXPORTS = ("dlimg_amd_test_grid_kernels",)
-
-
-def grid_hooks_library() -> C.CDLL:
-    """Loads lib/libdlimgedit_grid_test.so: the product's objects plus the hook of the label-map kernels.  Raises if it has
-    not been built; there is no fallback."""
-    global _grid_hooks_lib
-    if _grid_hooks_lib is None:
-        if not GRID_HOOKS_LIB_PATH.exists():
-            raise Error(f"{GRID_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
-        lib = C.CDLL(str(GRID_HOOKS_LIB_PATH))
-        lib.dlimg_init.restype = C.POINTER(_Api)
-        lib.dlimg_init.argtypes = []
-        ip, fp = C.POINTER(C.c_int), C.POINTER(C.c_float)
-        lib.dlimg_amd_test_grid_kernels.argtypes = [fp, C.c_int, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int,
-                                                    C.c_int, C.POINTER(C.c_int32), fp, C.c_void_p, ip, ip, ip, C.c_int, fp]
-        lib.dlimg_amd_test_grid_kernels.restype = C.c_int
-        _grid_hooks_lib = lib
-    return _grid_hooks_lib
-
-
-_prior_hooks_lib = None
-PRIOR_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_prior_test.so")
-# the hook of the prior-plane kernel alone (csrc/prior_test_hooks.cpp): bound by name, no header declares it
-PRIOR_HOOK_EXPORTS = ("dlimg_amd_test_prior_plane",)
-
-
-def prior_hooks_library() -> C.CDLL:
-    """Loads lib/libdlimgedit_prior_test.so: the product's objects plus the hook of the prior-plane kernel.  Raises if it has
-    not been built; there is no fallback."""
-    global _prior_hooks_lib
-    if _prior_hooks_lib is None:
-        if not PRIOR_HOOKS_LIB_PATH.exists():
-            raise Error(f"{PRIOR_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
-        lib = C.CDLL(str(PRIOR_HOOKS_LIB_PATH))
-        lib.dlimg_init.restype = C.POINTER(_Api)
-        lib.dlimg_init.argtypes = []
-        ci = C.c_int
-        lib.dlimg_amd_test_prior_plane.argtypes = [C.c_void_p, ci, ci, ci, ci, ci, C.POINTER(C.c_float), C.POINTER(ci), ci,
-                                                   C.POINTER(C.c_float)]
-        lib.dlimg_amd_test_prior_plane.restype = ci
-        _prior_hooks_lib = lib
-    return _prior_hooks_lib
-
-
-_lasso_hooks_lib = None
-LASSO_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_lasso_test.so")
-# the hook of the lasso derivation alone (csrc/lasso_test_hooks.cpp): bound by name, no header declares it
-LASSO_HOOK_EXPORTS = ("dlimg_amd_test_lasso_derive",)
-
-
-def lasso_hooks_library() -> C.CDLL:
-    """Loads lib/libdlimgedit_lasso_test.so: the product's objects plus the hook of the lasso derivation.  Raises if it has not
-    been built; there is no fallback."""
-    global _lasso_hooks_lib
-    if _lasso_hooks_lib is None:
-        if not LASSO_HOOKS_LIB_PATH.exists():
-            raise Error(f"{LASSO_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
-        lib = C.CDLL(str(LASSO_HOOKS_LIB_PATH))
-        lib.dlimg_init.restype = C.POINTER(_Api)
-        lib.dlimg_init.argtypes = []
-        ci = C.c_int
-        lib.dlimg_amd_test_lasso_derive.argtypes = [C.c_void_p, ci, ci, ci, ci, C.POINTER(C.c_int32), C.POINTER(ci), ci,
-                                                    C.POINTER(C.c_float)]
-        lib.dlimg_amd_test_lasso_derive.restype = ci
-        _lasso_hooks_lib = lib
-    return _lasso_hooks_lib
-
-
-def _check_neck_hook(result: int) -> None:
-    if result != 0:
-        msg = neck_hooks_library().dlimg_init().contents.last_error()
-        raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
 
 
 def _check_hook(result: int) -> None:
@@ -1086,40 +961,51 @@ class ext:
             cls._sigs_done = True
         return lib
 
+    # (argument types, result type) of every hook of the test / tuning libraries, as include/dlimgedit/dlimgedit_amd_test.h
+    # declares them; tests/test_abi.py holds its keys to HOOK_EXPORTS
+    _vp, _ci, _cf, _ip, _fp = C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int), C.POINTER(C.c_float)
+    _HOOK_SIGS = {
+        "dlimg_amd_test_mask_pieces": ([_ci, C.POINTER(C.c_longlong), C.c_longlong, C.POINTER(C.c_longlong), _ci,
+                                       C.POINTER(C.c_longlong), _ci, _ip], _ci),
+        "dlimg_amd_test_plan_steps": ([_ci, _ip, _ip, _ip, _ci, _ci, _ci, _ci, _ip, _ip, _ci], _ci),
+        "dlimg_amd_test_parse_cpu_list": ([C.c_char_p, _ip, _ci], _ci),
+        "dlimg_amd_test_preprocess": ([_vp, _ci, _ci, _ci, _ci, _vp], _ci),
+        "dlimg_amd_test_postprocess": ([_vp, _ci, _vp, _ci, _ci, _vp], _ci),
+        "dlimg_amd_test_postprocess_batch": ([_vp, _ci, _ci, _ci, _vp], _ci),
+        "dlimg_amd_test_force_gemm_tile": ([_ci], _ci),
+        "dlimg_amd_test_force_gemm_consumer_tile": ([_ci], _ci),
+        "dlimg_amd_test_gemm": ([_ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp], _ci),
+        "dlimg_amd_test_gemm_ln": ([_ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _ci, _vp, _vp, _vp, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_gemm_tile_shape": ([_ci, _ip, _ip], _ci),
+        "dlimg_amd_test_lane_worker": ([_ci, _ci, _vp], _ci),
+        "dlimg_amd_test_gemm_stream": ([_ci, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp], _ci),
+        "dlimg_amd_test_layernorm": ([_vp, _vp, _vp, _cf, _ci, _ci, _ci, _vp, _vp], _ci),
+        "dlimg_amd_test_attention": ([_ci, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp], _ci),
+        "dlimg_amd_test_resize": ([_vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp], _ci),
+        "dlimg_amd_test_decode": ([_vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp], _ci),
+        "dlimg_amd_test_decode_prompts": ([_vp, _ci, _vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, C.c_char_p, _ci], _ci),
+        "dlimg_amd_test_encoder_state": ([_vp, C.POINTER(_ImageView), _ci, _ci, _vp, C.c_longlong, C.c_char_p, _ci, _ci, _vp,
+                                          C.c_longlong, C.c_char_p, _ci], _ci),
+        "dlimg_amd_test_neck_conv1x1_ln": ([_vp, _ci, _ci, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_neck_conv3x3_ln": ([_vp, _ci, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_mask_cleanup": ([C.POINTER(C.c_void_p), _ip, _ip, _ip, _ip, _ci], _ci),
+        "dlimg_amd_test_grid_kernels": ([_fp, _ci, _fp, _ci, _ci, _ci, _ci, _ci, _ci, _ip, _ci, _ci, C.POINTER(C.c_int32), _fp, _vp,
+                                         _ip, _ip, _ip, _ci, _fp], _ci),
+        "dlimg_amd_test_prior_plane": ([_vp, _ci, _ci, _ci, _ci, _ci, _fp, _ip, _ci, _fp], _ci),
+        "dlimg_amd_test_lasso_derive": ([_vp, _ci, _ci, _ci, _ci, C.POINTER(C.c_int32), _ip, _ci, _fp], _ci),
+        "dlimg_amd_bench_attention": ([_ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
+        "dlimg_amd_bench_prepost": ([_ci, _ci, _ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], _ci),
+        "dlimg_amd_bench_gemm": ([_ci, _ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
+        "dlimg_amd_bench_gemm_streams": ([_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
+        "dlimg_amd_bench_gemm_stamps": ([_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double), _vp, _ci], _ci),
+    }
+
     @classmethod
     def _h(cls):
-        """The library with the test / benchmark hooks (hooks_library())."""
+        """The library with the test / benchmark hooks (hooks_library()), their argument types set."""
         lib = hooks_library()
         if not cls._hook_sigs_done:
-            vp, ci, cf = C.c_void_p, C.c_int, C.c_float
-            cls._apply(lib, {
-                "dlimg_amd_test_mask_pieces": ([ci, C.POINTER(C.c_longlong), C.c_longlong, C.POINTER(C.c_longlong), ci,
-                                               C.POINTER(C.c_longlong), ci, C.POINTER(ci)], ci),
-                "dlimg_amd_test_plan_steps": ([ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci), ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), ci], ci),
-                "dlimg_amd_test_parse_cpu_list": ([C.c_char_p, C.POINTER(ci), ci], ci),
-                "dlimg_amd_test_preprocess": ([vp, ci, ci, ci, ci, vp], ci),
-                "dlimg_amd_test_postprocess": ([vp, ci, vp, ci, ci, vp], ci),
-                "dlimg_amd_test_postprocess_batch": ([vp, ci, ci, ci, vp], ci),
-                "dlimg_amd_test_force_gemm_tile": ([ci], ci),
-                "dlimg_amd_test_force_gemm_consumer_tile": ([ci], ci),
-                "dlimg_amd_test_gemm": ([ci, ci, ci, vp, vp, vp, vp, ci, ci, vp, vp], ci),
-                "dlimg_amd_test_gemm_ln": ([ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp, C.POINTER(ci)], ci),
-                "dlimg_amd_test_gemm_tile_shape": ([ci, C.POINTER(ci), C.POINTER(ci)], ci),
-                "dlimg_amd_test_lane_worker": ([ci, ci, vp], ci),
-                "dlimg_amd_test_gemm_stream": ([ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp], ci),
-                "dlimg_amd_test_layernorm": ([vp, vp, vp, cf, ci, ci, ci, vp, vp], ci),
-                "dlimg_amd_test_attention": ([ci, vp, vp, vp, vp, ci, ci, ci, vp], ci),
-                "dlimg_amd_test_resize": ([vp, ci, ci, ci, ci, ci, ci, vp], ci),
-                "dlimg_amd_test_decode": ([vp, ci, vp, ci, vp, vp, vp, vp, vp], ci),
-                "dlimg_amd_test_decode_prompts": ([vp, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, C.c_char_p, ci], ci),
-                "dlimg_amd_test_encoder_state": ([vp, C.POINTER(_ImageView), ci, ci, vp, C.c_longlong, C.c_char_p, ci, ci, vp,
-                                                  C.c_longlong, C.c_char_p, ci], ci),
-                "dlimg_amd_bench_attention": ([ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
-                "dlimg_amd_bench_prepost": ([ci, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], ci),
-                "dlimg_amd_bench_gemm": ([ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
-                "dlimg_amd_bench_gemm_streams": ([ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double)], ci),
-                "dlimg_amd_bench_gemm_stamps": ([ci, ci, ci, ci, ci, ci, ci, ci, ci, C.POINTER(C.c_double), vp, ci], ci),
-            })
+            cls._apply(lib, cls._HOOK_SIGS)
             cls._hook_sigs_done = True
         return lib
 
@@ -1141,6 +1027,8 @@ class ext:
                "dlimg_amd_test_lane_worker", "dlimg_amd_test_gemm_stream", "dlimg_amd_test_layernorm",
                "dlimg_amd_test_attention", "dlimg_amd_test_resize", "dlimg_amd_test_decode", "dlimg_amd_test_decode_prompts",
                "dlimg_amd_test_encoder_state",
+               "dlimg_amd_test_neck_conv1x1_ln", "dlimg_amd_test_neck_conv3x3_ln", "dlimg_amd_test_mask_cleanup",
+               "dlimg_amd_test_grid_kernels", "dlimg_amd_test_prior_plane", "dlimg_amd_test_lasso_derive",
                "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps", "dlimg_amd_test_gemm_tile_shape")
@@ -1518,7 +1406,7 @@ class ext:
 
     @classmethod
     def test_mask_cleanup(cls, masks, max_hole, max_island, shapes=None) -> list:
-        """The mask clean-up kernels alone (the hook of cleanup_hooks_library()): `masks`, (h, w) uint8 arrays of 0 / 255 of
+        """The mask clean-up kernels alone (dlimg_amd_test_mask_cleanup): `masks`, (h, w) uint8 arrays of 0 / 255 of
         possibly different sizes, as ONE k::mask_cleanup call on the default device; max_hole / max_island: one int for all or
         one per mask.  Returns the cleaned masks (the inputs are left alone).  For the launcher's refusals a mask may be None
         (a null pointer) and shapes[i] = (h, w) may claim an extent of its own; a refusal raises Error."""
@@ -1535,17 +1423,14 @@ class ext:
         ptrs = (C.c_void_p * n)(*[None if o is None else o.ctypes.data for o in outs])
         w = (C.c_int * n)(*[int(s[1]) for s in shapes])
         h = (C.c_int * n)(*[int(s[0]) for s in shapes])
-        rc = cleanup_hooks_library().dlimg_amd_test_mask_cleanup(ptrs, w, h, (C.c_int * n)(*hole), (C.c_int * n)(*isle), n)
-        if rc != 0:
-            msg = cleanup_hooks_library().dlimg_init().contents.last_error()
-            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        _check_hook(cls._h().dlimg_amd_test_mask_cleanup(ptrs, w, h, (C.c_int * n)(*hole), (C.c_int * n)(*isle), n))
         return outs
 
     @classmethod
     def test_grid_kernels(cls, planes4: np.ndarray, out_w: int, out_h: int, pre_w: int, pre_h: int, kept=None, iou4=None,
                           iou_permille: int = 0, stability_permille: int = 0, cull: bool = True, want_store: bool = False,
                           time_iters: int = 0):
-        """The label-map kernels alone (the hook of grid_hooks_library()): planes4 [P, 4, 256, 256] fp32 as a decode leaves them,
+        """The label-map kernels alone (dlimg_amd_test_grid_kernels): planes4 [P, 4, 256, 256] fp32 as a decode leaves them,
         harvested in chunks of 16 prompts; then the candidates `kept` (label order; candidate c = 3 * prompt + plane - 1) are
         painted into an (out_h, out_w) map for an image encoded at pre_w x pre_h -- or, with kept None, the candidates the
         library's own selection keeps from the records and iou4 [P, 4] with the two thresholds.
@@ -1565,20 +1450,16 @@ class ext:
         kout = np.zeros(255, np.int32)
         nk, ok = C.c_int(0), C.c_int(0)
         ms = (C.c_float * 2)(0.0, 0.0)
-        lib = grid_hooks_library()
-        rc = lib.dlimg_amd_test_grid_kernels(
+        _check_hook(cls._h().dlimg_amd_test_grid_kernels(
             planes4.ctypes.data_as(fp), P, None if iou is None else iou.ctypes.data_as(fp), out_w, out_h, pre_w, pre_h,
             iou_permille, stability_permille, None if kin is None else kin.ctypes.data_as(ip), -1 if kin is None else len(kin),
             int(cull), records.ctypes.data_as(C.POINTER(C.c_int32)), None if store is None else store.ctypes.data_as(fp),
-            out.ctypes.data, kout.ctypes.data_as(ip), C.byref(nk), C.byref(ok), int(time_iters), ms)
-        if rc != 0:
-            msg = lib.dlimg_init().contents.last_error()
-            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+            out.ctypes.data, kout.ctypes.data_as(ip), C.byref(nk), C.byref(ok), int(time_iters), ms))
         return records, out, [int(v) for v in kout[:nk.value]], bool(ok.value), (store if time_iters <= 0 else (ms[0], ms[1]))
 
     @classmethod
     def test_prior_plane(cls, mask: np.ndarray, pre_w: int, pre_h: int, strength_milli: int, time_iters: int = 0):
-        """The prior-plane kernel alone (the hook of prior_hooks_library()): mask (h, w) uint8, of an image that was encoded at
+        """The prior-plane kernel alone (dlimg_amd_test_prior_plane): mask (h, w) uint8, of an image that was encoded at
         pre_w x pre_h, through ONE k::mask_prior launch on the default device, with guard bytes around the plane and around the
         mask's device copy.  -> (plane float32 [256, 256], guard bytes intact); with time_iters > 0 a third element, the
         milliseconds of one launch (the mean of time_iters repetitions between two events).  A refusal of the launcher raises
@@ -1588,17 +1469,14 @@ class ext:
         h, w = mask.shape
         plane = np.zeros((256, 256), np.float32)
         ok, ms = C.c_int(0), C.c_float(0.0)
-        lib = prior_hooks_library()
-        rc = lib.dlimg_amd_test_prior_plane(mask.ctypes.data, w, h, int(pre_w), int(pre_h), int(strength_milli),
-                                            plane.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ok), int(time_iters), C.byref(ms))
-        if rc != 0:
-            msg = lib.dlimg_init().contents.last_error()
-            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        _check_hook(cls._h().dlimg_amd_test_prior_plane(mask.ctypes.data, w, h, int(pre_w), int(pre_h), int(strength_milli),
+                                                        plane.ctypes.data_as(C.POINTER(C.c_float)), C.byref(ok), int(time_iters),
+                                                        C.byref(ms)))
         return (plane, bool(ok.value)) if time_iters <= 0 else (plane, bool(ok.value), float(ms.value))
 
     @classmethod
     def test_lasso_derive(cls, mask: np.ndarray, pre_w: int, pre_h: int, time_iters: int = 0):
-        """The lasso derivation alone (the hook of lasso_hooks_library()): mask (h, w) uint8, of an image that was encoded at
+        """The lasso derivation alone (dlimg_amd_test_lasso_derive): mask (h, w) uint8, of an image that was encoded at
         pre_w x pre_h, through k::mask_prior, the two launches of k::lasso_derive and the host's fold, with guard bytes around
         every device buffer.  -> (record int32 [8] = inside cells, box x0, y0, x1, y1, click x, click y, d2; guard bytes
         intact); with time_iters > 0 a third element, the milliseconds of one derivation (both launches; the mean of
@@ -1608,12 +1486,9 @@ class ext:
         h, w = mask.shape
         record = np.zeros(8, np.int32)
         ok, ms = C.c_int(0), C.c_float(0.0)
-        lib = lasso_hooks_library()
-        rc = lib.dlimg_amd_test_lasso_derive(mask.ctypes.data, w, h, int(pre_w), int(pre_h), record.ctypes.data_as(C.POINTER(C.c_int32)),
-                                             C.byref(ok), int(time_iters), C.byref(ms))
-        if rc != 0:
-            msg = lib.dlimg_init().contents.last_error()
-            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        _check_hook(cls._h().dlimg_amd_test_lasso_derive(mask.ctypes.data, w, h, int(pre_w), int(pre_h),
+                                                         record.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ok), int(time_iters),
+                                                         C.byref(ms)))
         return (record, bool(ok.value)) if time_iters <= 0 else (record, bool(ok.value), float(ms.value))
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
@@ -1622,7 +1497,7 @@ class ext:
     @classmethod
     def test_neck_conv_ln(cls, env: Environment, x, w, gamma, beta, eps: float, want_f16: bool = True, want_f32: bool = True,
                           own_buffer=None):
-        """One launch of the encoder neck on device buffers (the hooks of neck_hooks_library()): convolution +
+        """One launch of the encoder neck on device buffers (dlimg_amd_test_neck_conv1x1_ln / _conv3x3_ln): convolution +
         LayerNorm2d.  x: f16 [B*4096][K] with w [256][K] (1x1), or f16 [B][64][64][256] with w [256][2304] (3x3, zero pad 1,
         columns (ky*3+kx)*256 + c).  own_buffer (optional, one bool per image): image i's fp32 result goes to a device buffer
         of its own with NECK_GUARD bytes of NECK_GUARD_BYTE on either side, the others to the shared workspace.
@@ -1657,13 +1532,13 @@ class ext:
             for i in range(B):
                 ptrs[i] = dev(fill) + G if own[i] else None
             flag = C.c_int(-1)
-            h = neck_hooks_library()
+            h = cls._h()
             if conv3:
                 rc = h.dlimg_amd_test_neck_conv3x3_ln(d_x, B, d_w, d_g, d_b, eps, d_h, ptrs if any(own) else None, d_ws, C.byref(flag))
             else:
                 rc = h.dlimg_amd_test_neck_conv1x1_ln(d_x, B, K, d_w, d_g, d_b, eps, d_h, ptrs if any(own) else None, d_ws,
                                                       C.byref(flag))
-            _check_neck_hook(rc)
+            _check_hook(rc)
             out16 = out32 = None
             guards = [None] * B
             if want_f16:

@@ -3,23 +3,12 @@
 In-tree, no cmake: `python -m dlimgedit_amd.build`.  hipcc cross-compiles without a GPU, so this also
 runs in the CPU-only build container.  Objects are cached by source mtime under csrc/_obj/.
 
-Seven libraries (and the tuning build) come out of the same sources:
+Three libraries come out of the same sources:
   lib/libdlimgedit.so         the product: dlimg_init + the extension entry points of include/dlimgedit/dlimgedit_amd.h,
                               named one by one in csrc/exports.map
-  lib/libdlimgedit_test.so    the product's OBJECTS plus csrc/test_hooks.cpp: additionally exports the dlimg_amd_test_* /
-                              dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h) the parity tests and the
-                              kernels-alone timing loops call; built by default next to the product
-  lib/libdlimgedit_neck_test.so  the product's OBJECTS plus csrc/neck_test_hooks.cpp: the hooks of the two encoder-neck launches
-                              (tests/test_gpu_neck.py) in a library of their own because the set of hooks the test library
-                              exports is pinned (tests/test_abi.py); built by default next to the other two
-  lib/libdlimgedit_cleanup_test.so  the product's OBJECTS plus csrc/cleanup_test_hooks.cpp: the hook of the mask clean-up
-                              kernels alone (tests/test_gpu_cleanup.py), a library of its own for the same reason; built by default
-  lib/libdlimgedit_grid_test.so  the product's OBJECTS plus csrc/grid_test_hooks.cpp: the hook of the label-map kernels alone
-                              (tests/test_gpu_grid_kernels.py), a library of its own for the same reason; built by default
-  lib/libdlimgedit_prior_test.so  the product's OBJECTS plus csrc/prior_test_hooks.cpp: the hook of the prior-plane kernel alone
-                              (tests/test_gpu_prior_kernel.py), a library of its own for the same reason; built by default
-  lib/libdlimgedit_lasso_test.so  the product's OBJECTS plus csrc/lasso_test_hooks.cpp: the hook of the lasso derivation alone
-                              (tests/test_gpu_lasso_kernel.py), a library of its own for the same reason; built by default
+  lib/libdlimgedit_test.so    the product's OBJECTS plus the hook sources (HOOK_SOURCES, csrc/*test_hooks.cpp): additionally
+                              exports the dlimg_amd_test_* / dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h)
+                              the parity tests and the kernels-alone timing loops call; built by default next to the product
   lib/libdlimgedit_tuning.so  `--tuning`: everything compiled with -DDLIMG_TUNING -- additionally the ablated kernel variants
                               and in-kernel cycle stamps the scripts under tools/ use (DLIMGEDIT_*_ABLATE, GemmArgs::stamps);
                               tools select it with DLIMGEDIT_TUNING_LIB=1 (or the file name of a copy kept under lib/).
@@ -42,26 +31,13 @@ OBJ_TUNING = CSRC / "_obj_tuning"
 LIB = PKG / "lib" / "libdlimgedit.so"
 LIB_TEST = PKG / "lib" / "libdlimgedit_test.so"
 LIB_TUNING = PKG / "lib" / "libdlimgedit_tuning.so"
-LIB_NECK_TEST = PKG / "lib" / "libdlimgedit_neck_test.so"
-LIB_CLEANUP_TEST = PKG / "lib" / "libdlimgedit_cleanup_test.so"
-LIB_GRID_TEST = PKG / "lib" / "libdlimgedit_grid_test.so"
-LIB_PRIOR_TEST = PKG / "lib" / "libdlimgedit_prior_test.so"
-LIB_LASSO_TEST = PKG / "lib" / "libdlimgedit_lasso_test.so"
 ARCH = "gfx950"
 SONAME = "libdlimgedit.so.1"
 EXPORTS_MAP = CSRC / "exports.map"
 EXPORTS_TEST_MAP = CSRC / "exports_test.map"
-EXPORTS_NECK_TEST_MAP = CSRC / "exports_neck_test.map"
-EXPORTS_CLEANUP_TEST_MAP = CSRC / "exports_cleanup_test.map"
-EXPORTS_GRID_TEST_MAP = CSRC / "exports_grid_test.map"
-EXPORTS_PRIOR_TEST_MAP = CSRC / "exports_prior_test.map"
-EXPORTS_LASSO_TEST_MAP = CSRC / "exports_lasso_test.map"
-HOOK_SOURCES = ["test_hooks.cpp"]          # test and tuning libraries only
-NECK_HOOK_SOURCES = ["neck_test_hooks.cpp"]     # lib/libdlimgedit_neck_test.so only
-CLEANUP_HOOK_SOURCES = ["cleanup_test_hooks.cpp"]     # lib/libdlimgedit_cleanup_test.so only
-GRID_HOOK_SOURCES = ["grid_test_hooks.cpp"]           # lib/libdlimgedit_grid_test.so only
-PRIOR_HOOK_SOURCES = ["prior_test_hooks.cpp"]         # lib/libdlimgedit_prior_test.so only
-LASSO_HOOK_SOURCES = ["lasso_test_hooks.cpp"]         # lib/libdlimgedit_lasso_test.so only
+# test and tuning libraries only
+HOOK_SOURCES = ["test_hooks.cpp", "neck_test_hooks.cpp", "cleanup_test_hooks.cpp", "grid_test_hooks.cpp", "prior_test_hooks.cpp",
+                "lasso_test_hooks.cpp"]
 
 SOURCES = [
     "kernels/gemm.hip",
@@ -221,11 +197,8 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
     with ThreadPoolExecutor(workers) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, hdr, tuning), SOURCES))
         hooks = list(ex.map(lambda s: _compile(s, force, hdr, tuning), HOOK_SOURCES))
-        neck_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), NECK_HOOK_SOURCES))
-        cleanup_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), CLEANUP_HOOK_SOURCES))
-        grid_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), GRID_HOOK_SOURCES))
-        prior_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), PRIOR_HOOK_SOURCES))
-        lasso_hooks = [] if tuning else list(ex.map(lambda s: _compile(s, force, hdr), LASSO_HOOK_SOURCES))
+    for side in ("neck", "cleanup", "grid", "prior", "lasso"):     # an older build's library per hook file: nothing loads them now
+        (LIB.parent / f"libdlimgedit_{side}_test.so").unlink(missing_ok=True)
     if tuning:
         if _stale(LIB_TUNING, objs + hooks, force):
             _link(LIB_TUNING, objs + hooks, EXPORTS_TEST_MAP)
@@ -240,23 +213,13 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
             _link(LIB, objs, EXPORTS_MAP, SONAME)
         # the test library: the SAME objects (what the parity tests exercise is the product's code) + the hooks
         _link(LIB_TEST, objs + hooks, EXPORTS_TEST_MAP)
-    if _stale(LIB_NECK_TEST, objs + neck_hooks, force):
-        _link(LIB_NECK_TEST, objs + neck_hooks, EXPORTS_NECK_TEST_MAP)
-    if _stale(LIB_CLEANUP_TEST, objs + cleanup_hooks, force):
-        _link(LIB_CLEANUP_TEST, objs + cleanup_hooks, EXPORTS_CLEANUP_TEST_MAP)
-    if _stale(LIB_GRID_TEST, objs + grid_hooks, force):
-        _link(LIB_GRID_TEST, objs + grid_hooks, EXPORTS_GRID_TEST_MAP)
-    if _stale(LIB_PRIOR_TEST, objs + prior_hooks, force):
-        _link(LIB_PRIOR_TEST, objs + prior_hooks, EXPORTS_PRIOR_TEST_MAP)
-    if _stale(LIB_LASSO_TEST, objs + lasso_hooks, force):
-        _link(LIB_LASSO_TEST, objs + lasso_hooks, EXPORTS_LASSO_TEST_MAP)
     # consumers linked against the reference's library resolve libdlimgedit.so.1 (SOVERSION 1,
     # /root/reference/src/CMakeLists.txt:20-23)
     link = LIB.parent / SONAME
     if not link.is_symlink() and not link.exists():
         link.symlink_to(LIB.name)
     if verbose:
-        print(f"built {LIB} ({LIB.stat().st_size / 1e6:.1f} MB), {LIB_TEST.name}, {LIB_NECK_TEST.name}, {LIB_CLEANUP_TEST.name}, {LIB_GRID_TEST.name}, {LIB_PRIOR_TEST.name} and {LIB_LASSO_TEST.name}")
+        print(f"built {LIB} ({LIB.stat().st_size / 1e6:.1f} MB) and {LIB_TEST.name}")
     return LIB
 
 

@@ -1,13 +1,8 @@
-// Test hook of the mask clean-up kernels (kernels.hpp: k::mask_cleanup) alone.  It lives in a library of its own,
-// lib/libdlimgedit_cleanup_test.so (the product's objects plus this file; csrc/exports_cleanup_test.map): the set of hooks
-// lib/libdlimgedit_test.so exports is pinned by tests/test_abi.py.  No header declares it; dlimgedit_amd/api.py
-// (ext.test_mask_cleanup) binds it by name.
-//
-//   masks[i]: HOST memory, w[i] * h[i] bytes of 0 / 255 in packed rows, cleaned in place with max_hole[i] / max_island[i].
-//   All `count` masks are ONE k::mask_cleanup call on the current device's null stream.  The launcher's refusals (shapes,
-//   thresholds, a null mask) arrive as the call's error; nothing is allocated or copied for a list the launcher refuses for
-//   its shapes.
+// Test hook of the mask clean-up kernels (kernels.hpp: k::mask_cleanup) alone.  Its contract:
+// include/dlimgedit/dlimgedit_amd_test.h; the Python side is ext.test_mask_cleanup (dlimgedit_amd/api.py).
 #include "ext_common.hpp"
+
+#include <dlimgedit/dlimgedit_amd_test.h>
 
 #include <vector>
 

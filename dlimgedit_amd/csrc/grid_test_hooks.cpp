@@ -1,47 +1,15 @@
-// Test hook of the label-map kernels (kernels.hpp: k::grid_harvest, k::grid_paint) alone.  It lives in a library of its own,
-// lib/libdlimgedit_grid_test.so (the product's objects plus this file; csrc/exports_grid_test.map): the set of hooks
-// lib/libdlimgedit_test.so exports is pinned by tests/test_abi.py.  No header declares it; dlimgedit_amd/api.py
-// (ext.test_grid_kernels) binds it by name.
-//
-//   planes4 [prompts][4][256][256], iou4 [prompts][4]: HOST memory, what a decode leaves for the prompts of a grid.  The planes
-//   are harvested in chunks of 16 prompts, as the runtime harvests the chunks of its decodes; records_out [3 prompts][8] and
-//   store_out [3 prompts][256][256] (optional) receive what the harvest left.  n_kept_in >= 0: kept_in are the candidates to
-//   paint, in label order; n_kept_in < 0: they are selected on the host from the records and iou4 (csrc/grid_plan.hpp) with the
-//   two thresholds.  kept_out [255] / n_kept_out receive the painted list, map_out [out_h][out_w] the label map.  Store,
-//   records and map are device buffers with 256 guard bytes on either side; *guards_ok tells whether those are untouched.
-//   iters > 0 (tools/grid_probe.py): the harvest of all chunks and the paint launch are then repeated iters times each between
-//   two events, and ms_out[0] / ms_out[1] receive the milliseconds of ONE harvest of all candidates / ONE paint launch.
-#include "ext_common.hpp"
+// Test hook of the label-map kernels (kernels.hpp: k::grid_harvest, k::grid_paint) alone.  Its contract:
+// include/dlimgedit/dlimgedit_amd_test.h; the Python side is ext.test_grid_kernels (dlimgedit_amd/api.py).
+#include "test_support.hpp"
 #include "grid_plan.hpp"
+
+#include <dlimgedit/dlimgedit_amd_test.h>
 
 #include <cstring>
 #include <vector>
 
 using namespace dlimg;
 using namespace dlimg::extapi;
-
-namespace {
-constexpr size_t kGuard = 256;
-constexpr uint8_t kGuardByte = 0xA5;
-
-struct Guarded {
-    DeviceBuffer<uint8_t> buf;
-    size_t bytes;
-    explicit Guarded(size_t n) : bytes(n) {
-        buf.reserve(n + 2 * kGuard);
-        HIP_CHECK(hipMemset(buf.get(), kGuardByte, n + 2 * kGuard));
-    }
-    uint8_t* get() const { return buf.get() + kGuard; }
-    bool intact() const {
-        uint8_t g[2 * kGuard];
-        HIP_CHECK(hipMemcpy(g, buf.get(), kGuard, hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(g + kGuard, buf.get() + kGuard + bytes, kGuard, hipMemcpyDeviceToHost));
-        for (uint8_t v : g)
-            if (v != kGuardByte) return false;
-        return true;
-    }
-};
-}  // namespace
 
 extern "C" {
 
@@ -89,22 +57,9 @@ DLIMG_API int dlimg_amd_test_grid_kernels(float const* planes4, int prompts, flo
         paint();
         HIP_CHECK(hipDeviceSynchronize());
         if (iters > 0 && ms_out) {
-            hipEvent_t a = nullptr, b = nullptr;
-            HIP_CHECK(hipEventCreate(&a));
-            HIP_CHECK(hipEventCreate(&b));
-            auto timed = [&](auto&& launch) {
-                HIP_CHECK(hipEventRecord(a, nullptr));
-                for (int i = 0; i < iters; ++i) launch();
-                HIP_CHECK(hipEventRecord(b, nullptr));
-                HIP_CHECK(hipEventSynchronize(b));
-                float ms = 0;
-                HIP_CHECK(hipEventElapsedTime(&ms, a, b));
-                return ms / iters;
-            };
-            ms_out[0] = timed(harvest);
-            ms_out[1] = timed(paint);
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
+            EventPair events;
+            ms_out[0] = events.mean_ms(iters, harvest);
+            ms_out[1] = events.mean_ms(iters, paint);
         }
         download(map_out, static_cast<uint8_t const*>(map.get()), map.bytes);
         if (store_out) download(reinterpret_cast<uint8_t*>(store_out), static_cast<uint8_t const*>(store.get()), store.bytes);

@@ -1,13 +1,9 @@
 // Test hooks of the two encoder-neck launches (kernels.hpp: k::neck_conv1x1_ln, k::neck_conv3x3_ln), one per entry point, on
-// DEVICE buffers, as SamModel::encode calls them.  They live in a library of their own, lib/libdlimgedit_neck_test.so (the
-// product's objects plus this file; csrc/exports_neck_test.map): the set of hooks lib/libdlimgedit_test.so exports is pinned by
-// tests/test_abi.py.  No header declares them; dlimgedit_amd/api.py (ext.test_neck_conv_ln) binds them by name.
-//
-//   in: [B*4096][K] f16 (1x1) or the f16 map [B][64][64][256] (3x3, zero pad 1); w: [256][K] / [256][9*256] f16, 3x3 columns
-//   (ky*3+kx)*256 + c; gamma / beta [256] fp32.  Results, each optional: out_f16 [B*4096][256]; the fp32 result of image i
-//   [4096][256] in out_f32[i] (a HOST array of B device pointers, or NULL) where that is given, else at workspace + i*4096*256
-//   (NULL: not written).  *out_flag: the launch's non-finite report, 1 when a row's statistics were an infinity or a NaN.
+// DEVICE buffers, as SamModel::encode calls them.  Their contract: include/dlimgedit/dlimgedit_amd_test.h; the Python side is
+// ext.test_neck_conv_ln (dlimgedit_amd/api.py).
 #include "ext_common.hpp"
+
+#include <dlimgedit/dlimgedit_amd_test.h>
 
 #include <vector>
 

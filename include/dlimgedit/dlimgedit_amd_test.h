@@ -1,5 +1,5 @@
 /* dlimgedit_amd_test.h -- test and benchmark hooks of the MI355X build.  They are exported by lib/libdlimgedit_test.so
- * (the product's objects plus csrc/test_hooks.cpp) and by the tuning library, NOT by the product libdlimgedit.so, whose
+ * (the product's objects plus the hook sources, csrc/test_hooks.cpp and its neighbours) and by the tuning library, NOT by the product libdlimgedit.so, whose
  * dynamic symbols are dlimg_init and the entry points of dlimgedit_amd.h only (reference:
  * /root/reference/src/CMakeLists.txt:11).  Single kernels behind plain host buffers so that every HIP kernel can be
  * compared with the CPU oracle in isolation, host-logic checks that need no GPU, and kernels-alone timing loops.
@@ -121,6 +121,52 @@ DLIMG_API int dlimg_amd_test_encoder_state(dlimg_Environment env, dlimg_ImageVie
  * pixels [height][stride] -> out_pixels [out_h][out_w * bytes_per_pixel] packed. */
 DLIMG_API int dlimg_amd_test_resize(uint8_t const* pixels, int width, int height, int stride, int channels, int out_w,
                                     int out_h, uint8_t* out_pixels);
+
+/* ---- kernel-alone hooks of the encoder neck and the marks (one source file each beside csrc/test_hooks.cpp) ---- */
+/* The two encoder-neck launches (k::neck_conv1x1_ln, k::neck_conv3x3_ln), one per entry point, on DEVICE buffers, as
+ * SamModel::encode calls them.  in: [B*4096][K] f16 (1x1) or the f16 map [B][64][64][256] (3x3, zero pad 1); w: [256][K] /
+ * [256][9*256] f16, 3x3 columns (ky*3+kx)*256 + c; gamma / beta [256] fp32.  Results, each optional: out_f16 [B*4096][256]; the
+ * fp32 result of image i [4096][256] in out_f32[i] (a HOST array of B device pointers, or NULL) where that is given, else at
+ * workspace + i*4096*256 (NULL: not written).  *out_flag: the launch's non-finite report, 1 when a row's statistics were an
+ * infinity or a NaN. */
+DLIMG_API int dlimg_amd_test_neck_conv1x1_ln(void const* in, int B, int K, void const* w, float const* gamma, float const* beta,
+                                             float eps, void* out_f16, float* const* out_f32, float* workspace, int* out_flag);
+DLIMG_API int dlimg_amd_test_neck_conv3x3_ln(void const* in, int B, void const* w, float const* gamma, float const* beta, float eps,
+                                             void* out_f16, float* const* out_f32, float* workspace, int* out_flag);
+/* The mask clean-up kernels (k::mask_cleanup) alone.  masks[i]: HOST memory, w[i] * h[i] bytes of 0 / 255 in packed rows,
+ * cleaned in place with max_hole[i] / max_island[i].  All `count` masks are ONE k::mask_cleanup call on the current device's
+ * null stream.  The launcher's refusals (shapes, thresholds, a null mask) arrive as the call's error; nothing is allocated or
+ * copied for a list the launcher refuses for its shapes. */
+DLIMG_API int dlimg_amd_test_mask_cleanup(uint8_t* const* masks, int const* w, int const* h, int const* max_hole,
+                                          int const* max_island, int count);
+/* The label-map kernels (k::grid_harvest, k::grid_paint) alone.  planes4 [prompts][4][256][256], iou4 [prompts][4]: HOST
+ * memory, what a decode leaves for the prompts of a grid.  The planes are harvested in chunks of 16 prompts, as the runtime
+ * harvests the chunks of its decodes; records_out [3 prompts][8] and store_out [3 prompts][256][256] (optional) receive what
+ * the harvest left.  n_kept_in >= 0: kept_in are the candidates to paint, in label order; n_kept_in < 0: they are selected on
+ * the host from the records and iou4 (csrc/grid_plan.hpp) with the two thresholds.  kept_out [255] / n_kept_out receive the
+ * painted list, map_out [out_h][out_w] the label map.  Store, records and map are device buffers with 256 guard bytes on
+ * either side; *guards_ok tells whether those are untouched.  iters > 0 (tools/grid_probe.py): the harvest of all chunks and
+ * the paint launch are then repeated iters times each between two events, and ms_out[0] / ms_out[1] receive the milliseconds
+ * of ONE harvest of all candidates / ONE paint launch. */
+DLIMG_API int dlimg_amd_test_grid_kernels(float const* planes4, int prompts, float const* iou4, int out_w, int out_h, int pre_w, int pre_h,
+                                          int iou_permille, int stability_permille, int const* kept_in, int n_kept_in, int cull,
+                                          int32_t* records_out, float* store_out, uint8_t* map_out, int* kept_out, int* n_kept_out,
+                                          int* guards_ok, int iters, float* ms_out);
+/* The prior-plane kernel (k::mask_prior) alone.  mask [h][w] u8: HOST memory.  Its device copy and the plane [256][256] fp32
+ * are device buffers with 256 guard bytes on either side; *guards_ok tells whether those are untouched after the launch.  The
+ * copy is exactly w * h bytes long inside its guards: a sum that took in a byte behind the mask's last one would take in a
+ * guard byte (0xA5) and miss the reference.  iters > 0 (tools/prior_probe.py): the launch is then repeated iters times between
+ * two events, and *ms_out receives the milliseconds of ONE launch. */
+DLIMG_API int dlimg_amd_test_prior_plane(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli, float* plane_out,
+                                         int* guards_ok, int iters, float* ms_out);
+/* The lasso derivation (k::lasso_derive) alone.  mask [h][w] u8: HOST memory, of an image that was encoded at pre_w x pre_h.
+ * Upload, k::mask_prior (default strength), k::lasso_derive and the fold of csrc/lasso_plan.hpp, behind plain host buffers:
+ * record_out [8] = {inside cells, box x0, y0, x1, y1, click x, click y, d2}.  The mask's device copy, the plane, g and the row
+ * records are device buffers with 256 guard bytes on either side; *guards_ok tells whether those are untouched after the
+ * launches.  iters > 0 (tools/lasso_probe.py): the two derive launches are then repeated iters times between two events, and
+ * *ms_out receives the milliseconds of ONE derivation (both launches). */
+DLIMG_API int dlimg_amd_test_lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int32_t* record_out, int* guards_ok,
+                                          int iters, float* ms_out);
 
 /* ---- kernels alone, timed on device-resident data --------------------------------------------- */
 /* Times the two pixel kernels of the path alone on `batch` (1..16) device-resident 1024x1024 RGBA images / mask requests in

@@ -65,11 +65,23 @@ def test_only_declared_dlimg_symbols_are_exported(api):
     # dlimg_amd_test_decode_prompts (any number of points, mask input, state: tests/test_gpu_decoder_prompts.py)
     # ... and dlimg_amd_test_gemm_tile_shape (the tile table for tests/test_gpu_gemm.py, so that no test restates it)
     # ... and dlimg_amd_test_encoder_state (the encoder's buffers and loaded operands, read only: tests/test_gpu_encoder.py)
-    assert len(api.ext.HOOK_EXPORTS) == 24 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
+    # ... and the six kernel-alone hooks that had a library each before: dlimg_amd_test_neck_conv1x1_ln and
+    # dlimg_amd_test_neck_conv3x3_ln (tests/test_gpu_neck.py), dlimg_amd_test_mask_cleanup (tests/test_gpu_cleanup.py),
+    # dlimg_amd_test_grid_kernels (tests/test_gpu_grid_kernels.py), dlimg_amd_test_prior_plane (tests/test_gpu_prior_kernel.py),
+    # dlimg_amd_test_lasso_derive (tests/test_gpu_lasso_kernel.py)
+    assert len(api.ext.HOOK_EXPORTS) == 30 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
+    # every hook has its ctypes signature in the one table ext._h() applies, and the library has every name of the table
+    assert set(api.ext._HOOK_SIGS) == set(api.ext.HOOK_EXPORTS)
+    hooks_lib = api.ext._h()
+    for name in api.ext.HOOK_EXPORTS:
+        assert getattr(hooks_lib, name).argtypes is not None, name
+    # one test library: no library per hook file and no export map of one is left
+    assert not list(lib_dir.glob("libdlimgedit_*_test.so")), list(lib_dir.glob("libdlimgedit_*_test.so"))
+    assert sorted(p.name for p in (ROOT / "dlimgedit_amd" / "csrc").glob("exports*.map")) == ["exports.map", "exports_test.map"]
 
 
 def test_hooks_come_from_the_test_library_not_the_product(api):
-    """A hook call loads lib/libdlimgedit_test.so (the product's objects + csrc/test_hooks.cpp); the product library has no
+    """A hook call loads lib/libdlimgedit_test.so (the product's objects + the hook sources csrc/*test_hooks.cpp); the product library has no
     such symbol to fall back on, and a hook's error text comes from the library it ran in."""
     assert api.hooks_library() is not api.library()
     assert not hasattr(api.library(), "dlimg_amd_test_plan_steps")

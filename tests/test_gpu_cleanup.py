@@ -1,5 +1,5 @@
-"""The mask clean-up kernels alone (csrc/kernels/mask_cleanup.hip) through their hook, ext.test_mask_cleanup, against the numpy
-reference (tests/cleanup_ref.py) on the named cases of tests/cleanup_cases.py.  The result is an integer problem: every
+"""The mask clean-up kernels alone (csrc/kernels/mask_cleanup.hip) through their hook, ext.test_mask_cleanup (lib/libdlimgedit_test.so),
+against the numpy reference (tests/cleanup_ref.py) on the named cases of tests/cleanup_cases.py.  The result is an integer problem: every
 comparison is np.array_equal.  That the cases are not vacuous (the reference changes pixels) is asserted on the CPU
 (tests/test_cleanup_oracle.py).
 """

@@ -2,7 +2,7 @@
 fc1, row statistics handed from writer to consumer, the loader's fold -- stage by stage against tests/encoder_ref.py's float64
 reference, every stage from the device's own operands of that stage (teacher forcing).
 
-encode() is not touched: dlimg_amd_test_encoder_state (csrc/neck_test_hooks.cpp) only READS what a pass left.  The per-block values come from models
+encode() is not touched: dlimg_amd_test_encoder_state (csrc/test_hooks.cpp) only READS what a pass left.  The per-block values come from models
 of their own (tests/encoder_cases.py): weights are drawn by name, so the depth-k model IS the first k blocks of the deeper one and
 its final stream / stats / qkv / hidden are block k-1's; the depth-k model with the last fc2 zeroed ends with the value behind
 the attention half (x_mid); the depth-1 model with proj zeroed too ends with stream 0.

@@ -1,5 +1,5 @@
-"""The label-map kernels alone (csrc/kernels/mask_grid.hip) through their hook, ext.test_grid_kernels, on synthetic planes
-against the numpy reference (tests/grid_ref.py): the harvest's records exactly, the store and the painted map bit for bit.
+"""The label-map kernels alone (csrc/kernels/mask_grid.hip) through their hook, ext.test_grid_kernels (lib/libdlimgedit_test.so), on
+synthetic planes against the numpy reference (tests/grid_ref.py): the harvest's records exactly, the store and the painted map bit for bit.
 Both are integer / bit-exact contracts: every comparison is np.array_equal.  Guard bytes around the store, the records and
 the map must be untouched in every call.
 """

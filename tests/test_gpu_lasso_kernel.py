@@ -1,9 +1,9 @@
-"""k::lasso_derive alone on the GPU (kernels/mask_lasso.hip, through the hook of lib/libdlimgedit_lasso_test.so): upload,
+"""k::lasso_derive alone on the GPU (kernels/mask_lasso.hip, through its hook in lib/libdlimgedit_test.so): upload,
 k::mask_prior, the two derive launches and the host's fold behind plain host buffers.  The record -- inside cells, box, click,
 squared distance -- must EQUAL tests/lasso_ref.py: the definition is integer arithmetic.  Extents: the identity, up-scaling
 (footprints share source columns; sh = 171 with a 3-row last footprint), down-scaling, sw = 10, and an image smaller than one
 wave's row.  Selections: what tests/lasso_cases.py lists.  The guard bytes around the mask's device copy, the plane, the column
-distances and the row records stay intact in every call.  On the parent commit the hook library does not exist."""
+distances and the row records stay intact in every call."""
 import numpy as np
 import pytest
 

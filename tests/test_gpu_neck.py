@@ -1,5 +1,6 @@
 """The two launches of the encoder neck (kernels.hpp: neck_conv1x1_ln, neck_conv3x3_ln -- convolution + LayerNorm2d in one
-kernel, the 3x3 operand read straight from the map) through their hooks, on the smallest shapes at which they can go wrong.
+kernel, the 3x3 operand read straight from the map) through their hooks in lib/libdlimgedit_test.so, on the smallest shapes at
+which they can go wrong.
 
 Accuracy is measured against tests/neck_ref.py's float64 reference in units of its rounding model, and the allowance is 1.25
 times what the FIVE launches they replace need on the same inputs (GEMM and LayerNorm through their own hooks, the im2col copy

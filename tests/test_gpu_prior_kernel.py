@@ -1,4 +1,4 @@
-"""k::mask_prior alone on the GPU (kernels/mask_prior.hip, through the hook of lib/libdlimgedit_prior_test.so): a caller's u8 mask
+"""k::mask_prior alone on the GPU (kernels/mask_prior.hip, through its hook in lib/libdlimgedit_test.so): a caller's u8 mask
 as the 256 x 256 fp32 plane of the prompt encoder's mask branch.  The plane must equal tests/prior_ref.py BIT FOR BIT -- the
 definition is integer arithmetic up to one correctly rounded fp32 division and one multiply -- at every extent the kernel takes
 another path for: the identity (1024 x 1024), up- and down-scaling, extents that are no multiple of anything, a tiny image whose

@@ -10,8 +10,8 @@ run (nothing more is started on the GPU after it):
            written once) over time, as a share of 8 TB/s
   paint    k::grid_paint alone, 1024 x 1024, 100 kept segments, with and without the box cull
 
-Kernel times are means between two events on the null stream (the hook of lib/libdlimgedit_grid_test.so); call times are wall
-clock of the calling thread, median of the repetitions after a warm-up.
+Kernel times are means between two events on the null stream (dlimg_amd_test_grid_kernels of lib/libdlimgedit_test.so); call times are
+wall clock of the calling thread, median of the repetitions after a warm-up.
 """
 import argparse
 import statistics

@@ -5,8 +5,8 @@ weights with the mask branch.
 
 Steps, each a fresh child process under its own time limit; the first one that fails, is killed or runs out of time ends the
 run (nothing more is started on the GPU after it):
-  kernel   k::lasso_derive alone (both launches, behind a plane k::mask_prior wrote; the hook of
-           lib/libdlimgedit_lasso_test.so) at 1024 x 1024, 1800 x 1200 and 4000 x 3000: microseconds per derivation, for an
+  kernel   k::lasso_derive alone (both launches, behind a plane k::mask_prior wrote; dlimg_amd_test_lasso_derive of
+           lib/libdlimgedit_test.so) at 1024 x 1024, 1800 x 1200 and 4000 x 3000: microseconds per derivation, for an
            ellipse and for a full selection (the longest column scans and the largest distances)
   query    a lasso-only call (what = 0: box, click and mask input) against the SAME prompt sent explicitly -- the reference's
            box and click (tests/lasso_ref.py) and a prior mark on the same buffer -- on one image of each extent: wall clock of

@@ -4,8 +4,8 @@
 
 Steps, each a fresh child process under its own time limit; the first one that fails, is killed or runs out of time ends the
 run (nothing more is started on the GPU after it):
-  kernel   k::mask_prior alone at 1024 x 1024 and 4000 x 3000 (the hook of lib/libdlimgedit_prior_test.so): microseconds per
-           launch and bytes moved (the mask read once, the plane written once) over time, as a share of 8 TB/s
+  kernel   k::mask_prior alone at 1024 x 1024 and 4000 x 3000 (dlimg_amd_test_prior_plane of lib/libdlimgedit_test.so):
+           microseconds per launch and bytes moved (the mask read once, the plane written once) over time, as a share of 8 TB/s
   query    a one-click query with a prior against the same query without one, on one 1024 x 1024 and one 4000 x 3000 image:
            wall clock of the calling thread (median and minimum of the repetitions after a warm-up) and, with the stage clocks
            on, the milliseconds and launches of the decoder stage and of stage 7 (post: this kernel and the post-processing)
