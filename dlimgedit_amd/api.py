@@ -25,6 +25,8 @@ LIB_PATH = Path(__file__).resolve().parent / "lib" / "libdlimgedit.so"
 # ext.mask_pieces, ext.plan_steps) are not in the product library: they come from lib/libdlimgedit_test.so, the product's own
 # objects plus the hook sources csrc/*test_hooks.cpp, loaded next to the product the first time a hook is called.
 HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_test.so")
+# ext.test_matte alone comes from a library of its own (build.py: LIB_MATTE_HOOKS; the tuning library has it as well)
+MATTE_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_matte_hooks.so")
 # tools/ only: the -DDLIMG_TUNING build with ablated kernel variants and in-kernel stamps (python -m dlimgedit_amd.build --tuning);
 # it exports the hooks too, so one library serves both roles
 if os.environ.get("DLIMGEDIT_TUNING_LIB") == "1":
@@ -153,6 +155,29 @@ def hooks_library() -> C.CDLL:
             _hooks_lib.dlimg_init.restype = C.POINTER(_Api)
             _hooks_lib.dlimg_init.argtypes = []
     return _hooks_lib
+
+
+_matte_hooks_lib = None
+
+
+def matte_hooks_library() -> C.CDLL:
+    """Loads the library that exports dlimg_amd_test_matte (libdlimgedit_matte_hooks.so; the tuning library when one is
+    selected).  Raises if it has not been built."""
+    global _matte_hooks_lib
+    if _matte_hooks_lib is None:
+        if HOOKS_LIB_PATH == LIB_PATH:
+            _matte_hooks_lib = library()
+        else:
+            if not MATTE_HOOKS_LIB_PATH.exists():
+                raise Error(f"{MATTE_HOOKS_LIB_PATH} not found: build it with `python -m dlimgedit_amd.build`")
+            _matte_hooks_lib = C.CDLL(str(MATTE_HOOKS_LIB_PATH))
+            _matte_hooks_lib.dlimg_init.restype = C.POINTER(_Api)
+            _matte_hooks_lib.dlimg_init.argtypes = []
+        _ip, _vpp = C.POINTER(C.c_int), C.POINTER(C.c_void_p)
+        _matte_hooks_lib.dlimg_amd_test_matte.argtypes = [_vpp, _vpp, _ip, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int,
+                                                          C.POINTER(C.c_float)]
+        _matte_hooks_lib.dlimg_amd_test_matte.restype = C.c_int
+    return _matte_hooks_lib
 
 
 def _check_hook(result: int) -> None:
@@ -313,6 +338,10 @@ PRIOR_MARK = 8               # regions[4 i] of a prior mark (dlimgedit.h: DLIMG_
 PRIOR_MAX_STRENGTH = 100000  # strength_milli of a prior mark, at most; 0: the library's default (8000)
 LASSO_MARK = 10              # regions[4 i] of a lasso mark (dlimgedit.h: DLIMG_LASSO_MARK; csrc/lasso_plan.hpp: kLassoMark)
 LASSO_BOX, LASSO_CLICK, LASSO_MASK = 1, 2, 4     # the bits of a lasso mark's `what`; 0: all three
+MATTE_MARK = 11              # regions[4 i] of a matte mark (dlimgedit.h: DLIMG_MATTE_MARK; csrc/matte_plan.hpp: kMatteMark)
+MATTE_MAX_RADIUS = 32
+MATTE_MAX_EPS = 65025        # eps of a matte mark, at most, in squared grey levels; 0: the library's default
+MATTE_DEFAULT_EPS = 650
 
 
 @dataclass
@@ -340,7 +369,10 @@ class ClickEntries:
     A lasso mark is a continuation entry (LASSO_MARK, strength_milli, what, 0) directly behind its head, whose out_masks pointer is
     READ likewise: lassos[j] is the (h, w) uint8 selection of prompt j, None without one.  Its box and / or first click are
     derived on the GPU: token_rows and stage_clicks count the derived click (it belongs to the first stage) and the derived
-    box.  Such a prompt is decoded behind the others like a prompt with marks."""
+    box.  Such a prompt is decoded behind the others like a prompt with marks.
+    A matte mark is a continuation entry (MATTE_MARK, radius, eps, channels), the last entry of its prompt (behind the clean-up
+    mark), whose out_masks pointer is READ as well: mattes[j] is the (h, w[, c]) uint8 image that guides the soft edge of prompt
+    j's mask, None without one.  It changes neither token_rows nor stage_clicks; such a prompt is decoded on its own."""
     heads: list
     points: list
     regions: list
@@ -350,10 +382,11 @@ class ClickEntries:
     grid_sides: list = field(default_factory=list)
     priors: list = field(default_factory=list)
     lassos: list = field(default_factory=list)
+    mattes: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
         return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None) \
-            or (j < len(self.lassos) and self.lassos[j] is not None)
+            or (j < len(self.lassos) and self.lassos[j] is not None) or (j < len(self.mattes) and self.mattes[j] is not None)
 
     def _grid(self, j) -> bool:
         return j < len(self.grid_sides) and self.grid_sides[j] > 0
@@ -524,9 +557,38 @@ def _checked_lasso(lasso, lasso_what, lasso_strength, n: int) -> list:
     return out
 
 
-def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos: Optional[list] = None) -> list:
+def _checked_matte(matte, n: int) -> list:
+    """`matte` of a call of n prompts -> per prompt None or (image, channels, radius, eps): matte is None or one entry per prompt,
+    None or (image, radius, eps) with image an (h, w), (h, w, 3) or (h, w, 4) C-contiguous uint8 array, radius 1 .. 32 and eps
+    0 (the library's default) .. 65025."""
+    if matte is None:
+        return [None] * n
+    matte = list(matte)
+    if len(matte) != n:
+        raise Error("matte: None, or one entry (None or (image, radius, eps)) per prompt")
+    out = []
+    for m in matte:
+        if m is None:
+            out.append(None)
+            continue
+        if not isinstance(m, (tuple, list)) or len(m) != 3:
+            raise Error("matte: a matte is (image, radius, eps)")
+        g, radius, eps = m
+        if not isinstance(g, np.ndarray) or g.dtype != np.uint8 or not g.flags.c_contiguous or \
+                not (g.ndim == 2 or (g.ndim == 3 and g.shape[2] in (1, 3, 4))):
+            raise Error("matte: the guide is a C-contiguous (h, w), (h, w, 3) or (h, w, 4) uint8 array of the image's extent")
+        if not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= MATTE_MAX_RADIUS:
+            raise Error(f"matte: radius is 1 .. {MATTE_MAX_RADIUS}")
+        if not isinstance(eps, (int, np.integer)) or not 0 <= int(eps) <= MATTE_MAX_EPS:
+            raise Error(f"matte: eps is 0 (the default) .. {MATTE_MAX_EPS}")
+        out.append((g, 1 if g.ndim == 2 else g.shape[2], int(radius), int(eps)))
+    return out
+
+
+def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos: Optional[list] = None,
+                    mattes: Optional[list] = None) -> list:
     """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), the selection of
-    a lasso mark (lassos likewise), None otherwise."""
+    a lasso mark (lassos likewise), the guide of a matte mark (mattes likewise), None otherwise."""
     ptrs, head = [], None
     for e, h in enumerate(heads):
         if h is not None:
@@ -542,13 +604,18 @@ def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos:
             if m.shape != (ext.height, ext.width):
                 raise Error(f"lasso: the selection of prompt {head} is {m.shape[1]} x {m.shape[0]}, its image {ext.width} x {ext.height}")
             ptrs.append(m.ctypes.data)
+        elif regs[e][0] == MATTE_MARK and head is not None and mattes is not None and mattes[head] is not None:
+            g, ext = mattes[head][0], segs[head].extent()
+            if g.shape[:2] != (ext.height, ext.width):
+                raise Error(f"matte: the guide of prompt {head} is {g.shape[1]} x {g.shape[0]}, its image {ext.width} x {ext.height}")
+            ptrs.append(g.ctypes.data)
         else:
             ptrs.append(None)
     return ptrs
 
 
 def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None,
-                    lasso: Optional[list] = None):
+                    lasso: Optional[list] = None, matte: Optional[list] = None):
     """The `points` / `regions` form of a batch call with clean-up, grid or prior marks as entry lists: entry i of the caller's,
     then its marks (the prior mark first: it stands directly behind its head).  -> (index into segs or None per entry, [(x, y)]
     or None, [(4 ints)]).  A point prompt gets the empty region (no box); a grid prompt is its head with the empty region and
@@ -565,6 +632,8 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
                 raise Error("a grid prompt takes no prior")
             if lasso is not None and lasso[i] is not None:
                 raise Error("a grid prompt takes no lasso")
+            if matte is not None and matte[i] is not None:
+                raise Error("a grid prompt takes no matte: a label map is not a coverage")
             regs.append(EMPTY_REGION)
             heads.append(None)
             if pts is not None:
@@ -588,6 +657,11 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
             if pts is not None:
                 pts.append((0, 0))
             regs.append((CLEAN_MARK, clean[i][0], clean[i][1], 0))
+        if matte is not None and matte[i] is not None:        # behind everything else of its prompt
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((MATTE_MARK, matte[i][2], matte[i][3], matte[i][1]))
     return heads, pts, regs
 
 
@@ -600,7 +674,7 @@ def _marked_arrays(segs, heads, pts, regs):
 
 
 def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
-                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0) -> ClickEntries:
+                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -616,6 +690,9 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     all or one per prompt.  clicks[j] are then the clicks BEHIND the derived one (the entry lists always carry `points`, so
     there is at least one; a lasso alone is Segmentation.snap_selection), and refine_after counts the clicks given.  Entry
     lists without lasso marks are what they were.
+    matte: None, or per prompt None / (image, radius, eps) -- a matte mark, the last entry of its prompt: the mask is delivered
+    as coverage 0 .. 255, its edge guided by the image (see compute_mask_clicks).  Entry lists without matte marks are what
+    they were.
     Pure host code."""
     n = len(clicks)
     clean = _checked_clean(clean, n)
@@ -624,6 +701,8 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     any_prior = any(p is not None for p in prior)
     lasso = _checked_lasso(lasso, lasso_what, lasso_strength, n)
     any_lasso = any(q is not None for q in lasso)
+    matte = _checked_matte(matte, n)
+    any_matte = any(q is not None for q in matte)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -636,8 +715,12 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.priors.append(None if prior[j] is None else prior[j][0])
         if any_lasso:
             out.lassos.append(None if lasso[j] is None else lasso[j][0])
+        if any_matte:
+            out.mattes.append(None if matte[j] is None else matte[j][0])
         if grid[j] is not None and lasso[j] is not None:
             raise Error("a grid prompt takes no lasso")
+        if grid[j] is not None and matte[j] is not None:
+            raise Error("a grid prompt takes no matte: a label map is not a coverage")
         if grid[j] is not None:
             if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None \
                     or prior[j] is not None:
@@ -684,6 +767,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.heads.append(None)
             out.points.append((0, 0))
             out.regions.append((CLEAN_MARK, clean[j][0], clean[j][1], 0))
+        if matte[j] is not None:             # behind everything else of its prompt
+            out.heads.append(None)
+            out.points.append((0, 0))
+            out.regions.append((MATTE_MARK, matte[j][2], matte[j][3], matte[j][1]))
     return out
 
 
@@ -777,7 +864,8 @@ class Segmentation:
     def compute_mask_clicks(self, clicks: Sequence[Point], labels: Optional[Sequence[int]] = None,
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
                             clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0,
-                            lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0) -> np.ndarray:
+                            lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0,
+                            matte=None) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
@@ -791,39 +879,46 @@ class Segmentation:
         with the mask branch.
         lasso: an (h, w) uint8 selection from which the prompt's box (LASSO_BOX), its first click (LASSO_CLICK: the most interior
         point, in front of `clicks`) and its first mask input (LASSO_MASK, at lasso_strength) are derived on the GPU;
-        lasso_what 0: all three.  See snap_selection."""
+        lasso_what 0: all three.  See snap_selection.
+        matte: (image, radius, eps) -- the mask is delivered as COVERAGE 0 .. 255 instead of 0 / 255: the mask this prompt would
+        deliver without it (cleaned, with `clean`) put through He et al.'s guided filter on the GPU, in integers, so that its
+        edge follows the picture (dlimgedit.h, DLIMG_MATTE_MARK).  image: the image this segmentation was made from, an
+        (h, w), (h, w, 3) or (h, w, 4) uint8 array (RGBA and BGRA give the same matte); radius 1 .. 32 pixels; eps 1 .. 65025
+        squared grey levels, 0: the library's default, 650."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
                                                out=None if out is None else [out],
                                                refine_after=None if refine_after is None else [refine_after],
                                                clean=None if clean is None else [tuple(clean)],
                                                prior=None if prior is None else [prior], prior_strength=prior_strength,
                                                lasso=None if lasso is None else [lasso], lasso_what=lasso_what,
-                                               lasso_strength=lasso_strength)[0]
+                                               lasso_strength=lasso_strength, matte=None if matte is None else [tuple(matte)])[0]
 
     def snap_selection(self, mask: np.ndarray, what: int = 0, strength: int = 0, clicks: Optional[Sequence[Point]] = None,
                        labels: Optional[Sequence[int]] = None, refine_after=None, clean=None,
-                       out: Optional[np.ndarray] = None) -> np.ndarray:
+                       out: Optional[np.ndarray] = None, matte=None) -> np.ndarray:
         """Snap a selection to the object: mask, an (h, w) uint8 selection of this image (a dragged lasso, a painted blob; 0 ..
         255 read as coverage), is the prompt -- its box (LASSO_BOX), its most interior point as a foreground click
         (LASSO_CLICK) and the selection itself as SAM's mask input (LASSO_MASK, at `strength` thousandths, 0: the default
         8000; needs a model with the mask branch), whichever bits `what` holds, 0: all three.  Box and click are derived on
         the GPU from the 256 x 256 low-res grid (dlimgedit.h, DLIMG_LASSO_MARK).  clicks / labels: further clicks behind the
         derived one (the first of them foreground); refine_after counts these; clean as for compute_mask_clicks.  `out` may be
-        `mask` itself: a selection snapped in place.  An empty selection (no low-res cell above half coverage) raises Error."""
+        `mask` itself: a selection snapped in place.  An empty selection (no low-res cell above half coverage) raises Error.
+        matte: (image, radius, eps) as for compute_mask_clicks -- the snapped selection comes back soft-edged."""
         if clicks:
             return self.compute_mask_clicks(clicks, labels, None, out, refine_after, clean, lasso=mask, lasso_what=what,
-                                            lasso_strength=strength)
+                                            lasso_strength=strength, matte=matte)
         if labels or refine_after is not None:
             raise Error("snap_selection: labels and refine_after go with `clicks`")
         return Segmentation.compute_mask_batch([self], out=None if out is None else [out], clean=None if clean is None else [tuple(clean)],
-                                               lasso=[mask], lasso_what=what, lasso_strength=strength)[0]
+                                               lasso=[mask], lasso_what=what, lasso_strength=strength,
+                                               matte=None if matte is None else [tuple(matte)])[0]
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
                            clean=None, grid=None, prior=None, prior_strength=0, lasso=None, lasso_what=0,
-                           lasso_strength=0) -> list:
+                           lasso_strength=0, matte=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -841,7 +936,9 @@ class Segmentation:
         lasso (either form): None, or per prompt None / an (h, w) uint8 selection -- lasso marks, see snap_selection; lasso_what
         and lasso_strength one int for all or one per prompt.  In a call with `points` or `clicks` those follow the derived
         click; a call without `points` may hold lasso-only prompts (regions[i] None) beside box-only ones, and with lasso
-        prompts alone neither `points` nor `regions` is needed."""
+        prompts alone neither `points` nor `regions` is needed.
+        matte (either form): None, or per prompt None / (image, radius, eps) -- matte marks, see compute_mask_clicks: the mask
+        of such a prompt comes back as coverage 0 .. 255."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -852,11 +949,11 @@ class Segmentation:
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
             entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength, lasso, lasso_what,
-                                    lasso_strength)
+                                    lasso_strength, matte)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             priors = _checked_prior(prior, prior_strength, len(segs))
             lassos = _checked_lasso(lasso, lasso_what, lasso_strength, len(segs))
-            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos)
+            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos, _checked_matte(matte, len(segs)))
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
                 ptrs = (C.c_void_p * n)(*[all_ptrs[i] for i in sel])
@@ -869,14 +966,15 @@ class Segmentation:
         grids = _checked_grid(grid, n)
         priors = _checked_prior(prior, prior_strength, n)
         lassos = _checked_lasso(lasso, lasso_what, lasso_strength, n)
+        mattes = _checked_matte(matte, n)
         if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors) \
-                or any(q is not None for q in lassos):
+                or any(q is not None for q in lassos) or any(q is not None for q in mattes):
             if points is None and regions is None and any(g is None and q is None for g, q in zip(grids, lassos)):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos, mattes)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors,
-                                                     lassos))
+                                                     lassos, mattes))
             _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
             return outs
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
@@ -1490,6 +1588,39 @@ class ext:
                                                          record.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ok), int(time_iters),
                                                          C.byref(ms)))
         return (record, bool(ok.value)) if time_iters <= 0 else (record, bool(ok.value), float(ms.value))
+
+    @classmethod
+    def test_matte(cls, mask, guide, radius, eps, shortcut: bool = True, time_iters: int = 0):
+        """The matte kernels alone (dlimg_amd_test_matte, lib/libdlimgedit_matte_hooks.so): mask (h, w) uint8 and guide (h, w),
+        (h, w, 3) or (h, w, 4) uint8 through ONE k::mask_matte call on the default device, with guard bytes around the mask,
+        the guide and the workspace.  -> (matte uint8 [h, w], guard bytes intact).  Lists of equal length for all four
+        arguments: that many jobs in the one call, -> (list of mattes, guards intact, launches).  guide None reaches the
+        launcher as a null guide.  shortcut False: no block is skipped for being uniform (same bytes).  time_iters > 0: a
+        further element, the milliseconds of one call (the mean of time_iters repetitions between two events, each on the
+        mask as given).  A refusal of the launcher raises Error."""
+        many = isinstance(mask, (list, tuple))
+        masks = [np.array(m, np.uint8, order="C") for m in (mask if many else [mask])]      # copies: the hook writes them
+        guides = [None if g is None else np.ascontiguousarray(g, np.uint8) for g in (guide if many else [guide])]
+        radii = [int(r) for r in (radius if many else [radius])]
+        epss = [int(e) for e in (eps if many else [eps])]
+        n = len(masks)
+        assert n == len(guides) == len(radii) == len(epss) and all(m.ndim == 2 for m in masks)
+        channels = []
+        for m, g in zip(masks, guides):
+            assert g is None or (g.shape[:2] == m.shape and (g.ndim == 2 or g.ndim == 3))
+            channels.append(1 if g is None or g.ndim == 2 else g.shape[2])
+        ints = lambda v: (C.c_int * n)(*v)
+        mp = (C.c_void_p * n)(*[m.ctypes.data for m in masks])
+        gp = (C.c_void_p * n)(*[None if g is None else g.ctypes.data for g in guides])
+        ok, launches, ms = C.c_int(0), C.c_int(0), C.c_float(0.0)
+        lib = matte_hooks_library()
+        if lib.dlimg_amd_test_matte(mp, gp, ints([m.shape[1] for m in masks]), ints([m.shape[0] for m in masks]), ints(channels),
+                                    ints(radii), ints(epss), n, int(bool(shortcut)), C.byref(ok), C.byref(launches), int(time_iters),
+                                    C.byref(ms)) != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        out = (masks, bool(ok.value), int(launches.value)) if many else (masks[0], bool(ok.value))
+        return out if time_iters <= 0 else out + (float(ms.value),)
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

@@ -403,5 +403,27 @@ void mask_prior(const uint8_t* mask, int W, int H, int pre_w, int pre_h, int str
 constexpr int kLassoRowInts = 8;
 void lasso_derive(const float* plane, int pre_w, int pre_h, int* g_scratch, int* rows, hipStream_t);
 
+// ---- matte marks (K21, kernels/mask_matte.hip) ------------------------------------------------
+// An image-guided soft edge for a delivered mask: the guided filter of He et al. with a grey guide, in integers, in place.
+// mask p [H][W] u8 (any 0 .. 255 is taken as is), guide [H][W][c] u8 tightly packed, c = 1, 3 or 4:  G = the byte for c == 1,
+// else (c0 + 2 c1 + c2 + 2) >> 2 (a fourth channel is ignored).  F = 16, E = eps; win(x, y) is the (2 r + 1)^2 square around
+// the pixel clipped to the image, N its pixel count; fdiv is floor division.
+//   pass 1, sums over win(x, y):  S_G, S_p, S_GG = sum G^2, S_Gp = sum G p
+//     cov = N S_Gp - S_G S_p        den = N S_GG - S_G^2 + E N^2                          (int64, den > 0)
+//     A   = fdiv(2 cov 2^F + den, 2 den)             B = fdiv(2 (S_p 2^F - A S_G) + N, 2 N)       (both int32)
+//   pass 2, sums over the same window:  S_A, S_B (int64)
+//     out = clamp(fdiv(2 (S_A G(x, y) + S_B) + N 2^F, 2 N 2^F), 0, 255)
+// Where p is one value over the radius-2r square around a pixel, out == p there; with a constant guide the matte is the twice
+// box-filtered mask.  radius 1 .. 32, eps 1 .. 65025 (squared grey levels).  Jobs of one call may differ in size.  Refused
+// before anything is launched: a null pointer, an extent that is not positive, whose w * h does not fit an int or which is so
+// thin that one mask needs 2^24 workgroups or more (1 x 2^31 - 1), parameters outside these ranges.  Stream-ordered, no host synchronisation, no global atomics: three launches per 16 jobs.  workspace:
+// mask_matte_workspace_bytes(jobs, count) bytes of device memory (8 per pixel, 4 per 64 x 64 cell), contents irrelevant before
+// and after.  shortcut = false: the blocks whose mask is one value over their halo are computed like any other (measurements
+// and tests; same bytes).
+struct MatteJob { uint8_t* mask; const uint8_t* guide; int w, h, channels, radius, eps; };   // mask: device, packed rows, in place
+size_t mask_matte_workspace_bytes(const MatteJob* jobs, int count);
+int mask_matte_launches(const MatteJob* jobs, int count);            // kernel launches mask_matte makes for these jobs
+void mask_matte(const MatteJob* jobs_host, int count, void* workspace, hipStream_t, bool shortcut = true);
+
 }  // namespace k
 }  // namespace dlimg

@@ -49,14 +49,16 @@ struct LassoPlannedPrompts {
 
 inline bool is_lasso_mark_entry(int const* regions, int i) { return regions && regions[4 * i] == kLassoMark; }
 
-// has_pointer, device_form: as for plan_prior_prompts.
+// has_pointer, device_form: as for plan_prior_prompts.  had_continuation: as for plan_prompts -- the caller's list held continuation
+// entries that are not in this one (matte marks, matte_plan.hpp).
 inline LassoPlannedPrompts plan_lasso_prompts(std::vector<char> const& has_handle, bool points_given, int const* regions, bool mask_branch,
-                                              std::vector<char> const& has_pointer, bool device_form = false) {
+                                              std::vector<char> const& has_pointer, bool device_form = false,
+                                              bool had_continuation = false) {
     const int count = (int)has_handle.size();
     LassoPlannedPrompts out;
     for (int i = 0; i < count; ++i) out.any_lasso |= !has_handle[i] && is_lasso_mark_entry(regions, i);
     if (!out.any_lasso) {
-        out.inner = plan_prior_prompts(has_handle, points_given, regions, mask_branch, has_pointer, device_form);
+        out.inner = plan_prior_prompts(has_handle, points_given, regions, mask_branch, has_pointer, device_form, had_continuation);
         out.lasso.resize(out.inner.planned.cleaned.staged.prompts.size());
         return out;
     }

@@ -1,5 +1,6 @@
 #include "mask_transport_exec.hpp"
 #include "image_memory.hpp"
+#include "roctx.hpp"
 
 #include <chrono>
 #include <cstdlib>
@@ -11,6 +12,8 @@ namespace {
 
 constexpr double kLogitBytes = 256.0 * 256.0 * 4.0;     // what the kernel reads per mask: the low-resolution logits
 constexpr double kCleanBytesPerPixelAndPass = 2 * 1 + 2 * 4 + 4 + 4 * 4 + 1;     // k::mask_cleanup, see MaskTransport::run
+// k::mask_matte, no block uniform: the mask read twice (cells, pass 1) and written, A and B written and read
+constexpr double kMatteBytesPerPixel = 2 * 1 + 1 + 2 * 2 * 4;
 
 // Direct xGMI copies between two GPUs need peer access switched on once per direction (without it the runtime stages
 // the copy through host memory: still correct, slower).  Failures are not errors: the copy falls back by itself.
@@ -39,6 +42,12 @@ void enable_peer_access(int from_device, int to_device) {
 bool any_cleanup(CleanSpec const* clean, int count) {
     for (int i = 0; clean && i < count; ++i)
         if (clean[i].any()) return true;
+    return false;
+}
+
+bool any_matte(MatteRequest const* matte, int count) {
+    for (int i = 0; matte && i < count; ++i)
+        if (matte[i].any()) return true;
     return false;
 }
 
@@ -90,9 +99,9 @@ hipEvent_t MaskTransport::piece_event(MaskSlot& slot, int i) {
 
 // The plan of the slot, step by step, on the lane's stream; slot.done behind the last of them.
 void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
-                        GridPaint const* paint) {
+                        GridPaint const* paint, MatteRequest const* matte) {
     MaskTransportPlan const& p = slot.plan;
-    DLIMG_ASSERT(!paint || (count == 1 && !clean));
+    DLIMG_ASSERT(!paint || (count == 1 && !clean && !matte));
     // the slot is ours, and its previous user waited for the slot's event before letting go of it
     slot.dev.reserve(p.reserve_device);
     slot.pin.reserve(p.reserve_pinned);
@@ -124,25 +133,8 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
             }
             for (int i = s.first; i < s.first + s.count; ++i) bytes += kLogitBytes + (double)slot.input.sizes[i];
             clock_.timed(ST_POST, bytes, [&] { k::postprocess_masks(&slot.kernel_jobs[s.first], s.count, stream_); });
-            if (!clean) continue;
-            // the masks of this launch that are cleaned, in place where the launch wrote them: device memory in every mode a
-            // request with clean-up marks is planned in (never the direct mode, whose kernel writes pinned host memory)
-            slot.clean_jobs.clear();
-            double clean_bytes = 0;
-            for (int i = s.first; i < s.first + s.count; ++i) {
-                if (!clean[i].any()) continue;
-                DLIMG_ASSERT(p.mode != MaskMode::direct);
-                k::PostJob const& j = slot.kernel_jobs[i];
-                slot.clean_jobs.push_back(k::CleanJob{j.dst, j.out_w, j.out_h, clean[i].max_hole, clean[i].max_island});
-                // per polarity pass and pixel: the mask read (K1, K4), labels and areas written (K1) and read (K3: areas,
-                // K4: both twice), at most one byte written
-                clean_bytes += kCleanBytesPerPixelAndPass * (double)slot.input.sizes[i] * ((clean[i].max_hole > 0) + (clean[i].max_island > 0));
-            }
-            if (slot.clean_jobs.empty()) continue;
-            const int n_clean = (int)slot.clean_jobs.size();
-            slot.clean_workspace.reserve(k::mask_cleanup_workspace_bytes(slot.clean_jobs.data(), n_clean));
-            clock_.timed(ST_POST, clean_bytes, [&] { k::mask_cleanup(slot.clean_jobs.data(), n_clean, slot.clean_workspace.get(), stream_); },
-                         clock_.profiling() ? k::mask_cleanup_launches(slot.clean_jobs.data(), n_clean) : 1);
+            if (clean) run_cleanup(slot, s, clean);
+            if (matte) run_matte(slot, s, matte);
         } else if (s.kind == MaskStep::event) {
             HIP_CHECK(hipEventRecord(piece_event(slot, s.first), stream_));
         } else if (s.to == MaskMem::peer) {
@@ -155,8 +147,51 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
     HIP_CHECK(hipEventRecord(slot.done, stream_));
 }
 
+// The clean-up of the masks of launch step `s`, behind its post-processing launch: in place where the launch wrote them, device
+// memory in every mode a request with clean-up marks is planned in (never the direct mode, whose kernel writes pinned host
+// memory).
+void MaskTransport::run_cleanup(MaskSlot& slot, MaskStep const& s, CleanSpec const* clean) {
+    slot.clean_jobs.clear();
+    double clean_bytes = 0;
+    for (int i = s.first; i < s.first + s.count; ++i) {
+        if (!clean[i].any()) continue;
+        DLIMG_ASSERT(slot.plan.mode != MaskMode::direct);
+        k::PostJob const& j = slot.kernel_jobs[i];
+        slot.clean_jobs.push_back(k::CleanJob{j.dst, j.out_w, j.out_h, clean[i].max_hole, clean[i].max_island});
+        // per polarity pass and pixel: the mask read (K1, K4), labels and areas written (K1) and read (K3: areas,
+        // K4: both twice), at most one byte written
+        clean_bytes += kCleanBytesPerPixelAndPass * (double)slot.input.sizes[i] * ((clean[i].max_hole > 0) + (clean[i].max_island > 0));
+    }
+    if (slot.clean_jobs.empty()) return;
+    const int n_clean = (int)slot.clean_jobs.size();
+    slot.clean_workspace.reserve(k::mask_cleanup_workspace_bytes(slot.clean_jobs.data(), n_clean));
+    clock_.timed(ST_POST, clean_bytes, [&] { k::mask_cleanup(slot.clean_jobs.data(), n_clean, slot.clean_workspace.get(), stream_); },
+                 clock_.profiling() ? k::mask_cleanup_launches(slot.clean_jobs.data(), n_clean) : 1);
+}
+
+// The mattes of the masks of launch step `s`, behind its post-processing launch and its clean-up: in place where the launch
+// wrote them, the slot's device buffer (a request with a matte never takes the direct mode).
+void MaskTransport::run_matte(MaskSlot& slot, MaskStep const& s, MatteRequest const* matte) {
+    slot.matte_jobs.clear();
+    double bytes = 0;
+    for (int i = s.first; i < s.first + s.count; ++i) {
+        if (!matte[i].any()) continue;
+        DLIMG_ASSERT(slot.plan.mode != MaskMode::direct);
+        k::PostJob const& j = slot.kernel_jobs[i];
+        slot.matte_jobs.push_back(k::MatteJob{j.dst, matte[i].guide, j.out_w, j.out_h, matte[i].channels, matte[i].radius, matte[i].eps});
+        bytes += (kMatteBytesPerPixel + 2 * matte[i].channels) * (double)slot.input.sizes[i];
+    }
+    if (slot.matte_jobs.empty()) return;
+    const int n = (int)slot.matte_jobs.size();
+    roctx::Range range("dlimg.mask_matte");
+    slot.matte_workspace.reserve(k::mask_matte_workspace_bytes(slot.matte_jobs.data(), n));
+    clock_.timed(ST_POST, bytes, [&] { k::mask_matte(slot.matte_jobs.data(), n, slot.matte_workspace.get(), stream_); },
+                 clock_.profiling() ? k::mask_matte_launches(slot.matte_jobs.data(), n) : 1);
+    HIP_CHECK(hipGetLastError());        // a launch that was not taken is reported here, not by the copy behind it
+}
+
 void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean,
-                            GridPaint const* paint) {
+                            GridPaint const* paint, MatteRequest const* matte) {
     if (count <= 0) return;
     // DLIMGEDIT_DIRECT_MASKS=0: measurement aid (always the copy path)
     static const bool direct_allowed = [] { const char* e = std::getenv("DLIMGEDIT_DIRECT_MASKS"); return !e || std::atoi(e) != 0; }();
@@ -164,7 +199,8 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
     fill_sizes(in.sizes, jobs, count);
     in.iou_count = iou_count;
     if (!any_cleanup(clean, count)) clean = nullptr;
-    in.direct_allowed = direct_allowed && !clean;      // a mask to clean goes through the slot's device buffer
+    if (!any_matte(matte, count)) matte = nullptr;
+    in.direct_allowed = direct_allowed && !clean && !matte;      // a mask to clean or to matte goes through the slot's device buffer
     in.others_idle = mask_mode_asks_idle(count, in.direct_allowed) && (!board_ || board_->others_idle(lane_index_));
     // a destination in pinned image memory of the library (the Image the reference's wrapper allocates for the result
     // through create_image).  Direct mode looks at every destination, staged mode only asks whether all of them are pinned:
@@ -176,7 +212,7 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
         if (!in.dst_pinned[i] && !every) break;
     }
     plan_mask_transport(in, slot.plan);
-    run(slot, jobs, count, iou, device_, clean, paint);
+    run(slot, jobs, count, iou, device_, clean, paint, matte);
     if (board_) board_->mark(lane_index_, stream_);
 }
 

@@ -11,6 +11,11 @@
 //                                            mode: k::mask_cleanup runs right behind the post-processing launch, in place
 //                                            where that launch wrote -- the slot's device buffer, or the destination itself
 //                                            when that is memory of the lane's own GPU -- before any copy or event
+//   matte (enqueue)                          optional, [count]: the matte of mask i (matte_plan.hpp; kernels.hpp K21; a null
+//                                            guide: none).  Treated as clean-up is: never the direct mode; k::mask_matte runs
+//                                            behind the post-processing launch and behind k::mask_cleanup when both are asked
+//                                            for, in place in the slot's device buffer, before any copy or event.  The guide
+//                                            is device memory of the lane (SamModel::matte_guide), valid in stream order
 //   paint (enqueue, enqueue_device)          optional: the request is ONE job whose bytes are a label map (grid_plan.hpp,
 //                                            kernels.hpp K18) -- the launch step runs k::grid_paint over the lane's grid store
 //                                            in place of the post-processing kernel; planning, staging, copies and events are
@@ -36,6 +41,13 @@ struct GridPaint {
     k::GridKept kept{};
 };
 
+// What a matte mark asks of one mask of a request: the guide where the lane uploaded it, and the mark's ints.
+struct MatteRequest {
+    uint8_t const* guide = nullptr;         // device memory, [out_h][out_w][channels]; null: the mask is delivered as it is
+    int channels = 0, radius = 0, eps = 0;
+    bool any() const { return guide != nullptr; }
+};
+
 struct MaskSlot {
     DeviceBuffer<uint8_t> dev;
     PinnedBuffer pin;
@@ -46,6 +58,8 @@ struct MaskSlot {
     std::vector<k::PostJob> kernel_jobs;    // the caller's jobs with the destinations the plan gives the kernel
     std::vector<k::CleanJob> clean_jobs;    // the masks of the request that are cleaned, where the kernel wrote them
     DeviceBuffer<uint8_t> clean_workspace;  // labels and areas of k::mask_cleanup, pooled with the slot like `dev`
+    std::vector<k::MatteJob> matte_jobs;    // the masks of the request that get a soft edge, where the kernel wrote them
+    DeviceBuffer<uint8_t> matte_workspace;  // the A and B planes and the cells of k::mask_matte, pooled with the slot like `dev`
 };
 
 class MaskTransport {
@@ -59,7 +73,7 @@ class MaskTransport {
     MaskSlot& acquire();
     void release(MaskSlot& s);
     void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean = nullptr,
-                 GridPaint const* paint = nullptr);
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr);
     void finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
     void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
                         GridPaint const* paint = nullptr);
@@ -68,7 +82,9 @@ class MaskTransport {
   private:
     hipEvent_t piece_event(MaskSlot& slot, int i);
     void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
-             GridPaint const* paint);
+             GridPaint const* paint, MatteRequest const* matte = nullptr);
+    void run_cleanup(MaskSlot& slot, MaskStep const& step, CleanSpec const* clean);
+    void run_matte(MaskSlot& slot, MaskStep const& step, MatteRequest const* matte);
 
     int device_;
     hipStream_t stream_;

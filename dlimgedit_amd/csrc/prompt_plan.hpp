@@ -38,8 +38,12 @@
 // marks to plan_grid_prompts.
 //
 // Lasso marks ({10, strength_milli, what, 0} directly behind a head: a selection whose box and first click are derived on the
-// GPU) are read by the outermost layer, lasso_plan.hpp (plan_lasso_prompts), which hands the call without its lasso marks to
+// GPU) are read one layer further out, in lasso_plan.hpp (plan_lasso_prompts), which hands the call without its lasso marks to
 // plan_prior_prompts and reserves the derived click and box in the PromptSpec.
+//
+// Matte marks ({11, radius, eps, channels}, the last entry of a prompt: the mask delivered as coverage, its edge guided by the
+// image) are read by the outermost layer, matte_plan.hpp (plan_matte_prompts), which hands the call without its matte marks to
+// plan_lasso_prompts.
 #pragma once
 
 #include "prompt_geometry.hpp"

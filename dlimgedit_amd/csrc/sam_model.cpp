@@ -905,6 +905,29 @@ k::MaskSource SamModel::prior_plane(uint8_t const* mask, int w, int h, int pre_w
     return k::MaskSource{prior_plane_.get(), nullptr};
 }
 
+uint8_t const* SamModel::matte_guide(uint8_t const* guide, int w, int h, int channels) {
+    DLIMG_ASSERT(guide != nullptr && w > 0 && h > 0 && (channels == 1 || channels == 3 || channels == 4));
+    roctx::Range range("dlimg.matte_guide");
+    const size_t row = (size_t)w * channels, bytes = row * h;
+    // the lane's buffer is re-used by the next guide in stream order; growing it frees memory a queued kernel may still read
+    if (bytes > matte_guide_.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        matte_guide_.reserve(bytes);
+    }
+    if (image_memory_is_pinned(guide, bytes)) {
+        HIP_CHECK(hipMemcpyAsync(matte_guide_.get(), guide, bytes, hipMemcpyHostToDevice, stream_));     // as upload_image
+        HIP_CHECK(hipEventRecord(caller_copied_, stream_));
+        caller_copy_pending_ = true;
+    } else {
+        // packed into pinned staging here and now: the caller's bytes are not read again
+        hipEvent_t copied = nullptr;
+        uint8_t* pin = stage_rows(guide, row, h, (int)row, &copied);
+        HIP_CHECK(hipMemcpyAsync(matte_guide_.get(), pin, bytes, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipEventRecord(copied, stream_));
+    }
+    return matte_guide_.get();
+}
+
 k::MaskSource SamModel::lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli,
                                      int32_t record[kLassoRecordInts]) {
     static_assert(kLassoRowRecordInts == k::kLassoRowInts && kLassoRows == kLowRes, "one row record, one grid");

@@ -223,6 +223,12 @@ class SamModel {
     // box x0, y0, x1, y1, click x, click y, d2} in image pixels; all zero: the selection is empty).  Returns the plane, which is
     // the first stage's mask input when the mark asks for it.  strength_milli 0: the plane is scratch.
     k::MaskSource lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int strength_milli, int32_t record[8]);
+    // Matte marks (matte_plan.hpp; kernels.hpp K21): the guide [h][w][channels] u8 (HOST memory, tightly packed) uploaded to the
+    // lane's guide buffer on the lane's stream, for the mask request enqueued behind the decode (MatteRequest::guide).  The bytes
+    // travel as a prior's do: through the pinned staging ring, or copied from where they lie when they are pinned image memory
+    // of the library, and then the caller waits for that copy (wait_caller_copies).  One buffer per lane, grown (behind a wait for
+    // the stream) to the largest guide seen and kept: valid until the next matte_guide of this lane, in stream order.
+    uint8_t const* matte_guide(uint8_t const* guide, int w, int h, int channels);
     // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
     std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
@@ -263,8 +269,8 @@ class SamModel {
     MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
     void release_mask_slot(MaskSlot& s) { masks_.release(s); }
     void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count, CleanSpec const* clean = nullptr,
-                       GridPaint const* paint = nullptr) {
-        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean, paint);
+                       GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) {
+        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean, paint, matte);
     }
     void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) { masks_.finish(slot, jobs, count, iou_out, iou_count); }
     void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
@@ -412,6 +418,7 @@ class SamModel {
     GridPaint grid_paint_;
     DeviceBuffer<uint8_t> prior_bytes_;  // prior marks: the caller's mask at its own size (grow-only) and its plane [256][256]
     DeviceBuffer<float> prior_plane_;
+    DeviceBuffer<uint8_t> matte_guide_;  // matte marks: the guide of the prompt being decoded (grow-only, as prior_bytes_)
     DeviceBuffer<int32_t> lasso_scratch_;    // lasso marks: g [256][256] and the row records [256][8] behind it
     PinnedBuffer lasso_host_;
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;

@@ -2,6 +2,7 @@
 
 #include "grid_plan.hpp"
 #include "lasso_plan.hpp"
+#include "matte_plan.hpp"
 #include "prior_plan.hpp"
 #include "prompt_plan.hpp"
 #include "roctx.hpp"
@@ -47,6 +48,9 @@ struct BatchPrompts {
     std::vector<LassoSpec> lasso;      // [prompt]: what its lasso mark says (lasso_plan.hpp; nothing without one); its packed points
                                        // are written once its click and box are derived (decode_batch_on)
     std::vector<uint8_t const*> lasso_mask;    // [prompt]: the selection, out_masks[] of the mark's entry (null without one)
+    std::vector<MatteSpec> matte;      // [prompt]: what its matte mark says (matte_plan.hpp; nothing without one)
+    std::vector<uint8_t const*> matte_guide;   // [prompt]: the guide, out_masks[] of the mark's entry (null without one)
+    bool any_matte = false;
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -68,8 +72,12 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        LassoPlannedPrompts with_lassos = plan_lasso_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+        MattePlannedPrompts with_mattes = plan_matte_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
                                                              /*device_form*/ out_masks == nullptr);
+        b.matte = std::move(with_mattes.matte);
+        b.any_matte = with_mattes.any_matte;
+        for (MatteSpec const& m : b.matte) b.matte_guide.push_back(m.any() ? out_masks[m.entry] : nullptr);
+        LassoPlannedPrompts& with_lassos = with_mattes.inner;
         PriorPlannedPrompts& with_priors = with_lassos.inner;
         b.lasso = std::move(with_lassos.lasso);
         for (LassoSpec const& l : b.lasso) b.lasso_mask.push_back(l.any() ? out_masks[l.entry] : nullptr);
@@ -105,17 +113,18 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
 // What one GPU decodes: its unstaged prompts in chunks as plan_prompt_chunks cuts them, then every staged prompt as a chunk
 // of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).  A prompt with
 // a prior is decoded the way a staged prompt is, whether it has refinement marks or not: its first stage takes a mask input.
-// So is a prompt with a lasso mark: its click and box are derived on the lane in front of its stages.
+// So is a prompt with a lasso mark: its click and box are derived on the lane in front of its stages.  And so is a prompt with
+// a matte mark: its guide is uploaded on the lane in front of its decode.
 // A grid prompt is a chunk of its own too, behind those: its side * side decodes and its label map run on one lane.
 struct BatchWork { PromptChunk part; bool staged; bool grid = false; };
 std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
     std::vector<int> plain;
     for (int j : mine)
-        if (!b.stages[j].staged() && !b.prior[j].any() && !b.lasso[j].any() && !b.grid[j].any()) plain.push_back(j);
+        if (!b.stages[j].staged() && !b.prior[j].any() && !b.lasso[j].any() && !b.matte[j].any() && !b.grid[j].any()) plain.push_back(j);
     std::vector<BatchWork> work;
     for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
     for (int j : mine)
-        if (b.stages[j].staged() || b.prior[j].any() || b.lasso[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+        if (b.stages[j].staged() || b.prior[j].any() || b.lasso[j].any() || b.matte[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
     for (int j : mine)
         if (b.grid[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, false, true});
     return work;
@@ -543,8 +552,8 @@ struct HostMasks {
     uint8_t* const* out_masks;
     uint8_t* dst(int head) const { return out_masks[head]; }
     void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
-                 GridPaint const* paint = nullptr) const {
-        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean, paint);
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) const {
+        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean, paint, matte);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
         model.finish_masks(slot, jobs.data(), (int)jobs.size(), nullptr, 0);
@@ -558,7 +567,8 @@ struct DeviceMasks {
     int root_device;
     uint8_t* dst(int head) const { return dev_out + offsets[head]; }
     void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
-                 GridPaint const* paint = nullptr) const {
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) const {
+        DLIMG_ASSERT(!matte);                    // (the planner refuses a matte mark in the device form)
         model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean, paint);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const&) const { model.wait_masks(slot); }
@@ -570,7 +580,8 @@ struct DeviceMasks {
 // lane and its masks handed to `sink`.  A prompt with refinement marks is a chunk of its own behind them: its stages run in
 // order on one lane's stream, each taking the logits of the one before it as its mask input, and only the last one is
 // post-processed.  A prompt with a clean-up mark has its mask cleaned on the GPU behind the post-processing (the mask of the
-// last stage only; the logits fed back between stages are untouched).
+// last stage only; the logits fed back between stages are untouched).  A prompt with a matte mark has its mask -- the cleaned
+// one when it has both -- turned into a coverage on the GPU behind that, guided by the image the mark brought.
 template <typename Sink>
 void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
                                        int const* regions, Sink const& sink) {
@@ -583,6 +594,7 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
     struct Chunk { MaskSlotLease lease; std::vector<k::PostJob> jobs; };
     std::vector<Chunk> chunks;
     std::vector<CleanSpec> clean;              // of the chunk being enqueued, [job]
+    MatteRequest matte;                        // of the chunk being enqueued: a prompt with a matte mark is a chunk of its own
     auto finish = [&](Chunk& c) {
         if (!c.lease.held()) return;
         const MaskSlotLease lease = std::move(c.lease);      // the slot goes back whether the wait throws or not
@@ -625,6 +637,13 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 if (batch.prior[j].any())
                     first = model.prior_plane(batch.prior_mask[j], rs.original.width, rs.original.height, rs.resized.width, rs.resized.height,
                                               batch.prior[j].strength_milli);
+                // a guide: its bytes are enqueued here too, for the matte behind the post-processing of this prompt's mask
+                matte = MatteRequest{};
+                if (batch.matte[j].any()) {
+                    MatteSpec const& m = batch.matte[j];
+                    matte = MatteRequest{model.matte_guide(batch.matte_guide[j], rs.original.width, rs.original.height, m.channels), m.channels,
+                                         m.radius, m.eps};
+                }
                 k::MaskSource src;
                 if (batch.lasso[j].any()) {
                     // a selection: uploaded and turned into the plane as a prior is, its box and click derived behind that; the
@@ -651,8 +670,9 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                     src = run_early_stages(model, prompts[j], batch.stages[j], emb[0], rs, points, regions, first);
                 }
                 model.decode(emb.data(), cc.data(), ll.data(), 1, npts, src.logits4 ? &src : nullptr, /*handles*/ true);
-                model.wait_caller_copies();        // a prior read in place (pinned image memory): the caller's again
+                model.wait_caller_copies();        // a prior or a guide read in place (pinned image memory): the caller's again
             } else {
+                matte = MatteRequest{};
                 model.decode(emb.data(), cc.data(), ll.data(), n, npts, nullptr, /*handles*/ true);
             }
             for (int j = 0; j < n; ++j) {
@@ -665,7 +685,8 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 clean.resize(n);
                 for (int j = 0; j < n; ++j) clean[j] = batch.clean[part.prompts[j]];
             }
-            sink.enqueue(model, cur.lease.slot(), cur.jobs, batch.any_clean ? clean.data() : nullptr);
+            // (a prompt with a matte mark is a chunk of its own: n == 1)
+            sink.enqueue(model, cur.lease.slot(), cur.jobs, batch.any_clean ? clean.data() : nullptr, nullptr, matte.any() ? &matte : nullptr);
         }
         for (auto& c : chunks) finish(c);
     } catch (...) {

@@ -153,7 +153,10 @@ typedef struct dlimg_Api {
      * out_masks[i] is READ: width * height bytes of the head's image, the prior.
      * Lasso marks (a selection snapped to the object): a continuation entry whose four ints are {DLIMG_LASSO_MARK,
      * strength_milli, what, 0} DIRECTLY BEHIND ITS HEAD -- see DLIMG_LASSO_MARK below.  Its out_masks[i] is READ likewise: the
-     * selection, from which the prompt's box and first click are derived on the GPU. */
+     * selection, from which the prompt's box and first click are derived on the GPU.
+     * Matte marks (an image-guided soft edge): a continuation entry whose four ints are {DLIMG_MATTE_MARK, radius, eps,
+     * channels}, THE LAST ENTRY OF ITS PROMPT -- see DLIMG_MATTE_MARK below.  Its out_masks[i] is READ as well: the image, the
+     * guide; the prompt's mask is then delivered as coverage 0 .. 255. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -237,6 +240,34 @@ typedef struct dlimg_Api {
 #define DLIMG_LASSO_BOX 1
 #define DLIMG_LASSO_CLICK 2
 #define DLIMG_LASSO_MASK 4
+/* regions[4 i] of a matte mark in get_segmentation_masks (slot 14): {DLIMG_MATTE_MARK, radius, eps, channels}, THE LAST ENTRY
+ * OF ITS PROMPT (behind the clean-up mark when the prompt has one, which is then the last of the remaining entries, as it must
+ * be), makes the prompt deliver its one mask as COVERAGE 0 .. 255 instead of 0 / 255: the mask the same prompt would deliver
+ * without the mark (after clean-up, if it has a clean-up mark), filtered with He et al.'s guided filter, the guide being the
+ * grey image.  Hair, fur and every edge that runs between the 256 x 256 low-res cells then follow the picture.
+ * The mark is neither a click nor a stage; points[i] is not read and it does not count towards the 8 clicks.  out_masks[i] OF
+ * THE MARK IS READ AS THE GUIDE: the image the head's handle was made from, height * width * channels bytes, tightly packed.
+ * It is uploaded before the mask of its prompt is delivered; in memory from create_image / load_image it is sent from where
+ * it lies.  channels is 1, 3 or 4; grey G = the byte for 1, else (c0 + 2 c1 + c2 + 2) >> 2, so RGBA and BGRA give the same
+ * matte and a fourth channel is ignored.  radius is 1 .. 32 pixels of the image.  eps is 1 .. 65025, in squared grey levels of
+ * the 0 .. 255 scale; 0 means 650, about 0.01 on the unit scale -- a choice, not a measurement.
+ * The definition is integer arithmetic, so the bytes are the same wherever they are computed.  With p the mask, F = 16,
+ * win(x, y) the (2 radius + 1)^2 square around a pixel clipped to the image, N its pixel count, fdiv floor division:
+ *   S_G, S_p, S_GG, S_Gp = sums of G, p, G^2, G p over win(x, y)
+ *   cov = N S_Gp - S_G S_p      den = N S_GG - S_G^2 + eps N^2
+ *   A = fdiv(2 cov 2^F + den, 2 den)      B = fdiv(2 (S_p 2^F - A S_G) + N, 2 N)
+ *   S_A, S_B = sums of A, B over win(x, y)
+ *   out = clamp(fdiv(2 (S_A G(x, y) + S_B) + N 2^F, 2 N 2^F), 0, 255)
+ * which is within one grey level of the float64 filter.  Where the mask is one value over the radius-2r square around a pixel
+ * the pixel keeps it exactly; with a constant guide the matte is the twice box-filtered mask.
+ * Everything in front of the mark is read as ever: clicks, box, refinement, prior, lasso and clean-up marks, SAM-HQ models.
+ * Like every call with continuation entries the call needs `regions`, and an empty head region means "no box".
+ * Refused before anything is launched (the message says "mark" and names the entry): a matte mark that is not the last entry
+ * of its prompt, one in front of any head, a second one on a prompt, a NULL guide, radius outside 1 .. 32, eps outside
+ * 0 .. 65025, channels other than 1 / 3 / 4, a grid prompt (a label map is not a coverage), and
+ * dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a guide from.  A call without matte marks
+ * is read as it always was. */
+#define DLIMG_MATTE_MARK 11      /* 5 and 9 stay refused labels */
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

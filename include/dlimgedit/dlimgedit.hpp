@@ -239,6 +239,18 @@ struct Lasso {
     int strength_milli = 0;
 };
 
+// A matte: the prompt's mask delivered as COVERAGE 0 .. 255 with an edge that follows the picture (He et al.'s guided filter on
+// the GPU, in integers; dlimgedit.h, DLIMG_MATTE_MARK).  guide: the image the segmentation was made from, height * width *
+// channels bytes, tightly packed; channels 1, 3 or 4 (RGBA and BGRA give the same matte).  radius: 1 .. 32 pixels.  eps: 1 ..
+// 65025 squared grey levels; 0: the library's default, 650.  Travels as a matte mark of table slot 14, the last entry of its
+// prompt.
+struct Matte {
+    uint8_t const* guide = nullptr;
+    int channels = 4;
+    int radius = 8;
+    int eps = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -249,7 +261,7 @@ struct Click {
 class Segmentation {
   public:
     struct Mask {
-        Image image;            // Channels::mask, values 0 / 255
+        Image image;            // Channels::mask, values 0 / 255 (coverage 0 .. 255 from a prompt with a Matte)
         float accuracy = 0.0f;  // predicted IoU
     };
 
@@ -347,22 +359,26 @@ class Segmentation {
     // prior: the caller's own mask as the mask input of the first stage (Prior).
     // lasso: the caller's selection, from which the box and / or the first click are derived (Lasso); the clicks given here
     // follow the derived one, and refine_after counts the clicks given here.  With DLIMG_LASSO_BOX there is no `region`.
+    // matte: the mask is delivered as coverage 0 .. 255, its edge guided by the image (Matte), behind the clean-up.
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
                        std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
-                       std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt) const {
+                       std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt,
+                       std::optional<Matte> matte = std::nullopt) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
                                             clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
                                             prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{},
-                                            lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{})[0]);
+                                            lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{},
+                                            matte ? std::vector<std::optional<Matte>>{matte} : std::vector<std::optional<Matte>>{})[0]);
     }
 
     // Snap a selection to the object (addition of this build): the lasso alone is the prompt -- its box, its most interior
     // point as a foreground click, and the selection itself as the mask input, whichever `what` names (Lasso) -- or the lasso
-    // and further clicks behind the derived one.  refine_after and cleanup as for compute_mask.  out_mask may be lasso.mask
-    // itself: a selection snapped in place.
+    // and further clicks behind the derived one.  refine_after, cleanup and matte as for compute_mask.  out_mask may be
+    // lasso.mask itself: a selection snapped in place.
     void snap(Lasso const& lasso, uint8_t* out_mask, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
-              std::optional<MaskCleanup> cleanup = std::nullopt) const {
+              std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
         if (!lasso.mask || !out_mask) throw Exception("snap: a lasso has a mask, and the result a place to go");
+        check_matte(matte, "snap");
         if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
             throw Exception("snap: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         if (clicks.size() > 8) throw Exception("snap: a prompt takes at most 8 clicks");
@@ -388,14 +404,23 @@ class Segmentation {
         }
         if (!clicks.empty() && !clicks[0].foreground) throw Exception("snap: the first click given is a foreground click");
         if (cleanup) entry(Point{0, 0}, Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}));
+        if (matte) {
+            entry(Point{0, 0}, Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}));
+            ptrs.back() = const_cast<uint8_t*>(matte->guide);      // the mark's out_masks pointer is the guide, which the call only reads
+        }
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), clicks.empty() ? nullptr : &pts.data()->x,
                                                    &regs.data()->top_left.x, ptrs.data()));
     }
     Image snap(Lasso const& lasso, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
-               std::optional<MaskCleanup> cleanup = std::nullopt) const {
+               std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
         Image m(extent(), Channels::mask);
-        snap(lasso, m.pixels(), clicks, refine_after, cleanup);
+        snap(lasso, m.pixels(), clicks, refine_after, cleanup, matte);
         return m;
+    }
+    static void check_matte(std::optional<Matte> const& m, char const* who) {
+        if (m && (!m->guide || m->radius < 1 || m->radius > 32 || m->eps < 0 || m->eps > 65025 ||
+                  (m->channels != 1 && m->channels != 3 && m->channels != 4)))
+            throw Exception(std::string(who) + ": a matte has a guide, a radius of 1 .. 32, an eps of 0 (the default) .. 65025 and 1, 3 or 4 channels");
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -406,17 +431,19 @@ class Segmentation {
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
     // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
     // optional clean-up per prompt; prior: empty, or one optional prior per prompt; lasso: empty, or one optional lasso per
-    // prompt (a prompt takes a prior or a lasso, not both).
+    // prompt (a prompt takes a prior or a lasso, not both); matte: empty, or one optional matte per prompt.
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
                                                  std::vector<std::vector<int>> const& refine_after = {},
                                                  std::vector<std::optional<MaskCleanup>> const& clean = {},
                                                  std::vector<std::optional<Prior>> const& prior = {},
-                                                 std::vector<std::optional<Lasso>> const& lasso = {}) {
+                                                 std::vector<std::optional<Lasso>> const& lasso = {},
+                                                 std::vector<std::optional<Matte>> const& matte = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
             (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
-            (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()))
+            (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()) ||
+            (!matte.empty() && matte.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
         for (auto const& p : prior)
             if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
@@ -424,6 +451,7 @@ class Segmentation {
         for (auto const& l : lasso)
             if (l && (!l->mask || l->what < 0 || l->what > 7 || l->what == DLIMG_LASSO_MASK || l->strength_milli < 0 || l->strength_milli > 100000))
                 throw Exception("compute_mask_batch: a lasso has a mask, a `what` of 0 (all) .. 7 other than 4, and a strength_milli of 0 .. 100000");
+        for (auto const& m : matte) check_matte(m, "compute_mask_batch");
         for (auto const& c : clean)
             if (c && (c->max_hole < 0 || c->max_island < 0 || (c->max_hole == 0 && c->max_island == 0)))
                 throw Exception("compute_mask_batch: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
@@ -437,7 +465,8 @@ class Segmentation {
             if (clicks[j].empty() || clicks[j].size() > 8) throw Exception("compute_mask_batch: a prompt takes 1 to 8 clicks");
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
             refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value()) ||
-                      (!prior.empty() && prior[j].has_value()) || (!lasso.empty() && lasso[j].has_value());     // any continuation entry
+                      (!prior.empty() && prior[j].has_value()) || (!lasso.empty() && lasso[j].has_value()) ||
+                      (!matte.empty() && matte[j].has_value());                                                // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -482,6 +511,12 @@ class Segmentation {
                     pts.push_back(Point{0, 0});
                     ptrs.push_back(nullptr);
                     regs.push_back(Region(Point{DLIMG_CLEAN_MARK, clean[j]->max_hole}, Point{clean[j]->max_island, 0}));
+                }
+                if (!matte.empty() && matte[j]) {
+                    hs.push_back(nullptr);               // the matte mark, behind everything else of its prompt: its point is not
+                    pts.push_back(Point{0, 0});          // read and its out_masks pointer is the guide, which the call only reads
+                    ptrs.push_back(const_cast<uint8_t*>(matte[j]->guide));
+                    regs.push_back(Region(Point{DLIMG_MATTE_MARK, matte[j]->radius}, Point{matte[j]->eps, matte[j]->channels}));
                 }
             }
             if (hs.empty()) continue;
