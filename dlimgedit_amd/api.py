@@ -25,7 +25,7 @@ LIB_PATH = Path(__file__).resolve().parent / "lib" / "libdlimgedit.so"
 # ext.mask_pieces, ext.plan_steps) are not in the product library: they come from lib/libdlimgedit_test.so, the product's own
 # objects plus the hook sources csrc/*test_hooks.cpp, loaded next to the product the first time a hook is called.
 HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_test.so")
-# ext.test_matte alone comes from a library of its own (build.py: LIB_MATTE_HOOKS; the tuning library has it as well)
+# ext.test_matte and ext.test_stroke_derive come from a library of their own (build.py: LIB_MATTE_HOOKS; the tuning library has it as well)
 MATTE_HOOKS_LIB_PATH = LIB_PATH.with_name("libdlimgedit_matte_hooks.so")
 # tools/ only: the -DDLIMG_TUNING build with ablated kernel variants and in-kernel stamps (python -m dlimgedit_amd.build --tuning);
 # it exports the hooks too, so one library serves both roles
@@ -161,8 +161,8 @@ _matte_hooks_lib = None
 
 
 def matte_hooks_library() -> C.CDLL:
-    """Loads the library that exports dlimg_amd_test_matte (libdlimgedit_matte_hooks.so; the tuning library when one is
-    selected).  Raises if it has not been built."""
+    """Loads the library that exports dlimg_amd_test_matte and dlimg_amd_test_stroke_derive (libdlimgedit_matte_hooks.so; the
+    tuning library when one is selected).  Raises if it has not been built."""
     global _matte_hooks_lib
     if _matte_hooks_lib is None:
         if HOOKS_LIB_PATH == LIB_PATH:
@@ -177,6 +177,9 @@ def matte_hooks_library() -> C.CDLL:
         _matte_hooks_lib.dlimg_amd_test_matte.argtypes = [_vpp, _vpp, _ip, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int,
                                                           C.POINTER(C.c_float)]
         _matte_hooks_lib.dlimg_amd_test_matte.restype = C.c_int
+        _matte_hooks_lib.dlimg_amd_test_stroke_derive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                                  C.POINTER(C.c_uint64), _ip, C.c_int, C.POINTER(C.c_float)]
+        _matte_hooks_lib.dlimg_amd_test_stroke_derive.restype = C.c_int
     return _matte_hooks_lib
 
 
@@ -342,6 +345,8 @@ MATTE_MARK = 11              # regions[4 i] of a matte mark (dlimgedit.h: DLIMG_
 MATTE_MAX_RADIUS = 32
 MATTE_MAX_EPS = 65025        # eps of a matte mark, at most, in squared grey levels; 0: the library's default
 MATTE_DEFAULT_EPS = 650
+STROKE_MARK = 12             # regions[4 i] of a stroke mark (dlimgedit.h: DLIMG_STROKE_MARK; csrc/stroke_plan.hpp: kStrokeMark)
+STROKE_DEFAULT_CLICKS = 3    # clicks of a stroke mark that says 0
 
 
 @dataclass
@@ -372,7 +377,12 @@ class ClickEntries:
     box.  Such a prompt is decoded behind the others like a prompt with marks.
     A matte mark is a continuation entry (MATTE_MARK, radius, eps, channels), the last entry of its prompt (behind the clean-up
     mark), whose out_masks pointer is READ as well: mattes[j] is the (h, w[, c]) uint8 image that guides the soft edge of prompt
-    j's mask, None without one.  It changes neither token_rows nor stage_clicks; such a prompt is decoded on its own."""
+    j's mask, None without one.  It changes neither token_rows nor stage_clicks; such a prompt is decoded on its own.
+    A stroke mark is a continuation entry (STROKE_MARK, clicks, label, 0) behind the prompt's clicks, whose out_masks pointer is
+    READ as a stroke map: strokes[j] are the (h, w) uint8 maps of prompt j's marks in their order, [] without one.  Each stands
+    for `clicks` clicks (0: STROKE_DEFAULT_CLICKS) of its label, derived on the GPU: token_rows and stage_clicks count them (they
+    belong to the last stage).  When the prompts of a call have strokes and no clicks, `points` is None and the first foreground
+    click of every prompt is its head's.  Such a prompt is decoded behind the others like a prompt with marks."""
     heads: list
     points: list
     regions: list
@@ -383,10 +393,12 @@ class ClickEntries:
     priors: list = field(default_factory=list)
     lassos: list = field(default_factory=list)
     mattes: list = field(default_factory=list)
+    strokes: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
         return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None) \
-            or (j < len(self.lassos) and self.lassos[j] is not None) or (j < len(self.mattes) and self.mattes[j] is not None)
+            or (j < len(self.lassos) and self.lassos[j] is not None) or (j < len(self.mattes) and self.mattes[j] is not None) \
+            or (j < len(self.strokes) and len(self.strokes[j]) > 0)
 
     def _grid(self, j) -> bool:
         return j < len(self.grid_sides) and self.grid_sides[j] > 0
@@ -585,15 +597,51 @@ def _checked_matte(matte, n: int) -> list:
     return out
 
 
+def _checked_strokes(strokes, n: int) -> list:
+    """`strokes` of a call of n prompts -> per prompt a list of ((h, w) uint8 array, label, clicks), empty without strokes:
+    strokes is None or one entry per prompt, None or a sequence of (map, label, clicks) with label 1 (foreground) or 0
+    (background) and clicks 0 (the library's default, 3) .. 8."""
+    if strokes is None:
+        return [[] for _ in range(n)]
+    strokes = list(strokes)
+    if len(strokes) != n:
+        raise Error("strokes: None, or one entry (None or a list of (map, label, clicks)) per prompt")
+    out = []
+    for marks in strokes:
+        if marks is None:
+            out.append([])
+            continue
+        if not isinstance(marks, (list, tuple)) or any(not isinstance(q, (list, tuple)) or len(q) != 3 for q in marks):
+            raise Error("strokes: the strokes of a prompt are a list of (map, label, clicks)")
+        checked = []
+        for m, label, clicks in marks:
+            if not isinstance(m, np.ndarray) or m.dtype != np.uint8 or m.ndim != 2 or not m.flags.c_contiguous:
+                raise Error("strokes: a stroke map is a C-contiguous (h, w) uint8 array of the image's extent")
+            if not isinstance(label, (int, np.integer)) or int(label) not in (0, 1):
+                raise Error("strokes: the label of a stroke is 1 (foreground) or 0 (background)")
+            if not isinstance(clicks, (int, np.integer)) or not 0 <= int(clicks) <= MAX_CLICKS:
+                raise Error(f"strokes: clicks is 0 (the default, {STROKE_DEFAULT_CLICKS}) .. {MAX_CLICKS}")
+            checked.append((m, int(label), int(clicks)))
+        out.append(checked)
+    return out
+
+
 def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos: Optional[list] = None,
-                    mattes: Optional[list] = None) -> list:
+                    mattes: Optional[list] = None, strokes: Optional[list] = None) -> list:
     """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), the selection of
-    a lasso mark (lassos likewise), the guide of a matte mark (mattes likewise), None otherwise."""
-    ptrs, head = [], None
+    a lasso mark (lassos likewise), the guide of a matte mark (mattes likewise), the map of a stroke mark (strokes likewise, the
+    marks of a prompt in their order), None otherwise."""
+    ptrs, head, mark = [], None, 0
     for e, h in enumerate(heads):
         if h is not None:
-            head = h
+            head, mark = h, 0
             ptrs.append(outs_by_head[e].ctypes.data)
+        elif regs[e][0] == STROKE_MARK and head is not None and strokes is not None and mark < len(strokes[head]):
+            m, ext = strokes[head][mark][0], segs[head].extent()
+            mark += 1
+            if m.shape != (ext.height, ext.width):
+                raise Error(f"strokes: a stroke map of prompt {head} is {m.shape[1]} x {m.shape[0]}, its image {ext.width} x {ext.height}")
+            ptrs.append(m.ctypes.data)
         elif regs[e][0] == PRIOR_MARK and head is not None and priors[head] is not None:
             m, ext = priors[head][0], segs[head].extent()
             if m.shape != (ext.height, ext.width):
@@ -674,7 +722,7 @@ def _marked_arrays(segs, heads, pts, regs):
 
 
 def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
-                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None) -> ClickEntries:
+                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None, strokes=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -693,8 +741,17 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     matte: None, or per prompt None / (image, radius, eps) -- a matte mark, the last entry of its prompt: the mask is delivered
     as coverage 0 .. 255, its edge guided by the image (see compute_mask_clicks).  Entry lists without matte marks are what
     they were.
+    strokes: None, or per prompt None / a list of (map, label, clicks) -- stroke marks behind the prompt's clicks, in front of
+    its clean-up mark: map an (h, w) uint8 scribble over the prompt's image (a pixel belongs to it from 128 on), label 1
+    (foreground) or 0 (background), clicks 1 .. 8 clicks to sample from it on the GPU, 0: the default 3.  The derived clicks count
+    towards the 8; refine_after counts the clicks given.  A prompt with strokes may have NO clicks (clicks[j] None): then no prompt
+    of the call has any, every one has a foreground stroke, whose first click is its head's, and the entry lists carry no
+    `points`.  Entry lists without strokes are what they were.
     Pure host code."""
     n = len(clicks)
+    strokes = _checked_strokes(strokes, n)
+    any_stroke = any(strokes)
+    clickless = [bool(strokes[j]) and not clicks[j] for j in range(n)]
     clean = _checked_clean(clean, n)
     grid = _checked_grid(grid, n)
     prior = _checked_prior(prior, prior_strength, n)
@@ -721,6 +778,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             raise Error("a grid prompt takes no lasso")
         if grid[j] is not None and matte[j] is not None:
             raise Error("a grid prompt takes no matte: a label map is not a coverage")
+        if grid[j] is not None and strokes[j]:
+            raise Error("a grid prompt takes no strokes")
+        if any_stroke:
+            out.strokes.append([q[0] for q in strokes[j]])
         if grid[j] is not None:
             if clicks[j] or labels[j] is not None or regions[j] is not None or refine_after[j] is not None or clean[j] is not None \
                     or prior[j] is not None:
@@ -732,9 +793,17 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.points += [(0, 0), (0, 0)]
             out.regions += [EMPTY_REGION, (GRID_MARK,) + grid[j]]
             continue
-        cs, ls = _checked_clicks(clicks[j], labels[j])
+        if clickless[j]:
+            if labels[j] or refine_after[j] is not None:
+                raise Error("strokes: labels and refine_after go with the clicks given, and this prompt has none")
+            if not any(label == 1 for _, label, _ in strokes[j]):
+                raise Error("strokes: background strokes alone are no prompt: without clicks a prompt needs a foreground stroke")
+            cs, ls = [], []
+        else:
+            cs, ls = _checked_clicks(clicks[j], labels[j])
         marks = _checked_marks(len(cs), refine_after[j])
         r = regions[j]
+        sampled = sum(q[2] or STROKE_DEFAULT_CLICKS for q in strokes[j])
         out.prompt_heads.append(len(out.heads))
         what = 0 if lasso[j] is None else (lasso[j][1] or 7)
         if what and prior[j] is not None:
@@ -742,8 +811,22 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
         if what & LASSO_BOX and r is not None:
             raise Error("lasso: with LASSO_BOX the prompt's box is the selection's: no region")
         derived = 1 if what & LASSO_CLICK else 0
-        out.token_rows.append(5 + derived + len(cs) + (2 if r is not None or what & LASSO_BOX else 1))
-        out.stage_clicks.append([k + derived for k in marks + [len(cs)]])
+        if derived + len(cs) + sampled > MAX_CLICKS:
+            raise Error(f"a prompt takes at most {MAX_CLICKS} clicks, the clicks its strokes stand for counted: not {derived + len(cs) + sampled}")
+        out.token_rows.append(5 + derived + len(cs) + sampled + (2 if r is not None or what & LASSO_BOX else 1))
+        out.stage_clicks.append([k + derived for k in marks] + [derived + len(cs) + sampled])
+        if clickless[j]:                     # the head alone: its click will be the first foreground click of its strokes
+            out.heads.append(j)
+            out.points.append((0, 0))
+            out.regions.append(EMPTY_REGION if r is None else (r.top_left.x, r.top_left.y, r.bottom_right.x, r.bottom_right.y))
+            if prior[j] is not None:
+                out.heads.append(None)
+                out.points.append((0, 0))
+                out.regions.append((PRIOR_MARK, prior[j][1], 0, 0))
+            if lasso[j] is not None:
+                out.heads.append(None)
+                out.points.append((0, 0))
+                out.regions.append((LASSO_MARK, lasso[j][2], lasso[j][1], 0))
         for k, (c, lab) in enumerate(zip(cs, ls)):
             if k in marks:               # a mark behind the first k clicks: in front of click k (0-based)
                 out.heads.append(None)
@@ -763,6 +846,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
                     out.heads.append(None)
                     out.points.append((0, 0))
                     out.regions.append((LASSO_MARK, lasso[j][2], lasso[j][1], 0))
+        for _, label, n_clicks in strokes[j]:    # behind the clicks given, in front of the marks that stay last
+            out.heads.append(None)
+            out.points.append((0, 0))
+            out.regions.append((STROKE_MARK, n_clicks, label, 0))
         if clean[j] is not None:
             out.heads.append(None)
             out.points.append((0, 0))
@@ -771,6 +858,12 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.heads.append(None)
             out.points.append((0, 0))
             out.regions.append((MATTE_MARK, matte[j][2], matte[j][3], matte[j][1]))
+    if any(clickless):
+        # a call without `points`: every prompt takes its head's click from a foreground stroke (dlimgedit.h, DLIMG_STROKE_MARK)
+        if not all(clickless):
+            raise Error("strokes: a prompt with strokes and no clicks travels in a call without `points`, so no prompt of the call has "
+                        "clicks and every one has a foreground stroke")
+        out.points = None
     return out
 
 
@@ -789,7 +882,7 @@ def _entry_calls(entries: ClickEntries) -> list:
 def _entry_arrays(segs, entries: ClickEntries, sel, regions_given: bool):
     n = len(sel)
     handles = (C.c_void_p * n)(*[None if entries.heads[i] is None else segs[entries.heads[i]]._handle for i in sel])
-    p = (C.c_int * (2 * n))(*[v for i in sel for v in entries.points[i]])
+    p = None if entries.points is None else (C.c_int * (2 * n))(*[v for i in sel for v in entries.points[i]])
     r = (C.c_int * (4 * n))(*[v for i in sel for v in entries.regions[i]]) if regions_given else None
     return n, handles, p, r
 
@@ -865,7 +958,7 @@ class Segmentation:
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
                             clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0,
                             lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0,
-                            matte=None) -> np.ndarray:
+                            matte=None, strokes=None) -> np.ndarray:
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
@@ -884,8 +977,13 @@ class Segmentation:
         deliver without it (cleaned, with `clean`) put through He et al.'s guided filter on the GPU, in integers, so that its
         edge follows the picture (dlimgedit.h, DLIMG_MATTE_MARK).  image: the image this segmentation was made from, an
         (h, w), (h, w, 3) or (h, w, 4) uint8 array (RGBA and BGRA give the same matte); radius 1 .. 32 pixels; eps 1 .. 65025
-        squared grey levels, 0: the library's default, 650."""
+        squared grey levels, 0: the library's default, 650.
+        strokes: a list of (map, label, clicks) -- scribbles over this image, (h, w) uint8 maps whose pixels belong to the stroke
+        from 128 on, each standing for `clicks` clicks (1 .. 8, 0: the default 3) of its label (1 foreground, 0 background) that
+        are sampled from it on the GPU, behind `clicks` (dlimgedit.h, DLIMG_STROKE_MARK).  With strokes, `clicks` may be None:
+        the first foreground click sampled is then the prompt's first.  See scribble."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
+                                               strokes=None if strokes is None else [list(strokes)],
                                                out=None if out is None else [out],
                                                refine_after=None if refine_after is None else [refine_after],
                                                clean=None if clean is None else [tuple(clean)],
@@ -913,12 +1011,23 @@ class Segmentation:
                                                lasso=[mask], lasso_what=what, lasso_strength=strength,
                                                matte=None if matte is None else [tuple(matte)])[0]
 
+    def scribble(self, fg: np.ndarray, bg: Optional[np.ndarray] = None, clicks: int = 0, region: Optional[Region] = None,
+                 out: Optional[np.ndarray] = None, clean=None, matte=None) -> np.ndarray:
+        """Select by scribbling: fg, an (h, w) uint8 map of a stroke drawn over the object (a pixel belongs to it from 128 on),
+        and optionally bg, a stroke over what the selection must leave out, are the prompt -- `clicks` foreground clicks (1 .. 8,
+        0: the default 3) spread along fg and as many background clicks along bg, sampled on the GPU from the 256 x 256 low-res
+        grid: the cell nearest the stroke's centroid, then farthest-point samples (dlimgedit.h, DLIMG_STROKE_MARK).  region: a
+        box to go with them; clean, matte and out as for compute_mask_clicks.  An empty stroke (no pixel from 128 on) raises
+        Error."""
+        marks = [(fg, 1, clicks)] + ([] if bg is None else [(bg, 0, clicks)])
+        return self.compute_mask_clicks(None, None, region, out, None, clean, matte=matte, strokes=marks)
+
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
                            clean=None, grid=None, prior=None, prior_strength=0, lasso=None, lasso_what=0,
-                           lasso_strength=0, matte=None) -> list:
+                           lasso_strength=0, matte=None, strokes=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -938,7 +1047,13 @@ class Segmentation:
         click; a call without `points` may hold lasso-only prompts (regions[i] None) beside box-only ones, and with lasso
         prompts alone neither `points` nor `regions` is needed.
         matte (either form): None, or per prompt None / (image, radius, eps) -- matte marks, see compute_mask_clicks: the mask
-        of such a prompt comes back as coverage 0 .. 255."""
+        of such a prompt comes back as coverage 0 .. 255.
+        strokes (with `clicks`, whose entries may then be None): None, or per prompt None / a list of (map, label, clicks) --
+        stroke marks, see compute_mask_clicks and scribble."""
+        if strokes is not None and clicks is None:
+            if points is not None:
+                raise Error("compute_mask_batch: strokes go with `clicks` (whose entries may be None), not with `points`")
+            clicks = [None] * len(segs)
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch: refine_after goes with `clicks`")
         if clicks is not None:
@@ -949,11 +1064,12 @@ class Segmentation:
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
             entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength, lasso, lasso_what,
-                                    lasso_strength, matte)
+                                    lasso_strength, matte, strokes)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             priors = _checked_prior(prior, prior_strength, len(segs))
             lassos = _checked_lasso(lasso, lasso_what, lasso_strength, len(segs))
-            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos, _checked_matte(matte, len(segs)))
+            all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos, _checked_matte(matte, len(segs)),
+                                       _checked_strokes(strokes, len(segs)))
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
                 ptrs = (C.c_void_p * n)(*[all_ptrs[i] for i in sel])
@@ -1621,6 +1737,27 @@ class ext:
             raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
         out = (masks, bool(ok.value), int(launches.value)) if many else (masks[0], bool(ok.value))
         return out if time_iters <= 0 else out + (float(ms.value),)
+
+    @classmethod
+    def test_stroke_derive(cls, stroke_map: np.ndarray, pre_w: int, pre_h: int, clicks: int = STROKE_DEFAULT_CLICKS, time_iters: int = 0):
+        """The stroke derivation alone (dlimg_amd_test_stroke_derive, lib/libdlimgedit_matte_hooks.so): stroke_map (h, w) uint8, of
+        an image that was encoded at pre_w x pre_h, through the two launches of k::stroke_derive on the default device, with guard
+        bytes around the map, the ballots and the record.  -> (record int32 [20] = ON cells, clicks, x0, y0 .. x7, y7, 0, 0 in
+        cells; ballots uint64 [256, 4]; guard bytes intact); with time_iters > 0 a fourth element, the milliseconds of one
+        derivation (both launches; the mean of time_iters repetitions between two events).  A refusal of the launcher raises
+        Error."""
+        stroke_map = np.ascontiguousarray(stroke_map, np.uint8)
+        assert stroke_map.ndim == 2
+        h, w = stroke_map.shape
+        record, bits = np.zeros(20, np.int32), np.zeros((256, 4), np.uint64)
+        ok, ms = C.c_int(0), C.c_float(0.0)
+        lib = matte_hooks_library()
+        if lib.dlimg_amd_test_stroke_derive(stroke_map.ctypes.data, w, h, int(pre_w), int(pre_h), int(clicks),
+                                            record.ctypes.data_as(C.POINTER(C.c_int32)), bits.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            C.byref(ok), int(time_iters), C.byref(ms)) != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        return (record, bits, bool(ok.value)) if time_iters <= 0 else (record, bits, bool(ok.value), float(ms.value))
 
     NECK_GUARD = 256          # bytes of guard pattern on either side of a buffer test_neck_conv_ln allocates for one image
     NECK_GUARD_BYTE = 0xA5

@@ -9,9 +9,11 @@ Three libraries come out of the same sources:
   lib/libdlimgedit_test.so    the product's OBJECTS plus the hook sources (HOOK_SOURCES, csrc/*test_hooks.cpp): additionally
                               exports the dlimg_amd_test_* / dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h)
                               the parity tests and the kernels-alone timing loops call; built by default next to the product
-  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp (MATTE_HOOK_SOURCE): exports dlimg_init and
-                              dlimg_amd_test_matte, the matte kernels alone (tests/test_gpu_matte_kernel.py).  The test library's
-                              list of hooks is held to its length by tests/test_abi.py, so this hook has a library of its own
+  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp and csrc/stroke_test_hooks.cpp
+                              (SIDE_HOOK_SOURCES): exports dlimg_init, dlimg_amd_test_matte, the matte kernels alone
+                              (tests/test_gpu_matte_kernel.py), and dlimg_amd_test_stroke_derive, the stroke derivation alone
+                              (tests/test_gpu_stroke_kernel.py).  The test library's list of hooks is held to its length by
+                              tests/test_abi.py, so these hooks have a library of their own
   lib/libdlimgedit_tuning.so  `--tuning`: everything compiled with -DDLIMG_TUNING -- additionally the ablated kernel variants
                               and in-kernel cycle stamps the scripts under tools/ use (DLIMGEDIT_*_ABLATE, GemmArgs::stamps);
                               tools select it with DLIMGEDIT_TUNING_LIB=1 (or the file name of a copy kept under lib/).
@@ -43,7 +45,7 @@ EXPORTS_TEST_MAP = CSRC / "exports_test.map"
 HOOK_SOURCES = ["test_hooks.cpp", "neck_test_hooks.cpp", "cleanup_test_hooks.cpp", "grid_test_hooks.cpp", "prior_test_hooks.cpp",
                 "lasso_test_hooks.cpp"]
 # its own library (and the tuning library), with a version script of its own
-MATTE_HOOK_SOURCE = "matte_test_hooks.cpp"
+SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp"]
 MATTE_HOOKS_MAP = CSRC / "matte_hooks_exports.map"
 
 SOURCES = [
@@ -60,6 +62,7 @@ SOURCES = [
     "kernels/mask_prior.hip",
     "kernels/mask_lasso.hip",
     "kernels/mask_matte.hip",
+    "kernels/mask_stroke.hip",
     "kernels/resize.hip",
     "kernels/objects.hip",
     "resize_tables.cpp",
@@ -88,6 +91,7 @@ EXTRA_FLAGS = {
     "kernels/mask_prior.hip": ["-ffp-contract=off"],       # one division, one multiply, bit for bit (tests/prior_ref.py)
     "kernels/mask_lasso.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbour all the same (tests/lasso_ref.py)
     "kernels/mask_matte.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbours all the same (tests/matte_ref.py)
+    "kernels/mask_stroke.hip": ["-ffp-contract=off"],      # integer throughout; as its neighbours all the same (tests/stroke_ref.py)
     "kernels/resize.hip": ["-ffp-contract=off"],
     "kernels/objects.hip": ["-ffp-contract=off"],
     "resize_tables.cpp": ["-ffp-contract=off"],
@@ -206,16 +210,16 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
     with ThreadPoolExecutor(workers) as ex:
         objs = list(ex.map(lambda s: _compile(s, force, hdr, tuning), SOURCES))
         hooks = list(ex.map(lambda s: _compile(s, force, hdr, tuning), HOOK_SOURCES))
-        matte_hook = _compile(MATTE_HOOK_SOURCE, force, hdr, tuning)
+        side_hooks = list(ex.map(lambda s: _compile(s, force, hdr, tuning), SIDE_HOOK_SOURCES))
     for side in ("neck", "cleanup", "grid", "prior", "lasso"):     # an older build's library per hook file: nothing loads them now
         (LIB.parent / f"libdlimgedit_{side}_test.so").unlink(missing_ok=True)
     if tuning:
-        if _stale(LIB_TUNING, objs + hooks + [matte_hook], force):
-            _link(LIB_TUNING, objs + hooks + [matte_hook], EXPORTS_TEST_MAP)
+        if _stale(LIB_TUNING, objs + hooks + side_hooks, force):
+            _link(LIB_TUNING, objs + hooks + side_hooks, EXPORTS_TEST_MAP)
         if verbose:
             print(f"built {LIB_TUNING} ({LIB_TUNING.stat().st_size / 1e6:.1f} MB)")
         return LIB_TUNING
-    if _stale(LIB, objs, force) or _stale(LIB_TEST, objs + hooks, force) or _stale(LIB_MATTE_HOOKS, objs + [matte_hook], force):
+    if _stale(LIB, objs, force) or _stale(LIB_TEST, objs + hooks, force) or _stale(LIB_MATTE_HOOKS, objs + side_hooks, force):
         for o in objs:                                          # before anything is linked: a refused build leaves no library
             if o.name.startswith("kernels_"):
                 check_packed_select_erratum(o)
@@ -223,7 +227,7 @@ def build(force: bool = False, verbose: bool = False, tuning: bool = False) -> P
             _link(LIB, objs, EXPORTS_MAP, SONAME)
         # the test library: the SAME objects (what the parity tests exercise is the product's code) + the hooks
         _link(LIB_TEST, objs + hooks, EXPORTS_TEST_MAP)
-        _link(LIB_MATTE_HOOKS, objs + [matte_hook], MATTE_HOOKS_MAP)
+        _link(LIB_MATTE_HOOKS, objs + side_hooks, MATTE_HOOKS_MAP)
     # consumers linked against the reference's library resolve libdlimgedit.so.1 (SOVERSION 1,
     # /root/reference/src/CMakeLists.txt:20-23)
     link = LIB.parent / SONAME

@@ -425,5 +425,23 @@ size_t mask_matte_workspace_bytes(const MatteJob* jobs, int count);
 int mask_matte_launches(const MatteJob* jobs, int count);            // kernel launches mask_matte makes for these jobs
 void mask_matte(const MatteJob* jobs_host, int count, void* workspace, hipStream_t, bool shortcut = true);
 
+// ---- stroke marks (K22, kernels/mask_stroke.hip) ----------------------------------------------
+// Clicks sampled from a caller's scribble: map [H][W] u8, tightly packed, of an image that was encoded at pre_w x pre_h; a pixel
+// belongs to the stroke when its byte is >= 128.  With sw = ceil(pre_w / 4), sh = ceil(pre_h / 4) and the footprints c0, c1, r0,
+// r1 of mask_prior above: cell (x, y), x < sw, y < sh, is ON when any pixel of map[r0 .. r1)[c0 .. c1) belongs to the stroke.
+//   ballots [256][4] u64     bit b of word [y][w] is cell (64 w + b, y); 0 outside the scored region
+//   record [kStrokeRecordInts] int32  {ON cells n, clicks, x0, y0 .. x7, y7, 0, 0}, cells; clicks not asked for are 0, and the
+//        whole record is 0 when no cell is ON
+//   click 0      the ON cell with the smallest (n x - Sx)^2 + (n y - Sy)^2 (int64; Sx, Sy the coordinate sums of the ON cells)
+//   click c > 0  the ON cell with the largest minimum over the clicks before it of dx^2 + dy^2: farthest-point sampling; with
+//                fewer ON cells than clicks a cell is chosen again
+// Ties go to the smallest y, then the smallest x.  Integer arithmetic throughout.  clicks 1 .. kStrokeMaxClicks.  Two launches,
+// no atomics on global memory, any W and H whose product fits 2^31; 16-byte loads when W is a multiple of 16 and the map aligned.
+constexpr int kStrokeRecordInts = 20;
+constexpr int kStrokeMaxClicks = 8;
+constexpr int kStrokeBallotWords = 256 * 4;
+void stroke_derive(const uint8_t* map, int W, int H, int pre_w, int pre_h, int clicks, unsigned long long* ballots, int32_t* record,
+                   hipStream_t);
+
 }  // namespace k
 }  // namespace dlimg

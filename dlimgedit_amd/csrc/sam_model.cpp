@@ -4,6 +4,7 @@
 #include "image_memory.hpp"
 #include "lasso_plan.hpp"
 #include "roctx.hpp"
+#include "stroke_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -946,6 +947,47 @@ k::MaskSource SamModel::lasso_derive(uint8_t const* mask, int w, int h, int pre_
     HIP_CHECK(hipStreamSynchronize(stream_));          // the one host round trip of a lasso prompt
     fold_lasso_rows(static_cast<int32_t const*>(lasso_host_.get()), w, h, pre_w, pre_h, record);
     return plane;
+}
+
+void SamModel::stroke_derive(uint8_t const* map, int w, int h, int pre_w, int pre_h, int clicks, int32_t const** record) {
+    static_assert(kStrokeRecordInts == k::kStrokeRecordInts && kMaxClicks == k::kStrokeMaxClicks, "one record, one limit");
+    DLIMG_ASSERT(map != nullptr && record != nullptr && w > 0 && h > 0 && stroke_queued_ < kMaxClicks);
+    roctx::Range range("dlimg.stroke_derive");
+    const size_t bytes = (size_t)w * h;
+    // the lane's buffer is re-used by the next map in stream order; growing it frees memory a queued kernel may still read
+    if (bytes > stroke_bytes_.capacity()) {
+        HIP_CHECK(hipStreamSynchronize(stream_));
+        stroke_bytes_.reserve(bytes);
+    }
+    constexpr size_t kBallotInts = (size_t)k::kStrokeBallotWords * 2, kRecords = (size_t)kMaxClicks * kStrokeRecordInts;
+    stroke_scratch_.reserve(kBallotInts + kRecords);           // allocated once
+    stroke_host_.reserve(kRecords * sizeof(int32_t));
+    if (image_memory_is_pinned(map, bytes)) {
+        HIP_CHECK(hipMemcpyAsync(stroke_bytes_.get(), map, bytes, hipMemcpyHostToDevice, stream_));       // as upload_image
+        HIP_CHECK(hipEventRecord(caller_copied_, stream_));
+        caller_copy_pending_ = true;
+    } else {
+        // packed into pinned staging here and now: the caller's bytes are not read again
+        hipEvent_t copied = nullptr;
+        uint8_t* pin = stage_rows(map, (size_t)w, h, w, &copied);
+        HIP_CHECK(hipMemcpyAsync(stroke_bytes_.get(), pin, bytes, hipMemcpyHostToDevice, stream_));
+        HIP_CHECK(hipEventRecord(copied, stream_));
+    }
+    int32_t* const record_dev = stroke_scratch_.get() + kBallotInts + (size_t)stroke_queued_ * kStrokeRecordInts;
+    int32_t* const record_host = static_cast<int32_t*>(stroke_host_.get()) + (size_t)stroke_queued_ * kStrokeRecordInts;
+    clock_.timed(ST_POST, (double)bytes + 2.0 * kBallotInts * sizeof(int32_t), [&] {
+        k::stroke_derive(stroke_bytes_.get(), w, h, pre_w, pre_h, clicks, reinterpret_cast<unsigned long long*>(stroke_scratch_.get()),
+                         record_dev, stream_);
+    }, 2);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(record_host, record_dev, kStrokeRecordInts * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    ++stroke_queued_;
+    *record = record_host;
+}
+
+void SamModel::stroke_wait() {
+    stroke_queued_ = 0;
+    HIP_CHECK(hipStreamSynchronize(stream_));          // the one host round trip of a prompt with stroke marks
 }
 
 std::vector<std::pair<const char*, size_t>> SamModel::decoder_state_layout() { return decoder_state_layout(kDecTokens); }

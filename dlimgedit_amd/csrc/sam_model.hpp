@@ -229,6 +229,14 @@ class SamModel {
     // of the library, and then the caller waits for that copy (wait_caller_copies).  One buffer per lane, grown (behind a wait for
     // the stream) to the largest guide seen and kept: valid until the next matte_guide of this lane, in stream order.
     uint8_t const* matte_guide(uint8_t const* guide, int w, int h, int channels);
+    // Stroke marks (stroke_plan.hpp; kernels.hpp K22): the stroke map [h][w] u8 (HOST memory, tightly packed) of an image that was
+    // encoded at pre_w x pre_h uploaded as a prior's bytes are (staging ring, or in place from pinned image memory, and then the
+    // caller waits for that copy: wait_caller_copies), the two launches of the derivation behind it on the lane's stream and the
+    // record {ON cells, clicks, x0, y0 .. x7, y7, 0, 0} (cells) copied to pinned memory.  Nothing is waited for: the marks of one
+    // prompt (kMaxClicks at most) are enqueued back to back, *record is where this one's will lie, and stroke_wait is the ONE wait
+    // of the prompt, after which the records are valid until the next stroke_derive of this lane.
+    void stroke_derive(uint8_t const* map, int w, int h, int pre_w, int pre_h, int clicks, int32_t const** record);
+    void stroke_wait();
     // why a SAM-HQ model refuses a prompt of `points` points (empty: it does not)
     std::string hq_refusal(int points) const;
     bool has_mask_branch() const { return weights_->has_mask_branch_; }       // no mutex needed
@@ -421,6 +429,10 @@ class SamModel {
     DeviceBuffer<uint8_t> matte_guide_;  // matte marks: the guide of the prompt being decoded (grow-only, as prior_bytes_)
     DeviceBuffer<int32_t> lasso_scratch_;    // lasso marks: g [256][256] and the row records [256][8] behind it
     PinnedBuffer lasso_host_;
+    DeviceBuffer<uint8_t> stroke_bytes_;     // stroke marks: the map being derived from (grow-only, as prior_bytes_)
+    DeviceBuffer<int32_t> stroke_scratch_;   // the ballots [256][4] u64, then one record per mark of the prompt
+    PinnedBuffer stroke_host_;               // the records
+    int stroke_queued_ = 0;                  // marks enqueued since the last stroke_wait
     DeviceBuffer<float> tokens_, queries_, tk_, tv_, sq_, sk_, sv_, tsa_, tt2i_, tmlp_, t2i_part_;
 
     // ---- pass flags

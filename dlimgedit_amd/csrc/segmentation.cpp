@@ -6,6 +6,7 @@
 #include "prior_plan.hpp"
 #include "prompt_plan.hpp"
 #include "roctx.hpp"
+#include "stroke_plan.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -51,6 +52,18 @@ struct BatchPrompts {
     std::vector<MatteSpec> matte;      // [prompt]: what its matte mark says (matte_plan.hpp; nothing without one)
     std::vector<uint8_t const*> matte_guide;   // [prompt]: the guide, out_masks[] of the mark's entry (null without one)
     bool any_matte = false;
+    std::vector<std::vector<StrokeSpec>> strokes;      // [prompt]: its stroke marks (stroke_plan.hpp; none without one); its packed
+                                                       // points are written once their clicks are derived (decode_batch_on)
+    std::vector<std::vector<uint8_t const*>> stroke_map;       // [prompt][mark]: the map, out_masks[] of the mark's entry
+    // A call with stroke marks is REWRITTEN (stroke_plan.hpp): every list above numbers the entries of these arrays, which the
+    // batch call goes on with in place of the caller's; entry_of[e] is the caller's entry, for what is reported.  Empty otherwise.
+    std::vector<int> entry_of;
+    std::vector<SegmentationImpl const*> segs;
+    std::vector<int> points, regions;
+    std::vector<uint8_t*> out_masks;                   // a placeholder click's: its mark's map
+    int* derived_points = nullptr;                     // `points`, where decode_batch_on writes what the marks of a prompt derive
+    bool rewritten() const { return !entry_of.empty(); }
+    int caller_entry(int e) const { return rewritten() ? entry_of[e] : e; }
     std::vector<size_t> at;
     std::vector<float> coords, labels;
 };
@@ -72,8 +85,32 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        MattePlannedPrompts with_mattes = plan_matte_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
-                                                             /*device_form*/ out_masks == nullptr);
+        StrokePlannedPrompts with_strokes = plan_stroke_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+                                                                /*device_form*/ out_masks == nullptr);
+        b.strokes = std::move(with_strokes.strokes);
+        for (std::vector<StrokeSpec> const& marks : b.strokes) {
+            b.stroke_map.emplace_back();
+            for (StrokeSpec const& s : marks) b.stroke_map.back().push_back(out_masks[s.entry]);
+        }
+        if (with_strokes.any_stroke) {
+            // from here on the call is the rewritten one: a placeholder click has no point yet
+            b.entry_of = std::move(with_strokes.entry_of);
+            b.regions = std::move(with_strokes.regions);
+            for (size_t e = 0; e < b.entry_of.size(); ++e) {
+                const int from = b.entry_of[e];
+                b.segs.push_back(with_strokes.handles[e] ? segs[from] : nullptr);
+                b.out_masks.push_back(out_masks[from]);
+                const bool own = points && !with_strokes.derived[e];
+                b.points.push_back(own ? points[2 * from] : 0);
+                b.points.push_back(own ? points[2 * from + 1] : 0);
+            }
+            b.derived_points = b.points.data();
+            segs = b.segs.data();
+            points = b.points.data();
+            regions = b.regions.data();
+            out_masks = b.out_masks.data();
+        }
+        MattePlannedPrompts& with_mattes = with_strokes.inner;
         b.matte = std::move(with_mattes.matte);
         b.any_matte = with_mattes.any_matte;
         for (MatteSpec const& m : b.matte) b.matte_guide.push_back(m.any() ? out_masks[m.entry] : nullptr);
@@ -92,9 +129,12 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
         b.any_clean = plan.any_clean;
         // a SAM-HQ model takes one point less (its HQ token is a token row): refused here, before any prompt of the call is launched
         if (any)
-            for (PromptSpec const& p : b.prompts) {
-                const std::string why = any->environment().lane(any->replica(), 0).hq_refusal(p.points());
-                if (!why.empty()) throw Exception(why);
+            for (size_t j = 0; j < b.prompts.size(); ++j) {
+                const std::string why = any->environment().lane(any->replica(), 0).hq_refusal(b.prompts[j].points());
+                if (why.empty()) continue;
+                if (b.strokes[j].empty()) throw Exception(why);
+                throw Exception("mask batch: entry " + std::to_string(b.strokes[j].back().entry) + ": the clicks a stroke mark stands for "
+                                "count: " + why);
             }
     }
     size_t total = 0;
@@ -105,7 +145,8 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     b.coords.resize(total * 2);
     b.labels.resize(total);
     for (size_t j = 0; j < b.prompts.size(); ++j)
-        if (!b.grid[j].any() && !b.lasso[j].any())     // (a grid prompt's points are its grid's: pack_grid; a lasso prompt's are derived)
+        // (a grid prompt's points are its grid's: pack_grid; a lasso prompt's and a stroke prompt's are derived)
+        if (!b.grid[j].any() && !b.lasso[j].any() && b.strokes[j].empty())
             pack_points(segs[b.prompts[j].head]->geometry(), b.prompts[j], b.stages[j], b.prompts[j].clicks, points, regions,
                         &b.coords[b.at[j] * 2], &b.labels[b.at[j]]);
     return b;
@@ -114,17 +155,20 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
 // of its own (its stages run one after the other on one lane; equal stages of several prompts are not batched).  A prompt with
 // a prior is decoded the way a staged prompt is, whether it has refinement marks or not: its first stage takes a mask input.
 // So is a prompt with a lasso mark: its click and box are derived on the lane in front of its stages.  And so is a prompt with
-// a matte mark: its guide is uploaded on the lane in front of its decode.
+// a matte mark: its guide is uploaded on the lane in front of its decode.  And so is a prompt with stroke marks: the clicks they
+// stand for are derived on the lane in front of its stages.
 // A grid prompt is a chunk of its own too, behind those: its side * side decodes and its label map run on one lane.
 struct BatchWork { PromptChunk part; bool staged; bool grid = false; };
 std::vector<BatchWork> plan_batch_work(BatchPrompts const& b, std::vector<int> const& mine, int chunk) {
     std::vector<int> plain;
     for (int j : mine)
-        if (!b.stages[j].staged() && !b.prior[j].any() && !b.lasso[j].any() && !b.matte[j].any() && !b.grid[j].any()) plain.push_back(j);
+        if (!b.stages[j].staged() && !b.prior[j].any() && !b.lasso[j].any() && !b.matte[j].any() && b.strokes[j].empty() && !b.grid[j].any())
+            plain.push_back(j);
     std::vector<BatchWork> work;
     for (PromptChunk& part : plan_prompt_chunks(b.prompts, plain, chunk)) work.push_back(BatchWork{std::move(part), false});
     for (int j : mine)
-        if (b.stages[j].staged() || b.prior[j].any() || b.lasso[j].any() || b.matte[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
+        if (b.stages[j].staged() || b.prior[j].any() || b.lasso[j].any() || b.matte[j].any() || !b.strokes[j].empty())
+            work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, true});
     for (int j : mine)
         if (b.grid[j].any()) work.push_back(BatchWork{PromptChunk{b.prompts[j].points(), {j}}, false, true});
     return work;
@@ -644,6 +688,34 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                     matte = MatteRequest{model.matte_guide(batch.matte_guide[j], rs.original.width, rs.original.height, m.channels), m.channels,
                                          m.radius, m.eps};
                 }
+                if (!batch.strokes[j].empty()) {
+                    // stroke marks: every map of the prompt uploaded and derived back to back, the call waits for the lane's
+                    // stream once, and the pixels go where the placeholder clicks of the rewritten call stand
+                    std::vector<StrokeSpec> const& marks = batch.strokes[j];
+                    std::vector<int32_t const*> records(marks.size());
+                    for (size_t m = 0; m < marks.size(); ++m)
+                        model.stroke_derive(batch.stroke_map[j][m], rs.original.width, rs.original.height,
+                                            rs.resized.width, rs.resized.height, marks[m].clicks, &records[m]);
+                    model.stroke_wait();
+                    model.wait_caller_copies();
+                    for (size_t m = 0; m < marks.size(); ++m) {
+                        if (records[m][0] == 0) {
+                            // nothing of this prompt is queued (stroke_wait waited for the stream): its slot goes back unused, so
+                            // that nothing is delivered to its out_masks
+                            cur.lease.release();
+                            throw Exception("mask batch: entry " + std::to_string(marks[m].entry) + ": the stroke mark's map is empty: no "
+                                            "pixel of it is 128 or more, so there are no clicks to derive");
+                        }
+                        for (int c = 0; c < marks[m].clicks; ++c)
+                            stroke_cell_pixel(records[m][2 + 2 * c], records[m][3 + 2 * c], rs.original.width, rs.original.height,
+                                              rs.resized.width, rs.resized.height, batch.derived_points + 2 * marks[m].click_entry[c]);
+                    }
+                    if (!batch.lasso[j].any()) {
+                        cc.resize((size_t)npts * 2);
+                        ll.resize((size_t)npts);
+                        pack_points(rs, prompts[j], batch.stages[j], prompts[j].clicks, points, regions, cc.data(), ll.data());
+                    }
+                }
                 k::MaskSource src;
                 if (batch.lasso[j].any()) {
                     // a selection: uploaded and turned into the plane as a prior is, its box and click derived behind that; the
@@ -657,7 +729,7 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                         // nothing of this prompt is queued (lasso_derive waited for the stream): its slot goes back unused, so
                         // that nothing is delivered to its out_masks
                         cur.lease.release();
-                        throw Exception("mask batch: entry " + std::to_string(l.entry) + ": the lasso mark's selection is empty: no low-res "
+                        throw Exception("mask batch: entry " + std::to_string(batch.caller_entry(l.entry)) + ": the lasso mark's selection is empty: no low-res "
                                         "cell of it reaches half coverage, so there is no box and no click to derive");
                     }
                     const LassoPromptArrays own = lasso_prompt_arrays(prompts[j], batch.stages[j], l, points, regions, record);
@@ -707,6 +779,13 @@ void SegmentationImpl::compute_mask_batch(SegmentationImpl const* const* segs, i
     if (count <= 0) return;
     DLIMG_ASSERT(points != nullptr || regions != nullptr);
     const BatchPrompts batch = read_batch_prompts(segs, count, points, regions, out_masks);
+    if (batch.rewritten()) {
+        // stroke marks: the call goes on as the rewritten one, whose placeholder clicks the derivation fills in (stroke_plan.hpp)
+        segs = batch.segs.data();
+        points = batch.points.data();
+        regions = batch.regions.data();
+        out_masks = batch.out_masks.data();
+    }
     std::vector<PromptSpec> const& prompts = batch.prompts;
     EnvironmentImpl& env = segs[prompts[0].head]->env_;
     std::vector<int> used;

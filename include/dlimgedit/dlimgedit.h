@@ -156,7 +156,10 @@ typedef struct dlimg_Api {
      * selection, from which the prompt's box and first click are derived on the GPU.
      * Matte marks (an image-guided soft edge): a continuation entry whose four ints are {DLIMG_MATTE_MARK, radius, eps,
      * channels}, THE LAST ENTRY OF ITS PROMPT -- see DLIMG_MATTE_MARK below.  Its out_masks[i] is READ as well: the image, the
-     * guide; the prompt's mask is then delivered as coverage 0 .. 255. */
+     * guide; the prompt's mask is then delivered as coverage 0 .. 255.
+     * Stroke marks (clicks sampled from a scribble): a continuation entry whose four ints are {DLIMG_STROKE_MARK, clicks,
+     * label, 0}, wherever a click entry may stand -- see DLIMG_STROKE_MARK below.  Its out_masks[i] is READ too: the stroke map,
+     * from which that many clicks of that label are derived on the GPU. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -268,6 +271,37 @@ typedef struct dlimg_Api {
  * dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a guide from.  A call without matte marks
  * is read as it always was. */
 #define DLIMG_MATTE_MARK 11      /* 5 and 9 stay refused labels */
+/* regions[4 i] of a stroke mark in get_segmentation_masks (slot 14): {DLIMG_STROKE_MARK, clicks, label, 0} makes clicks of a
+ * scribble the caller holds -- a foreground stroke drawn over the object, a background stroke over what the selection must
+ * leave out.  label is 1 (foreground) or 0 (background); clicks is 1 .. 8, 0 meaning 3 -- a choice, not a measurement.
+ * points[i] of the mark is not read.  out_masks[i] OF THE MARK IS READ AS THE STROKE MAP: width * height bytes of the head's
+ * image, tightly packed; a pixel belongs to the stroke when its byte is >= 128.  The map is taken before anything is delivered
+ * (it may be out_masks[head] itself); in memory from create_image it is sent from where it lies.
+ * The mark may stand wherever a click entry may stand and STANDS FOR `clicks` click entries of its label at that position: they
+ * count towards the 8 clicks and towards a SAM-HQ file's point limit, a refinement mark behind them stages them like any click,
+ * and a prompt may hold several stroke marks (stroke, refinement mark, stroke).  Prior and lasso marks keep their place directly
+ * behind the head, in front of every stroke mark; clean-up and matte marks stay last, behind every stroke mark.  In a call
+ * WITHOUT `points` the first foreground click a prompt's strokes stand for takes the place of the head's own click, the others
+ * keep their order; every prompt of such a call therefore needs a foreground stroke mark, and a click entry still needs
+ * `points`.  With `points` the head's click comes first, as always.
+ * The derivation is integer arithmetic on the 256 x 256 low-res grid.  With the image encoded at pre_w x pre_h, cell (x, y),
+ * x < ceil(pre_w / 4), y < ceil(pre_h / 4), stands for the source pixels floor(4 x W / pre_w) .. ceil(min(4 x + 4, pre_w) W /
+ * pre_w) - 1 (rows likewise), exactly as for a prior mark, and is ON when ANY of them belongs to the stroke (a maximum, not the
+ * prior's mean: a one-pixel line switches on every cell it crosses).  With n ON cells of coordinate sums Sx, Sy the first click
+ * is the ON cell with the smallest (n x - Sx)^2 + (n y - Sy)^2 -- the one nearest the centroid; every further click is the ON
+ * cell with the largest minimum of dx^2 + dy^2 to the cells chosen before it (farthest-point sampling).  Ties go to the smallest
+ * y, then the smallest x; with fewer ON cells than clicks a cell is chosen again.  A click is the middle pixel of its cell's
+ * source pixels.
+ * Refused before anything is launched (the message says "mark" and names the entry): a non-zero fourth int, label outside
+ * {0, 1}, clicks outside 0 .. 8, a NULL map, a mark in front of any head, a grid prompt, a stroke mark in front of a prior or
+ * lasso mark or behind a clean-up or matte mark, a call without `points` in which a prompt has no foreground stroke mark
+ * (background strokes alone are no prompt), more than 8 clicks or a SAM-HQ file's limit counting the derived clicks, and
+ * dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to read a map from.
+ * ONE refusal arrives later, as a lasso mark's: a map without a stroke pixel in the image is reported after the derivation ran
+ * and before its prompt is decoded -- "entry i: the stroke mark's map is empty ...".  out_masks of that prompt is not written;
+ * what OTHER prompts of the same call have received by then is unspecified.  The call waits for the GPU once per prompt with
+ * stroke marks, however many it has.  A call without stroke marks is read as it always was. */
+#define DLIMG_STROKE_MARK 12
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

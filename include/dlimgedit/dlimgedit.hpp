@@ -251,6 +251,18 @@ struct Matte {
     int eps = 0;
 };
 
+// A stroke: a scribble the caller holds, from which `clicks` clicks of one label are sampled on the GPU -- spread along it:
+// the low-res cell nearest its centroid, then farthest-point samples (dlimgedit.h, DLIMG_STROKE_MARK).  map: width * height
+// bytes of the segmentation's image, tightly packed; a pixel belongs to the stroke when its byte is >= 128.  label: 1, a
+// foreground stroke drawn over the object, or 0, a background stroke over what the selection must leave out.  clicks: 1 .. 8;
+// 0: the library's default, 3.  The sampled clicks count towards the 8 clicks of a prompt.  Travels as a stroke mark of table
+// slot 14.
+struct Stroke {
+    uint8_t const* map = nullptr;
+    int label = 1;
+    int clicks = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -360,15 +372,61 @@ class Segmentation {
     // lasso: the caller's selection, from which the box and / or the first click are derived (Lasso); the clicks given here
     // follow the derived one, and refine_after counts the clicks given here.  With DLIMG_LASSO_BOX there is no `region`.
     // matte: the mask is delivered as coverage 0 .. 255, its edge guided by the image (Matte), behind the clean-up.
+    // strokes: scribbles whose sampled clicks follow the clicks given here (Stroke), in the order given; refine_after counts the
+    // clicks given here.  (The last argument, behind matte, so that calls written before it read as they did.)
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
                        std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
                        std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt,
-                       std::optional<Matte> matte = std::nullopt) const {
+                       std::optional<Matte> matte = std::nullopt, std::vector<Stroke> const& strokes = {}) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
                                             clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
                                             prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{},
                                             lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{},
-                                            matte ? std::vector<std::optional<Matte>>{matte} : std::vector<std::optional<Matte>>{})[0]);
+                                            matte ? std::vector<std::optional<Matte>>{matte} : std::vector<std::optional<Matte>>{},
+                                            strokes.empty() ? std::vector<std::vector<Stroke>>{} : std::vector<std::vector<Stroke>>{strokes})[0]);
+    }
+
+    // Select by scribbling (addition of this build): the strokes alone are the prompt -- the clicks sampled from them in the
+    // order given, the first FOREGROUND one first (so at least one stroke is a foreground stroke), and an optional box.  cleanup
+    // and matte as for compute_mask.  out_mask may be a stroke's map itself.  A stroke without a pixel >= 128 is reported by the
+    // library ("the stroke mark's map is empty") and nothing is delivered.
+    void scribble(std::vector<Stroke> const& strokes, uint8_t* out_mask, std::optional<Region> region = std::nullopt,
+                  std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+        if (!out_mask) throw Exception("scribble: the result has a place to go");
+        check_strokes(strokes, "scribble");
+        check_matte(matte, "scribble");
+        if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
+            throw Exception("scribble: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
+        if (std::none_of(strokes.begin(), strokes.end(), [](Stroke const& s) { return s.label == 1; }))
+            throw Exception("scribble: background strokes alone are no prompt: one stroke is a foreground stroke");
+        // the head with its box (or the empty region), the stroke marks, then the marks that stay last; no `points`
+        std::vector<dlimg_Segmentation> hs{handle_.get()};
+        std::vector<Region> regs{region ? *region : Region(Point{0, 0}, Point{-1, -1})};
+        std::vector<uint8_t*> ptrs{out_mask};
+        auto entry = [&](Region r, uint8_t const* read) {
+            hs.push_back(nullptr);
+            regs.push_back(r);
+            ptrs.push_back(const_cast<uint8_t*>(read));          // a mark's out_masks pointer is only read
+        };
+        for (Stroke const& s : strokes) entry(Region(Point{DLIMG_STROKE_MARK, s.clicks}, Point{s.label, 0}), s.map);
+        if (cleanup) entry(Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}), nullptr);
+        if (matte) entry(Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}), matte->guide);
+        detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), nullptr, &regs.data()->top_left.x, ptrs.data()));
+    }
+    Image scribble(std::vector<Stroke> const& strokes, std::optional<Region> region = std::nullopt,
+                   std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+        Image m(extent(), Channels::mask);
+        scribble(strokes, m.pixels(), region, cleanup, matte);
+        return m;
+    }
+    static void check_strokes(std::vector<Stroke> const& strokes, char const* who) {
+        int clicks = 0;
+        for (Stroke const& s : strokes) {
+            if (!s.map || (s.label != 0 && s.label != 1) || s.clicks < 0 || s.clicks > 8)
+                throw Exception(std::string(who) + ": a stroke has a map, a label of 1 (foreground) or 0 (background) and 0 (the default, 3) .. 8 clicks");
+            clicks += s.clicks ? s.clicks : 3;
+        }
+        if (strokes.empty() || clicks > 8) throw Exception(std::string(who) + ": strokes stand for 1 to 8 clicks in all");
     }
 
     // Snap a selection to the object (addition of this build): the lasso alone is the prompt -- its box, its most interior
@@ -431,7 +489,8 @@ class Segmentation {
     // The same for several segmentations in one batch; prompts of different sizes may share the call.  regions: empty, or one
     // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
     // optional clean-up per prompt; prior: empty, or one optional prior per prompt; lasso: empty, or one optional lasso per
-    // prompt (a prompt takes a prior or a lasso, not both); matte: empty, or one optional matte per prompt.
+    // prompt (a prompt takes a prior or a lasso, not both); matte: empty, or one optional matte per prompt; strokes: empty, or
+    // one list of strokes per prompt (empty: none), whose sampled clicks follow the prompt's clicks.
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
@@ -439,11 +498,12 @@ class Segmentation {
                                                  std::vector<std::optional<MaskCleanup>> const& clean = {},
                                                  std::vector<std::optional<Prior>> const& prior = {},
                                                  std::vector<std::optional<Lasso>> const& lasso = {},
-                                                 std::vector<std::optional<Matte>> const& matte = {}) {
+                                                 std::vector<std::optional<Matte>> const& matte = {},
+                                                 std::vector<std::vector<Stroke>> const& strokes = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
             (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
             (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()) ||
-            (!matte.empty() && matte.size() != segs.size()))
+            (!matte.empty() && matte.size() != segs.size()) || (!strokes.empty() && strokes.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
         for (auto const& p : prior)
             if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
@@ -452,6 +512,8 @@ class Segmentation {
             if (l && (!l->mask || l->what < 0 || l->what > 7 || l->what == DLIMG_LASSO_MASK || l->strength_milli < 0 || l->strength_milli > 100000))
                 throw Exception("compute_mask_batch: a lasso has a mask, a `what` of 0 (all) .. 7 other than 4, and a strength_milli of 0 .. 100000");
         for (auto const& m : matte) check_matte(m, "compute_mask_batch");
+        for (auto const& s : strokes)
+            if (!s.empty()) check_strokes(s, "compute_mask_batch");
         for (auto const& c : clean)
             if (c && (c->max_hole < 0 || c->max_island < 0 || (c->max_hole == 0 && c->max_island == 0)))
                 throw Exception("compute_mask_batch: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
@@ -466,7 +528,7 @@ class Segmentation {
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
             refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value()) ||
                       (!prior.empty() && prior[j].has_value()) || (!lasso.empty() && lasso[j].has_value()) ||
-                      (!matte.empty() && matte[j].has_value());                                                // any continuation entry
+                      (!matte.empty() && matte[j].has_value()) || (!strokes.empty() && !strokes[j].empty());   // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -506,6 +568,13 @@ class Segmentation {
                         regs.push_back(Region(Point{DLIMG_LASSO_MARK, lasso[j]->strength_milli}, Point{lasso[j]->what, 0}));
                     }
                 }
+                if (!strokes.empty())
+                    for (Stroke const& s : strokes[j]) {
+                        hs.push_back(nullptr);           // a stroke mark, behind the clicks given: its point is not read and its
+                        pts.push_back(Point{0, 0});      // out_masks pointer is the map, which the call only reads
+                        ptrs.push_back(const_cast<uint8_t*>(s.map));
+                        regs.push_back(Region(Point{DLIMG_STROKE_MARK, s.clicks}, Point{s.label, 0}));
+                    }
                 if (!clean.empty() && clean[j]) {
                     hs.push_back(nullptr);               // the clean-up mark, the last entry of its prompt: its point is not read
                     pts.push_back(Point{0, 0});
