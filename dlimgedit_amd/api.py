@@ -1207,6 +1207,9 @@ class ext:
                                          _ip, _ip, _ip, _ci, _fp], _ci),
         "dlimg_amd_test_prior_plane": ([_vp, _ci, _ci, _ci, _ci, _ci, _fp, _ip, _ci, _fp], _ci),
         "dlimg_amd_test_lasso_derive": ([_vp, _ci, _ci, _ci, _ci, C.POINTER(C.c_int32), _ip, _ci, _fp], _ci),
+        "dlimg_amd_test_hq_mask_path": ([_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _ci, _ip, _vp, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_upscale_logits": ([_vp, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _ci, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_hq_features_finish": ([_vp, _vp, _vp, _vp, _vp, _ip], _ci),
         "dlimg_amd_bench_attention": ([_ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
         "dlimg_amd_bench_prepost": ([_ci, _ci, _ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], _ci),
         "dlimg_amd_bench_gemm": ([_ci, _ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
@@ -1243,6 +1246,7 @@ class ext:
                "dlimg_amd_test_encoder_state",
                "dlimg_amd_test_neck_conv1x1_ln", "dlimg_amd_test_neck_conv3x3_ln", "dlimg_amd_test_mask_cleanup",
                "dlimg_amd_test_grid_kernels", "dlimg_amd_test_prior_plane", "dlimg_amd_test_lasso_derive",
+               "dlimg_amd_test_hq_mask_path", "dlimg_amd_test_upscale_logits", "dlimg_amd_test_hq_features_finish",
                "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps", "dlimg_amd_test_gemm_tile_shape")
@@ -1704,6 +1708,69 @@ class ext:
                                                          record.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ok), int(time_iters),
                                                          C.byref(ms)))
         return (record, bool(ok.value)) if time_iters <= 0 else (record, bool(ok.value), float(ms.value))
+
+    @classmethod
+    def test_hq_mask_path(cls, U, weights, eps: float, features, feat_index, hyper_hq, logits_in=None, want_h: bool = True,
+                          prompts: Optional[int] = None):
+        """k::hq_mask_path alone (dlimg_amd_test_hq_mask_path), ONE launcher call on host operands with guard bytes around every
+        device buffer.  U (P, 256, 256, 32) float16; weights = (conv1_w (9, 64, 32) f16, conv1_b, ln_w, ln_b (64,), conv2_w
+        (9, 32, 64) f16, conv2_b (32,)); features (n, 256, 256, 32) float32, prompt i taking features[feat_index[i]] (-1: a null
+        pointer); hyper_hq (P, 32); logits_in (P, 4, 256, 256), zeros when omitted.  prompts: the P the launcher is given, when it
+        is not len(U) (the refusals).  -> (logits (P, 4, 256, 256) float32, H (P, 256, 256, 64) float16 or None, guard bytes
+        intact).  A refusal of the launcher raises Error."""
+        f16, f32 = np.float16, np.float32
+        U = np.ascontiguousarray(U, f16)
+        P = len(U) if prompts is None else int(prompts)
+        assert U.shape[1:] == (256, 256, 32)
+        w1, b1, lw, lb, w2, b2 = weights
+        w1, w2 = np.ascontiguousarray(w1, f16), np.ascontiguousarray(w2, f16)
+        b1, lw, lb, b2 = (np.ascontiguousarray(a, f32) for a in (b1, lw, lb, b2))
+        assert w1.shape == (9, 64, 32) and w2.shape == (9, 32, 64) and b1.shape == lw.shape == lb.shape == (64,) and b2.shape == (32,)
+        features = np.ascontiguousarray(features, f32)
+        assert features.ndim == 4 and features.shape[1:] == (256, 256, 32)
+        index = np.ascontiguousarray(feat_index, np.int32)
+        hyper_hq = np.ascontiguousarray(hyper_hq, f32)
+        logits = np.zeros((len(U), 4, 256, 256), f32) if logits_in is None else np.array(logits_in, f32, order="C")
+        assert len(index) >= P and hyper_hq.size >= P * 32 and logits.size >= P * 4 * 65536 and len(U) >= P
+        H = np.zeros((max(P, 0), 256, 256, 64), f16) if want_h else None
+        ok = C.c_int(0)
+        _check_hook(cls._h().dlimg_amd_test_hq_mask_path(
+            U.ctypes.data, P, w1.ctypes.data, b1.ctypes.data, lw.ctypes.data, lb.ctypes.data, w2.ctypes.data, b2.ctypes.data,
+            float(eps), features.ctypes.data, len(features), index.ctypes.data_as(C.POINTER(C.c_int)), hyper_hq.ctypes.data,
+            logits.ctypes.data, cls._ptr(H), C.byref(ok)))
+        return logits, H, bool(ok.value)
+
+    @classmethod
+    def test_upscale_logits(cls, keys_h, W1, b1, ln_w, ln_b, eps: float, W2, b2, hyper, store_u: bool):
+        """k::upscale_logits alone (dlimg_amd_test_upscale_logits), ONE launcher call on host operands with guard bytes around
+        every device buffer.  keys_h (P * 4096, 256) float16, W1 (256, 256) / W2 (128, 64) float16, b1 (256,), ln_w / ln_b (64,),
+        b2 (128,), hyper (P, 4, 32).  -> (logits (P, 4, 256, 256) float32, U (P, 256, 256, 32) float16 or None without store_u,
+        guard bytes intact)."""
+        f16, f32 = np.float16, np.float32
+        keys_h, W1, W2 = (np.ascontiguousarray(a, f16) for a in (keys_h, W1, W2))
+        b1, ln_w, ln_b, b2, hyper = (np.ascontiguousarray(a, f32) for a in (b1, ln_w, ln_b, b2, hyper))
+        P = len(hyper)
+        assert keys_h.shape == (P * 4096, 256) and W1.shape == (256, 256) and W2.shape == (128, 64) and hyper.shape == (P, 4, 32)
+        assert b1.shape == (256,) and ln_w.shape == ln_b.shape == (64,) and b2.shape == (128,)
+        logits = np.zeros((P, 4, 256, 256), f32)
+        U = np.zeros((P, 256, 256, 32), f16) if store_u else None
+        ok = C.c_int(0)
+        _check_hook(cls._h().dlimg_amd_test_upscale_logits(
+            keys_h.ctypes.data, P, W1.ctypes.data, b1.ctypes.data, ln_w.ctypes.data, ln_b.ctypes.data, float(eps), W2.ctypes.data,
+            b2.ctypes.data, hyper.ctypes.data, int(bool(store_u)), logits.ctypes.data, cls._ptr(U), C.byref(ok)))
+        return logits, U, bool(ok.value)
+
+    @classmethod
+    def test_hq_features_finish(cls, vit, emb, b_vit, b_emb):
+        """k::hq_features_finish alone (dlimg_amd_test_hq_features_finish): the two GEMM results (16384, 128) float32 and the two
+        biases (32,) -> (features (256, 256, 32) float32, guard bytes intact)."""
+        vit, emb, b_vit, b_emb = (np.ascontiguousarray(a, np.float32) for a in (vit, emb, b_vit, b_emb))
+        assert vit.shape == emb.shape == (16384, 128) and b_vit.shape == b_emb.shape == (32,)
+        out = np.zeros((256, 256, 32), np.float32)
+        ok = C.c_int(0)
+        _check_hook(cls._h().dlimg_amd_test_hq_features_finish(vit.ctypes.data, emb.ctypes.data, b_vit.ctypes.data, b_emb.ctypes.data,
+                                                               out.ctypes.data, C.byref(ok)))
+        return out, bool(ok.value)
 
     @classmethod
     def test_matte(cls, mask, guide, radius, eps, shortcut: bool = True, time_iters: int = 0):

@@ -43,7 +43,7 @@ EXPORTS_MAP = CSRC / "exports.map"
 EXPORTS_TEST_MAP = CSRC / "exports_test.map"
 # test and tuning libraries only
 HOOK_SOURCES = ["test_hooks.cpp", "neck_test_hooks.cpp", "cleanup_test_hooks.cpp", "grid_test_hooks.cpp", "prior_test_hooks.cpp",
-                "lasso_test_hooks.cpp"]
+                "lasso_test_hooks.cpp", "hq_test_hooks.cpp"]
 # its own library (and the tuning library), with a version script of its own
 SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp"]
 MATTE_HOOKS_MAP = CSRC / "matte_hooks_exports.map"

@@ -228,20 +228,24 @@ void hq_features_finish(const float* vit, const float* emb, const float* b_vit, 
     hipLaunchKernelGGL(hq_finish_kernel, dim3(RES * RES * 8 / 256), dim3(256), 0, s, a);
 }
 
+bool hq_mask_path_prompts(const float* const* features, int P) {
+    if (P <= 0) return false;
+    if (P > kDecoderMaxPrompts) throw_error("hq_mask_path: too many prompts for one launch");
+    for (int i = 0; features && i < P; ++i)
+        if (!features[i] || ((uintptr_t)features[i] & 15)) throw_error("hq_mask_path: every prompt needs its image's 16-byte aligned HQ features");
+    return true;
+}
+
 void hq_mask_path(const half_t* U, const HqMaskWeights& w, float eps, half_t* H, const float* const* features,
                   const float* hyper_hq, float* logits, int P, hipStream_t s) {
-    if (P <= 0) return;
-    if (P > kDecoderMaxPrompts) throw_error("hq_mask_path: too many prompts for one launch");
+    if (!hq_mask_path_prompts(features, P)) return;
     if (!U || !H || !features || !hyper_hq || !logits || !w.conv1_w || !w.conv1_b || !w.ln_w || !w.ln_b || !w.conv2_w || !w.conv2_b)
         throw_error("hq_mask_path: the model has no SAM-HQ group (dec.hq.*)");
     if (((uintptr_t)U | (uintptr_t)H | (uintptr_t)hyper_hq | (uintptr_t)w.conv1_w | (uintptr_t)w.conv1_b | (uintptr_t)w.ln_w |
          (uintptr_t)w.ln_b | (uintptr_t)w.conv2_w | (uintptr_t)w.conv2_b) & 15)
         throw_error("hq_mask_path: operands must be 16-byte aligned");
     HqConv2 b{H, w.conv2_w, w.conv2_b, {}, hyper_hq, logits};
-    for (int i = 0; i < P; ++i) {
-        if (!features[i] || ((uintptr_t)features[i] & 15)) throw_error("hq_mask_path: every prompt needs its image's 16-byte aligned HQ features");
-        b.feat[i] = features[i];
-    }
+    for (int i = 0; i < P; ++i) b.feat[i] = features[i];
     // both kernels stay below the 64 KB every kernel may ask for; the opt-in is made all the same, so that a device that
     // grants less is reported by name instead of by a failed launch
     static k::LdsOptIn opt_in1, opt_in2;

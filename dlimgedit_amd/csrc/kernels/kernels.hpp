@@ -290,8 +290,9 @@ void image_update(const half_t* q, int ldq, const float* tk, const float* tv, co
 // Up-scaling path + mask product in one launch (kernels/decoder_image.hip): logits [P,4,256,256] from the f16 keys, the two
 // transposed convolutions as GEMM weights (W1 [256][256], rows = sub-pixel * 64 + channel; W2 [128][64], rows = sub-pixel * 32
 // + channel), the LayerNorm2d between them and the hyper vectors [P,4,32].
-// u_out (optional, SAM-HQ models): the up-scaled embedding itself, [P][256][256][32] f16 in raster order -- the values the
-// mask product is taken with -- for hq_mask_path.
+// u_out (optional, SAM-HQ models): the up-scaled embedding itself, [P][256][256][32] f16 in raster order, for hq_mask_path:
+// each value is the f16 rounding of the fp32 value the mask product is taken with (the product itself never sees the
+// rounding, and the logits are the same bits with and without u_out).
 void upscale_logits(const half_t* keys_h, const half_t* W1, const float* b1, const float* ln_w, const float* ln_b, float eps,
                     const half_t* W2, const float* b2, const float* hyper, float* logits, int P, hipStream_t, half_t* u_out = nullptr);
 // hyper-network MLPs (4 x 256->256->256->32) and IoU head (256->256->256->4) on the output tokens: the launch finishes the
@@ -318,6 +319,9 @@ struct HqMaskWeights {
 };
 void hq_mask_path(const half_t* U, const HqMaskWeights& w, float eps, half_t* H, const float* const* features,
                   const float* hyper_hq, float* logits, int P, hipStream_t);
+// What hq_mask_path refuses for its prompts alone, which it does before anything else: more than kDecoderMaxPrompts prompts, a
+// prompt whose entry of `features` is null or not 16-byte aligned.  False: P <= 0, the call does nothing.
+bool hq_mask_path_prompts(const float* const* features, int P);
 
 // ---- mask post-processing (K16) --------------------------------------------------------------
 // For each of `count` jobs: logits plane job.src (256x256 f32, device) -> two-stage bilinear

@@ -167,6 +167,30 @@ DLIMG_API int dlimg_amd_test_prior_plane(uint8_t const* mask, int w, int h, int 
  * *ms_out receives the milliseconds of ONE derivation (both launches). */
 DLIMG_API int dlimg_amd_test_lasso_derive(uint8_t const* mask, int w, int h, int pre_w, int pre_h, int32_t* record_out, int* guards_ok,
                                           int iters, float* ms_out);
+/* The SAM-HQ kernels alone, and the kernel that feeds them: one launcher call each on the current device's null stream.  All
+ * operands are HOST memory; every device buffer (operands, results, workspace) has 256 guard bytes of 0xA5 on either side, and
+ * *guards_ok tells whether those are untouched after the launch.  A launcher's refusal arrives as the call's error, and what
+ * it refuses for the prompts alone is refused before anything is allocated.
+ *
+ * k::hq_mask_path.  U [P][256][256][32] f16; conv1_w [9][64][32] and conv2_w [9][32][64] f16 (tap = ky * 3 + kx, then output,
+ * then input channel), conv1_b / ln_w / ln_b [64] and conv2_b [32] fp32; features [n_feat][256][256][32] fp32, prompt i taking
+ * image feat_index[i] (two prompts may share one; -1 passes a null pointer, which the launcher refuses); hyper_hq [P][32].
+ * logits [P][4][256][256]: in and out, the launch adds the HQ plane to all four planes.  out_H (optional): the intermediate
+ * [P][256][256][64] f16 as the launch left it.  P = 0 returns without touching anything. */
+DLIMG_API int dlimg_amd_test_hq_mask_path(uint16_t const* U, int P, uint16_t const* conv1_w, float const* conv1_b, float const* ln_w,
+                                          float const* ln_b, uint16_t const* conv2_w, float const* conv2_b, float eps,
+                                          float const* features, int n_feat, int const* feat_index, float const* hyper_hq,
+                                          float* logits, uint16_t* out_H, int* guards_ok);
+/* k::upscale_logits.  keys_h [P*4096][256] f16; W1 [256][256] f16 (rows = sub-pixel * 64 + channel), b1 [256]; ln_w / ln_b [64];
+ * W2 [128][64] f16 (rows = sub-pixel * 32 + channel), b2 [128]; hyper [P][4][32].  out_logits [P][4][256][256]; store_u != 0
+ * selects the launch that also stores the up-scaled embedding, out_U [P][256][256][32] f16.  P: 1 .. 16. */
+DLIMG_API int dlimg_amd_test_upscale_logits(uint16_t const* keys_h, int P, uint16_t const* W1, float const* b1, float const* ln_w,
+                                            float const* ln_b, float eps, uint16_t const* W2, float const* b2, float const* hyper,
+                                            int store_u, float* out_logits, uint16_t* out_U, int* guards_ok);
+/* k::hq_features_finish.  vit / emb: the two GEMM results [16384][128] fp32 (row = token * 4 + first sub-pixel, column = second
+ * sub-pixel * 32 + channel); b_vit / b_emb [32]; out [256][256][32]. */
+DLIMG_API int dlimg_amd_test_hq_features_finish(float const* vit, float const* emb, float const* b_vit, float const* b_emb, float* out,
+                                                int* guards_ok);
 
 /* ---- kernels alone, timed on device-resident data --------------------------------------------- */
 /* Times the two pixel kernels of the path alone on `batch` (1..16) device-resident 1024x1024 RGBA images / mask requests in

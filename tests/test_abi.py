@@ -69,7 +69,9 @@ def test_only_declared_dlimg_symbols_are_exported(api):
     # dlimg_amd_test_neck_conv3x3_ln (tests/test_gpu_neck.py), dlimg_amd_test_mask_cleanup (tests/test_gpu_cleanup.py),
     # dlimg_amd_test_grid_kernels (tests/test_gpu_grid_kernels.py), dlimg_amd_test_prior_plane (tests/test_gpu_prior_kernel.py),
     # dlimg_amd_test_lasso_derive (tests/test_gpu_lasso_kernel.py)
-    assert len(api.ext.HOOK_EXPORTS) == 30 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
+    # ... and the three kernel-alone hooks of csrc/hq_test_hooks.cpp: dlimg_amd_test_hq_mask_path, dlimg_amd_test_upscale_logits and
+    # dlimg_amd_test_hq_features_finish (tests/test_gpu_hq_kernels.py)
+    assert len(api.ext.HOOK_EXPORTS) == 33 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
     # every hook has its ctypes signature in the one table ext._h() applies, and the library has every name of the table
     assert set(api.ext._HOOK_SIGS) == set(api.ext.HOOK_EXPORTS)
     hooks_lib = api.ext._h()
