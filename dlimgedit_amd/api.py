@@ -180,6 +180,9 @@ def matte_hooks_library() -> C.CDLL:
         _matte_hooks_lib.dlimg_amd_test_stroke_derive.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
                                                                   C.POINTER(C.c_uint64), _ip, C.c_int, C.POINTER(C.c_float)]
         _matte_hooks_lib.dlimg_amd_test_stroke_derive.restype = C.c_int
+        _matte_hooks_lib.dlimg_amd_test_cutout.argtypes = [_vpp, _vpp, _vpp, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int,
+                                                           C.POINTER(C.c_float)]
+        _matte_hooks_lib.dlimg_amd_test_cutout.restype = C.c_int
     return _matte_hooks_lib
 
 
@@ -347,6 +350,9 @@ MATTE_MAX_EPS = 65025        # eps of a matte mark, at most, in squared grey lev
 MATTE_DEFAULT_EPS = 650
 STROKE_MARK = 12             # regions[4 i] of a stroke mark (dlimgedit.h: DLIMG_STROKE_MARK; csrc/stroke_plan.hpp: kStrokeMark)
 STROKE_DEFAULT_CLICKS = 3    # clicks of a stroke mark that says 0
+CUTOUT_MARK = 13             # regions[4 i] of a cut-out mark (dlimgedit.h: DLIMG_CUTOUT_MARK; csrc/cutout_plan.hpp: kCutoutMark)
+CUTOUT_MAX_RADIUS = 32
+CUTOUT_DEFAULT_RADIUS = 16   # radius of a cut-out mark that says 0
 
 
 @dataclass
@@ -382,7 +388,10 @@ class ClickEntries:
     READ as a stroke map: strokes[j] are the (h, w) uint8 maps of prompt j's marks in their order, [] without one.  Each stands
     for `clicks` clicks (0: STROKE_DEFAULT_CLICKS) of its label, derived on the GPU: token_rows and stage_clicks count them (they
     belong to the last stage).  When the prompts of a call have strokes and no clicks, `points` is None and the first foreground
-    click of every prompt is its head's.  Such a prompt is decoded behind the others like a prompt with marks."""
+    click of every prompt is its head's.  Such a prompt is decoded behind the others like a prompt with marks.
+    A cut-out mark is a continuation entry (CUTOUT_MARK, radius, 0, 0) directly behind the matte mark, the last entry of its
+    prompt then, whose out_masks pointer is WRITTEN: cutouts[j] is (radius, the (h, w, 4) uint8 array that receives prompt j's
+    foreground colours and coverage), None without one.  It changes nothing else."""
     heads: list
     points: list
     regions: list
@@ -394,6 +403,7 @@ class ClickEntries:
     lassos: list = field(default_factory=list)
     mattes: list = field(default_factory=list)
     strokes: list = field(default_factory=list)
+    cutouts: list = field(default_factory=list)
 
     def _staged(self, j) -> bool:
         return (j < len(self.stage_clicks) and len(self.stage_clicks[j]) > 1) or (j < len(self.priors) and self.priors[j] is not None) \
@@ -597,6 +607,40 @@ def _checked_matte(matte, n: int) -> list:
     return out
 
 
+def _checked_cutout(cutout, matte: list, n: int) -> list:
+    """`cutout` of a call of n prompts whose checked mattes are `matte` -> per prompt None or (radius, out): cutout is None or
+    one entry per prompt, None, a radius 0 (the library's default, 16) .. 32, or (radius, out) with out the C-contiguous
+    (h, w, 4) uint8 array that receives the RGBA -- a new one without it.  The prompt has a matte whose image has 3 or 4
+    channels; out may be that image itself when it has 4."""
+    if cutout is None:
+        return [None] * n
+    cutout = list(cutout)
+    if len(cutout) != n:
+        raise Error("cutout: None, or one entry (None, a radius or (radius, out)) per prompt")
+    out = []
+    for j, q in enumerate(cutout):
+        if q is None:
+            out.append(None)
+            continue
+        radius, dst = q if isinstance(q, (tuple, list)) and len(q) == 2 else (q, None)
+        if not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= CUTOUT_MAX_RADIUS:
+            raise Error(f"cutout: a cut-out is a radius 0 (the default, {CUTOUT_DEFAULT_RADIUS}) .. {CUTOUT_MAX_RADIUS}, or (radius, out)")
+        if matte[j] is None or matte[j][1] not in (3, 4):
+            raise Error("cutout: a cut-out takes its colours from the prompt's matte image, which has 3 or 4 channels")
+        shape = matte[j][0].shape[:2] + (4,)
+        if dst is None:
+            dst = np.empty(shape, np.uint8)
+        if not isinstance(dst, np.ndarray) or dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.shape != shape:
+            raise Error("cutout: out is a C-contiguous (h, w, 4) uint8 array of the image's extent")
+        out.append((int(radius), dst))
+    return out
+
+
+def _with_cutouts(outs: list, cutouts: list) -> list:
+    """The results of a batch call: the mask of a prompt, (coverage, rgba) of one with a cut-out."""
+    return [o if q is None else (o, q[1]) for o, q in zip(outs, cutouts)]
+
+
 def _checked_strokes(strokes, n: int) -> list:
     """`strokes` of a call of n prompts -> per prompt a list of ((h, w) uint8 array, label, clicks), empty without strokes:
     strokes is None or one entry per prompt, None or a sequence of (map, label, clicks) with label 1 (foreground) or 0
@@ -627,10 +671,10 @@ def _checked_strokes(strokes, n: int) -> list:
 
 
 def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos: Optional[list] = None,
-                    mattes: Optional[list] = None, strokes: Optional[list] = None) -> list:
+                    mattes: Optional[list] = None, strokes: Optional[list] = None, cutouts: Optional[list] = None) -> list:
     """out_masks of a call: the result of a head entry, the prior of a prior mark (priors by index into segs), the selection of
     a lasso mark (lassos likewise), the guide of a matte mark (mattes likewise), the map of a stroke mark (strokes likewise, the
-    marks of a prompt in their order), None otherwise."""
+    marks of a prompt in their order), the destination of a cut-out mark (cutouts likewise), None otherwise."""
     ptrs, head, mark = [], None, 0
     for e, h in enumerate(heads):
         if h is not None:
@@ -657,13 +701,15 @@ def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos:
             if g.shape[:2] != (ext.height, ext.width):
                 raise Error(f"matte: the guide of prompt {head} is {g.shape[1]} x {g.shape[0]}, its image {ext.width} x {ext.height}")
             ptrs.append(g.ctypes.data)
+        elif regs[e][0] == CUTOUT_MARK and head is not None and cutouts is not None and cutouts[head] is not None:
+            ptrs.append(cutouts[head][1].ctypes.data)
         else:
             ptrs.append(None)
     return ptrs
 
 
 def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None,
-                    lasso: Optional[list] = None, matte: Optional[list] = None):
+                    lasso: Optional[list] = None, matte: Optional[list] = None, cutout: Optional[list] = None):
     """The `points` / `regions` form of a batch call with clean-up, grid or prior marks as entry lists: entry i of the caller's,
     then its marks (the prior mark first: it stands directly behind its head).  -> (index into segs or None per entry, [(x, y)]
     or None, [(4 ints)]).  A point prompt gets the empty region (no box); a grid prompt is its head with the empty region and
@@ -710,6 +756,11 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
             if pts is not None:
                 pts.append((0, 0))
             regs.append((MATTE_MARK, matte[i][2], matte[i][3], matte[i][1]))
+        if cutout is not None and cutout[i] is not None:      # directly behind the matte mark
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((CUTOUT_MARK, cutout[i][0], 0, 0))
     return heads, pts, regs
 
 
@@ -722,7 +773,8 @@ def _marked_arrays(segs, heads, pts, regs):
 
 
 def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
-                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None, strokes=None) -> ClickEntries:
+                  prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None, strokes=None,
+                  cutout=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -747,6 +799,9 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     towards the 8; refine_after counts the clicks given.  A prompt with strokes may have NO clicks (clicks[j] None): then no prompt
     of the call has any, every one has a foreground stroke, whose first click is its head's, and the entry lists carry no
     `points`.  Entry lists without strokes are what they were.
+    cutout: None, or per prompt None / a radius / (radius, out) -- a cut-out mark directly behind the prompt's matte mark (which
+    it needs, with an image of 3 or 4 channels): the image's foreground colours under the matte's coverage, as RGBA (see
+    compute_mask_clicks).  Entry lists without cut-outs are what they were.
     Pure host code."""
     n = len(clicks)
     strokes = _checked_strokes(strokes, n)
@@ -760,6 +815,8 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     any_lasso = any(q is not None for q in lasso)
     matte = _checked_matte(matte, n)
     any_matte = any(q is not None for q in matte)
+    cutout = _checked_cutout(cutout, matte, n)
+    any_cutout = any(q is not None for q in cutout)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -774,6 +831,8 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.lassos.append(None if lasso[j] is None else lasso[j][0])
         if any_matte:
             out.mattes.append(None if matte[j] is None else matte[j][0])
+        if any_cutout:
+            out.cutouts.append(cutout[j])
         if grid[j] is not None and lasso[j] is not None:
             raise Error("a grid prompt takes no lasso")
         if grid[j] is not None and matte[j] is not None:
@@ -858,6 +917,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.heads.append(None)
             out.points.append((0, 0))
             out.regions.append((MATTE_MARK, matte[j][2], matte[j][3], matte[j][1]))
+        if cutout[j] is not None:            # directly behind the matte mark
+            out.heads.append(None)
+            out.points.append((0, 0))
+            out.regions.append((CUTOUT_MARK, cutout[j][0], 0, 0))
     if any(clickless):
         # a call without `points`: every prompt takes its head's click from a foreground stroke (dlimgedit.h, DLIMG_STROKE_MARK)
         if not all(clickless):
@@ -958,7 +1021,7 @@ class Segmentation:
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
                             clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0,
                             lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0,
-                            matte=None, strokes=None) -> np.ndarray:
+                            matte=None, strokes=None, cutout=None):
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
@@ -981,8 +1044,14 @@ class Segmentation:
         strokes: a list of (map, label, clicks) -- scribbles over this image, (h, w) uint8 maps whose pixels belong to the stroke
         from 128 on, each standing for `clicks` clicks (1 .. 8, 0: the default 3) of its label (1 foreground, 0 background) that
         are sampled from it on the GPU, behind `clicks` (dlimgedit.h, DLIMG_STROKE_MARK).  With strokes, `clicks` may be None:
-        the first foreground click sampled is then the prompt's first.  See scribble."""
+        the first foreground click sampled is then the prompt's first.  See scribble.
+        cutout (with matte, whose image has 3 or 4 channels): a radius 1 .. 32 pixels (0: the default, 16), or (radius, out) --
+        the call returns (coverage, rgba): rgba an (h, w, 4) uint8 array (`out`, a C-contiguous one of the caller's, which may be
+        the matte's 4-channel image itself: decontaminated in place) whose first three bytes are the FOREGROUND colour of the
+        pixel in the image's channel order -- one pass of Blur-Fusion over that radius on the GPU, in integers, which takes the
+        old background out of the soft edge -- and whose fourth byte is the coverage (dlimgedit.h, DLIMG_CUTOUT_MARK)."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
+                                               cutout=None if cutout is None else [cutout],
                                                strokes=None if strokes is None else [list(strokes)],
                                                out=None if out is None else [out],
                                                refine_after=None if refine_after is None else [refine_after],
@@ -993,7 +1062,7 @@ class Segmentation:
 
     def snap_selection(self, mask: np.ndarray, what: int = 0, strength: int = 0, clicks: Optional[Sequence[Point]] = None,
                        labels: Optional[Sequence[int]] = None, refine_after=None, clean=None,
-                       out: Optional[np.ndarray] = None, matte=None) -> np.ndarray:
+                       out: Optional[np.ndarray] = None, matte=None, cutout=None):
         """Snap a selection to the object: mask, an (h, w) uint8 selection of this image (a dragged lasso, a painted blob; 0 ..
         255 read as coverage), is the prompt -- its box (LASSO_BOX), its most interior point as a foreground click
         (LASSO_CLICK) and the selection itself as SAM's mask input (LASSO_MASK, at `strength` thousandths, 0: the default
@@ -1001,33 +1070,35 @@ class Segmentation:
         the GPU from the 256 x 256 low-res grid (dlimgedit.h, DLIMG_LASSO_MARK).  clicks / labels: further clicks behind the
         derived one (the first of them foreground); refine_after counts these; clean as for compute_mask_clicks.  `out` may be
         `mask` itself: a selection snapped in place.  An empty selection (no low-res cell above half coverage) raises Error.
-        matte: (image, radius, eps) as for compute_mask_clicks -- the snapped selection comes back soft-edged."""
+        matte: (image, radius, eps) as for compute_mask_clicks -- the snapped selection comes back soft-edged.  cutout (with
+        matte): as for compute_mask_clicks -- (coverage, rgba) comes back."""
         if clicks:
             return self.compute_mask_clicks(clicks, labels, None, out, refine_after, clean, lasso=mask, lasso_what=what,
-                                            lasso_strength=strength, matte=matte)
+                                            lasso_strength=strength, matte=matte, cutout=cutout)
         if labels or refine_after is not None:
             raise Error("snap_selection: labels and refine_after go with `clicks`")
         return Segmentation.compute_mask_batch([self], out=None if out is None else [out], clean=None if clean is None else [tuple(clean)],
                                                lasso=[mask], lasso_what=what, lasso_strength=strength,
-                                               matte=None if matte is None else [tuple(matte)])[0]
+                                               matte=None if matte is None else [tuple(matte)],
+                                               cutout=None if cutout is None else [cutout])[0]
 
     def scribble(self, fg: np.ndarray, bg: Optional[np.ndarray] = None, clicks: int = 0, region: Optional[Region] = None,
-                 out: Optional[np.ndarray] = None, clean=None, matte=None) -> np.ndarray:
+                 out: Optional[np.ndarray] = None, clean=None, matte=None, cutout=None):
         """Select by scribbling: fg, an (h, w) uint8 map of a stroke drawn over the object (a pixel belongs to it from 128 on),
         and optionally bg, a stroke over what the selection must leave out, are the prompt -- `clicks` foreground clicks (1 .. 8,
         0: the default 3) spread along fg and as many background clicks along bg, sampled on the GPU from the 256 x 256 low-res
         grid: the cell nearest the stroke's centroid, then farthest-point samples (dlimgedit.h, DLIMG_STROKE_MARK).  region: a
-        box to go with them; clean, matte and out as for compute_mask_clicks.  An empty stroke (no pixel from 128 on) raises
+        box to go with them; clean, matte, cutout and out as for compute_mask_clicks.  An empty stroke (no pixel from 128 on) raises
         Error."""
         marks = [(fg, 1, clicks)] + ([] if bg is None else [(bg, 0, clicks)])
-        return self.compute_mask_clicks(None, None, region, out, None, clean, matte=matte, strokes=marks)
+        return self.compute_mask_clicks(None, None, region, out, None, clean, matte=matte, strokes=marks, cutout=cutout)
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
                            clean=None, grid=None, prior=None, prior_strength=0, lasso=None, lasso_what=0,
-                           lasso_strength=0, matte=None, strokes=None) -> list:
+                           lasso_strength=0, matte=None, strokes=None, cutout=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -1049,7 +1120,9 @@ class Segmentation:
         matte (either form): None, or per prompt None / (image, radius, eps) -- matte marks, see compute_mask_clicks: the mask
         of such a prompt comes back as coverage 0 .. 255.
         strokes (with `clicks`, whose entries may then be None): None, or per prompt None / a list of (map, label, clicks) --
-        stroke marks, see compute_mask_clicks and scribble."""
+        stroke marks, see compute_mask_clicks and scribble.
+        cutout (either form): None, or per prompt None / a radius / (radius, out) -- cut-out marks, see compute_mask_clicks: the
+        result of such a prompt is (coverage, rgba) in place of the mask."""
         if strokes is not None and clicks is None:
             if points is not None:
                 raise Error("compute_mask_batch: strokes go with `clicks` (whose entries may be None), not with `points`")
@@ -1063,18 +1136,19 @@ class Segmentation:
                 raise Error("compute_mask_batch: one list of clicks per segmentation")
             outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
+            cutouts = _checked_cutout(cutout, _checked_matte(matte, len(segs)), len(segs))
             entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength, lasso, lasso_what,
-                                    lasso_strength, matte, strokes)
+                                    lasso_strength, matte, strokes, cutouts)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             priors = _checked_prior(prior, prior_strength, len(segs))
             lassos = _checked_lasso(lasso, lasso_what, lasso_strength, len(segs))
             all_ptrs = _entry_pointers(segs, entries.heads, entries.regions, out_of, priors, lassos, _checked_matte(matte, len(segs)),
-                                       _checked_strokes(strokes, len(segs)))
+                                       _checked_strokes(strokes, len(segs)), cutouts)
             for sel, given in _entry_calls(entries):
                 n, handles, p, r = _entry_arrays(segs, entries, sel, given)
                 ptrs = (C.c_void_p * n)(*[all_ptrs[i] for i in sel])
                 _check(api().get_segmentation_masks(handles, n, p, r, ptrs))
-            return outs
+            return _with_cutouts(outs, cutouts)
         n = len(segs)
         outs = [_mask_image(s.extent()) for s in segs] if out is None else list(out)
         assert len(outs) == n and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
@@ -1083,16 +1157,17 @@ class Segmentation:
         priors = _checked_prior(prior, prior_strength, n)
         lassos = _checked_lasso(lasso, lasso_what, lasso_strength, n)
         mattes = _checked_matte(matte, n)
+        cutouts = _checked_cutout(cutout, mattes, n)
         if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors) \
                 or any(q is not None for q in lassos) or any(q is not None for q in mattes):
             if points is None and regions is None and any(g is None and q is None for g, q in zip(grids, lassos)):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos, mattes)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos, mattes, cutouts)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors,
-                                                     lassos, mattes))
+                                                     lassos, mattes, None, cutouts))
             _check(api().get_segmentation_masks(handles, m, p, r, ptrs))
-            return outs
+            return _with_cutouts(outs, cutouts)
         handles = (C.c_void_p * n)(*[s._handle for s in segs])
         ptrs = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
         p = r = None
@@ -1803,6 +1878,38 @@ class ext:
             msg = lib.dlimg_init().contents.last_error()
             raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
         out = (masks, bool(ok.value), int(launches.value)) if many else (masks[0], bool(ok.value))
+        return out if time_iters <= 0 else out + (float(ms.value),)
+
+    @classmethod
+    def test_cutout(cls, coverage, guide, radius, shortcut: bool = True, time_iters: int = 0):
+        """The cut-out kernels alone (dlimg_amd_test_cutout, lib/libdlimgedit_matte_hooks.so): coverage (h, w) uint8 and guide
+        (h, w, 3) or (h, w, 4) uint8 through ONE k::mask_cutout call on the default device, with guard bytes around the output,
+        the coverage, the guide and the workspace.  -> (rgba uint8 [h, w, 4], guard bytes intact and coverage and guide on the
+        device unchanged).  Lists of equal length for all three arguments: that many jobs in the one call, -> (list of rgba, ok,
+        launches).  guide None reaches the launcher as a null guide.  shortcut False: no block is copied for being covered or
+        bare throughout (same bytes).  time_iters > 0: a further element, the milliseconds of one call (the mean of time_iters
+        repetitions between two events).  A refusal of the launcher raises Error."""
+        many = isinstance(coverage, (list, tuple))
+        given_a = [np.ascontiguousarray(a, np.uint8) for a in (coverage if many else [coverage])]
+        given_g = [None if g is None else np.ascontiguousarray(g, np.uint8) for g in (guide if many else [guide])]
+        radii = [int(r) for r in (radius if many else [radius])]
+        n = len(given_a)
+        assert n == len(given_g) == len(radii) and all(a.ndim == 2 for a in given_a)
+        assert all(g is None or (g.ndim == 3 and g.shape[:2] == a.shape) for a, g in zip(given_a, given_g))
+        covs = [a.copy() for a in given_a]                      # copies: the hook writes back what the device holds afterwards
+        guides = [None if g is None else g.copy() for g in given_g]
+        outs = [np.zeros(a.shape + (4,), np.uint8) for a in covs]
+        ints = lambda v: (C.c_int * n)(*v)
+        ptrs = lambda arrays: (C.c_void_p * n)(*[None if a is None else a.ctypes.data for a in arrays])
+        ok, launches, ms = C.c_int(0), C.c_int(0), C.c_float(0.0)
+        lib = matte_hooks_library()
+        if lib.dlimg_amd_test_cutout(ptrs(covs), ptrs(guides), ptrs(outs), ints([a.shape[1] for a in covs]), ints([a.shape[0] for a in covs]),
+                                     ints([3 if g is None else g.shape[2] for g in guides]), ints(radii), n, int(bool(shortcut)),
+                                     C.byref(ok), C.byref(launches), int(time_iters), C.byref(ms)) != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        same = all((a == b).all() for a, b in zip(covs, given_a)) and all((a == b).all() for a, b in zip(guides, given_g))
+        out = (outs, bool(ok.value) and same, int(launches.value)) if many else (outs[0], bool(ok.value) and same)
         return out if time_iters <= 0 else out + (float(ms.value),)
 
     @classmethod

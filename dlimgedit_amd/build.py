@@ -9,10 +9,11 @@ Three libraries come out of the same sources:
   lib/libdlimgedit_test.so    the product's OBJECTS plus the hook sources (HOOK_SOURCES, csrc/*test_hooks.cpp): additionally
                               exports the dlimg_amd_test_* / dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h)
                               the parity tests and the kernels-alone timing loops call; built by default next to the product
-  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp and csrc/stroke_test_hooks.cpp
-                              (SIDE_HOOK_SOURCES): exports dlimg_init, dlimg_amd_test_matte, the matte kernels alone
-                              (tests/test_gpu_matte_kernel.py), and dlimg_amd_test_stroke_derive, the stroke derivation alone
-                              (tests/test_gpu_stroke_kernel.py).  The test library's list of hooks is held to its length by
+  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp, csrc/stroke_test_hooks.cpp and
+                              csrc/cutout_test_hooks.cpp (SIDE_HOOK_SOURCES): exports dlimg_init, dlimg_amd_test_matte, the matte
+                              kernels alone (tests/test_gpu_matte_kernel.py), dlimg_amd_test_stroke_derive, the stroke derivation
+                              alone (tests/test_gpu_stroke_kernel.py), and dlimg_amd_test_cutout, the cut-out kernels alone
+                              (tests/test_gpu_cutout_kernel.py).  The test library's list of hooks is held to its length by
                               tests/test_abi.py, so these hooks have a library of their own
   lib/libdlimgedit_tuning.so  `--tuning`: everything compiled with -DDLIMG_TUNING -- additionally the ablated kernel variants
                               and in-kernel cycle stamps the scripts under tools/ use (DLIMGEDIT_*_ABLATE, GemmArgs::stamps);
@@ -45,7 +46,7 @@ EXPORTS_TEST_MAP = CSRC / "exports_test.map"
 HOOK_SOURCES = ["test_hooks.cpp", "neck_test_hooks.cpp", "cleanup_test_hooks.cpp", "grid_test_hooks.cpp", "prior_test_hooks.cpp",
                 "lasso_test_hooks.cpp", "hq_test_hooks.cpp"]
 # its own library (and the tuning library), with a version script of its own
-SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp"]
+SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp", "cutout_test_hooks.cpp"]
 MATTE_HOOKS_MAP = CSRC / "matte_hooks_exports.map"
 
 SOURCES = [
@@ -63,6 +64,7 @@ SOURCES = [
     "kernels/mask_lasso.hip",
     "kernels/mask_matte.hip",
     "kernels/mask_stroke.hip",
+    "kernels/mask_cutout.hip",
     "kernels/resize.hip",
     "kernels/objects.hip",
     "resize_tables.cpp",
@@ -92,6 +94,7 @@ EXTRA_FLAGS = {
     "kernels/mask_lasso.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbour all the same (tests/lasso_ref.py)
     "kernels/mask_matte.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbours all the same (tests/matte_ref.py)
     "kernels/mask_stroke.hip": ["-ffp-contract=off"],      # integer throughout; as its neighbours all the same (tests/stroke_ref.py)
+    "kernels/mask_cutout.hip": ["-ffp-contract=off"],      # integer throughout; as its neighbours all the same (tests/cutout_ref.py)
     "kernels/resize.hip": ["-ffp-contract=off"],
     "kernels/objects.hip": ["-ffp-contract=off"],
     "resize_tables.cpp": ["-ffp-contract=off"],

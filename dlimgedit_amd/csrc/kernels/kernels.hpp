@@ -447,5 +447,27 @@ constexpr int kStrokeBallotWords = 256 * 4;
 void stroke_derive(const uint8_t* map, int W, int H, int pre_w, int pre_h, int clicks, unsigned long long* ballots, int32_t* record,
                    hipStream_t);
 
+// ---- cut-out marks (K23, kernels/mask_cutout.hip) ---------------------------------------------
+// A matte's foreground colours as RGBA: one pass of Forte's Blur-Fusion in integers (tests/cutout_ref.py restates it in numpy).
+// coverage a [H][W] u8, guide [H][W][c] u8 tightly packed, c = 3 or 4 (a fourth channel is ignored), out [H][W][4] u8.  I_c is
+// channel c of the guide (c = 0, 1, 2); win(x, y) the (2 r + 1)^2 square around the pixel clipped to the image, N its pixel
+// count; fdiv is floor division.
+//   sums over win(x, y):  S_a, S_I, S_Ia = sum I_c a;      S_b = 255 N - S_a      S_Ib = 255 S_I - S_Ia
+//     Fh = fdiv(512 S_Ia + S_a, 2 S_a) if S_a > 0 else 256 I_c(x, y)        (the a-weighted mean of the window, in 1/256 levels)
+//     Bh = fdiv(512 S_Ib + S_b, 2 S_b) if S_b > 0 else 256 I_c(x, y)        (the (255 - a)-weighted one)
+//     num = 65025 Fh + a (65280 I_c - a Fh - (255 - a) Bh)                   D = 65025 * 256
+//     out_c = clamp(fdiv(2 num + D, 2 D), 0, 255)                            out_3 = a
+// Where a == 255 the pixel keeps its colour; where S_a == 0 too; a constant image stays constant.  radius 1 .. 32.  The kernels
+// read coverage and guide and never write them; out is neither.  out, and a guide of 4 channels, are aligned to 4 bytes: one
+// 4-byte store per pixel, one 4-byte load.  Jobs of one call may differ in size.  Refused before anything is launched: what
+// mask_matte refuses, channels other than 3 or 4, a pointer not so aligned.  Stream-ordered, no host synchronisation, no global
+// atomics: two launches per 16 jobs.  workspace: mask_cutout_workspace_bytes(jobs, count) bytes of device memory (4 per 64 x 64
+// cell), contents irrelevant before and after.  shortcut = false: the blocks whose coverage is 0, or 255, over their halo --
+// whose output is the guide's colours under that alpha -- are computed like any other (measurements and tests; same bytes).
+struct CutoutJob { const uint8_t* coverage; const uint8_t* guide; uint8_t* out; int w, h, channels, radius; };
+size_t mask_cutout_workspace_bytes(const CutoutJob* jobs, int count);
+int mask_cutout_launches(const CutoutJob* jobs, int count);          // kernel launches mask_cutout makes for these jobs
+void mask_cutout(const CutoutJob* jobs_host, int count, void* workspace, hipStream_t, bool shortcut = true);
+
 }  // namespace k
 }  // namespace dlimg

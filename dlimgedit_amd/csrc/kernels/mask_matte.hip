@@ -21,15 +21,18 @@
 //
 // Widths: a column sum of G p over 65 rows is at most 65 * 255^2 < 2^23, the prefix over 256 columns of G^2 < 2^31; sums are
 // unsigned, so even a wrapped prefix would leave the difference exact.  A fits 23 bits, B 31; the column sums of K2 are 64 bits.
-#include "device_common.hpp"
+#include "box_window.hpp"
 #include "kernels.hpp"
 
 namespace dlimg {
 namespace {
 
-constexpr int BLOCK = 256;
-constexpr int BAND = 128;
-constexpr int CELL = 64;
+using boxwin::BAND;        // the strips, bands, cells and scan mask_cutout.hip has too
+using boxwin::BLOCK;
+using boxwin::CELL;
+using boxwin::block_scan;
+using boxwin::cell_extremes;
+using boxwin::uniform_over;
 constexpr int MAX_JOBS = 16;
 constexpr int F = 16;
 constexpr int MAX_RADIUS = 32, MAX_EPS = 65025;
@@ -79,86 +82,8 @@ DLIMG_DEVICE i64 floor_div(i64 n, i64 d) {
 }
 
 __global__ __launch_bounds__(BLOCK) void matte_cells_kernel(PassPack pack) {
-    __shared__ int s_lo, s_hi;
     const PassJob job = pack.j[job_of_cell(pack, (int)blockIdx.x)];
-    const int cell = (int)blockIdx.x - job.cell_begin;
-    const int x0 = (cell % job.cells_x) * CELL, y0 = (cell / job.cells_x) * CELL;
-    const int t = (int)threadIdx.x;
-    if (t == 0) {
-        s_lo = 255;
-        s_hi = 0;
-    }
-    __syncthreads();
-    int lo = 255, hi = 0;
-    const int x = x0 + (t & 63);
-    if (x < job.w)
-        for (int y = y0 + (t >> 6); y < y0 + CELL && y < job.h; y += BLOCK / 64) {
-            const int v = job.mask[(size_t)y * job.w + x];
-            lo = v < lo ? v : lo;
-            hi = v > hi ? v : hi;
-        }
-    atomicMin(&s_lo, lo);
-    atomicMax(&s_hi, hi);
-    __syncthreads();
-    if (t == 0) job.cells[cell] = s_lo | (s_hi << 8);
-}
-
-// Whether the mask is one value over the pixels [xa, xb] x [ya, yb] (clipped to the image), by the cells that touch them; the
-// value in *value.  Every thread of the block calls it and gets the same answer.
-DLIMG_DEVICE bool uniform_over(PassJob const& job, int xa, int xb, int ya, int yb, int* value) {
-    __shared__ int u_lo, u_hi;
-    const int t = (int)threadIdx.x;
-    if (t == 0) {
-        u_lo = 255;
-        u_hi = 0;
-    }
-    __syncthreads();
-    xa = xa < 0 ? 0 : xa;
-    ya = ya < 0 ? 0 : ya;
-    xb = xb > job.w - 1 ? job.w - 1 : xb;
-    yb = yb > job.h - 1 ? job.h - 1 : yb;
-    const int cx0 = xa / CELL, cx1 = xb / CELL, cy0 = ya / CELL, cy1 = yb / CELL;
-    const int nx = cx1 - cx0 + 1, n = nx * (cy1 - cy0 + 1);
-    int lo = 255, hi = 0;
-    for (int i = t; i < n; i += BLOCK) {
-        const int c = job.cells[(cy0 + i / nx) * job.cells_x + cx0 + i % nx];
-        lo = (c & 255) < lo ? (c & 255) : lo;
-        hi = (c >> 8) > hi ? (c >> 8) : hi;
-    }
-    if (t < n) {
-        atomicMin(&u_lo, lo);
-        atomicMax(&u_hi, hi);
-    }
-    __syncthreads();
-    *value = u_lo;
-    return u_lo == u_hi;
-}
-
-// Inclusive scan of one value per thread over the block: prefix[t + 1] = v(0) + .. + v(t), prefix[0] = 0.  The caller places a
-// __syncthreads() between this and its reads of prefix; totals and prefix alternate between two copies from row to row, so no
-// third barrier is needed.
-template <typename T, int K>
-DLIMG_DEVICE void block_scan(T (&v)[K], T (*prefix)[BLOCK + 1], T (*totals)[K]) {
-    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const T up = __shfl_up(v[k], d, 64);
-            if (lane >= d) v[k] += up;
-        }
-    }
-    if (lane == 63)
-#pragma unroll
-        for (int k = 0; k < K; ++k) totals[wave][k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        T base = 0;
-        for (int i = 0; i < wave; ++i) base += totals[i][k];
-        prefix[k][t + 1] = v[k] + base;
-        if (t == 0) prefix[k][0] = 0;
-    }
+    cell_extremes(job.mask, job.w, job.h, job.cells_x, (int)blockIdx.x - job.cell_begin, job.cells);
 }
 
 __global__ __launch_bounds__(BLOCK) void matte_ab_kernel(PassPack pack) {

@@ -14,6 +14,8 @@ constexpr double kLogitBytes = 256.0 * 256.0 * 4.0;     // what the kernel reads
 constexpr double kCleanBytesPerPixelAndPass = 2 * 1 + 2 * 4 + 4 + 4 * 4 + 1;     // k::mask_cleanup, see MaskTransport::run
 // k::mask_matte, no block uniform: the mask read twice (cells, pass 1) and written, A and B written and read
 constexpr double kMatteBytesPerPixel = 2 * 1 + 1 + 2 * 2 * 4;
+// k::mask_cutout, no block uniform: the coverage read twice (cells, sums), the RGBA written; the guide's channels on top
+constexpr double kCutoutBytesPerPixel = 2 * 1 + 4;
 
 // Direct xGMI copies between two GPUs need peer access switched on once per direction (without it the runtime stages
 // the copy through host memory: still correct, slower).  Failures are not errors: the copy falls back by itself.
@@ -108,6 +110,7 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
     uint8_t* const dev = slot.dev.get();
     uint8_t* const pin = static_cast<uint8_t*>(slot.pin.get());
     uint8_t* const staging = p.mode == MaskMode::direct ? pin : dev;
+    slot.cutout_dst = slot.cutout_staged_for = nullptr;
     slot.kernel_jobs.assign(jobs, jobs + count);
     for (int i = 0; i < count; ++i)
         if (p.kernel_dst[i] != kCallersPointer) slot.kernel_jobs[i].dst = staging + p.kernel_dst[i];
@@ -145,6 +148,7 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
         }
     }
     HIP_CHECK(hipEventRecord(slot.done, stream_));
+    slot.cutout_dst = slot.cutout_staged_for;
 }
 
 // The clean-up of the masks of launch step `s`, behind its post-processing launch: in place where the launch wrote them, device
@@ -188,6 +192,31 @@ void MaskTransport::run_matte(MaskSlot& slot, MaskStep const& s, MatteRequest co
     clock_.timed(ST_POST, bytes, [&] { k::mask_matte(slot.matte_jobs.data(), n, slot.matte_workspace.get(), stream_); },
                  clock_.profiling() ? k::mask_matte_launches(slot.matte_jobs.data(), n) : 1);
     HIP_CHECK(hipGetLastError());        // a launch that was not taken is reported here, not by the copy behind it
+    for (int i = s.first; i < s.first + s.count; ++i)
+        if (matte[i].any() && matte[i].cutout.any()) run_cutout(slot, slot.kernel_jobs[i], matte[i]);
+}
+
+// The cut-out of one mask behind its matte: the coverage read where the matte left it, the RGBA written to the slot's own buffer
+// and sent on its way by one copy command.  A request holds one at most (a prompt with a matte is a chunk of its own).
+void MaskTransport::run_cutout(MaskSlot& slot, k::PostJob const& j, MatteRequest const& m) {
+    DLIMG_ASSERT(slot.cutout_staged_for == nullptr && slot.plan.mode != MaskMode::direct);
+    roctx::Range range("dlimg.mask_cutout");
+    const size_t pixels = (size_t)j.out_w * j.out_h, bytes = pixels * 4;
+    slot.cutout_dev.reserve(bytes);
+    const k::CutoutJob job{j.dst, m.guide, slot.cutout_dev.get(), j.out_w, j.out_h, m.channels, m.cutout.radius};
+    slot.cutout_workspace.reserve(k::mask_cutout_workspace_bytes(&job, 1));
+    clock_.timed(ST_POST, (kCutoutBytesPerPixel + m.channels) * (double)pixels,
+                 [&] { k::mask_cutout(&job, 1, slot.cutout_workspace.get(), stream_); }, clock_.profiling() ? k::mask_cutout_launches(&job, 1) : 1);
+    HIP_CHECK(hipGetLastError());
+    // pinned image memory of the library: the copy command writes it; anything else goes through staging, and finish() copies
+    uint8_t* to = m.cutout.dst;
+    if (!image_memory_is_pinned(to, bytes)) {
+        slot.cutout_pin.reserve(bytes);
+        to = static_cast<uint8_t*>(slot.cutout_pin.get());
+        slot.cutout_staged_for = m.cutout.dst;
+        slot.cutout_bytes = bytes;
+    }
+    HIP_CHECK(hipMemcpyAsync(to, slot.cutout_dev.get(), bytes, hipMemcpyDeviceToHost, stream_));
 }
 
 void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean,
@@ -235,6 +264,8 @@ void MaskTransport::finish(MaskSlot& slot, k::PostJob const* jobs, int count, fl
         begin = p.piece_end[i];
     }
     HIP_CHECK(hipEventSynchronize(slot.done));
+    if (slot.cutout_dst) std::memcpy(slot.cutout_dst, slot.cutout_pin.get(), slot.cutout_bytes);
+    slot.cutout_dst = nullptr;
     const auto t1 = std::chrono::steady_clock::now();
     if (iou_out && iou_count > 0) std::memcpy(iou_out, pin + p.iou_offset, (size_t)iou_count * sizeof(float));
     if (trace)

@@ -16,6 +16,12 @@
 //                                            behind the post-processing launch and behind k::mask_cleanup when both are asked
 //                                            for, in place in the slot's device buffer, before any copy or event.  The guide
 //                                            is device memory of the lane (SamModel::matte_guide), valid in stream order
+//   cut-out (MatteRequest::cutout)           optional, of a mask with a matte (cutout_plan.hpp; kernels.hpp K23; a null
+//                                            destination: none): k::mask_cutout runs behind the matte, reads the coverage where
+//                                            it lies and the guide, and writes the RGBA to a buffer of the slot's; one copy
+//                                            command takes that to the destination when it is pinned image memory of the
+//                                            library, else to pinned staging of the slot's from which finish() copies it -- all
+//                                            in front of slot.done, so a cut-out costs no wait of its own
 //   paint (enqueue, enqueue_device)          optional: the request is ONE job whose bytes are a label map (grid_plan.hpp,
 //                                            kernels.hpp K18) -- the launch step runs k::grid_paint over the lane's grid store
 //                                            in place of the post-processing kernel; planning, staging, copies and events are
@@ -41,10 +47,18 @@ struct GridPaint {
     k::GridKept kept{};
 };
 
+// What a cut-out mark asks of a mask with a matte: where the RGBA goes, and the mark's radius.
+struct CutoutRequest {
+    uint8_t* dst = nullptr;                 // HOST memory, [out_h][out_w][4]; null: no cut-out
+    int radius = 0;
+    bool any() const { return dst != nullptr; }
+};
+
 // What a matte mark asks of one mask of a request: the guide where the lane uploaded it, and the mark's ints.
 struct MatteRequest {
     uint8_t const* guide = nullptr;         // device memory, [out_h][out_w][channels]; null: the mask is delivered as it is
     int channels = 0, radius = 0, eps = 0;
+    CutoutRequest cutout{};                 // the cut-out mark behind the matte mark, if any
     bool any() const { return guide != nullptr; }
 };
 
@@ -60,6 +74,12 @@ struct MaskSlot {
     DeviceBuffer<uint8_t> clean_workspace;  // labels and areas of k::mask_cleanup, pooled with the slot like `dev`
     std::vector<k::MatteJob> matte_jobs;    // the masks of the request that get a soft edge, where the kernel wrote them
     DeviceBuffer<uint8_t> matte_workspace;  // the A and B planes and the cells of k::mask_matte, pooled with the slot like `dev`
+    DeviceBuffer<uint8_t> cutout_dev;       // the RGBA of the request's cut-out, 4 bytes per pixel, and the cells of k::mask_cutout:
+    DeviceBuffer<uint8_t> cutout_workspace; // pooled with the slot likewise
+    PinnedBuffer cutout_pin;                // its staging when the destination is not pinned; finish() copies cutout_bytes from
+    uint8_t* cutout_dst = nullptr;          // here to cutout_dst (null: nothing to copy); set once slot.done is recorded, from
+    uint8_t* cutout_staged_for = nullptr;   // what run_cutout noted: a request that failed half-way delivers no RGBA
+    size_t cutout_bytes = 0;
 };
 
 class MaskTransport {
@@ -85,6 +105,7 @@ class MaskTransport {
              GridPaint const* paint, MatteRequest const* matte = nullptr);
     void run_cleanup(MaskSlot& slot, MaskStep const& step, CleanSpec const* clean);
     void run_matte(MaskSlot& slot, MaskStep const& step, MatteRequest const* matte);
+    void run_cutout(MaskSlot& slot, k::PostJob const& job, MatteRequest const& matte);
 
     int device_;
     hipStream_t stream_;

@@ -1,5 +1,6 @@
 #include "segmentation.hpp"
 
+#include "cutout_plan.hpp"
 #include "grid_plan.hpp"
 #include "lasso_plan.hpp"
 #include "matte_plan.hpp"
@@ -52,6 +53,8 @@ struct BatchPrompts {
     std::vector<MatteSpec> matte;      // [prompt]: what its matte mark says (matte_plan.hpp; nothing without one)
     std::vector<uint8_t const*> matte_guide;   // [prompt]: the guide, out_masks[] of the mark's entry (null without one)
     bool any_matte = false;
+    std::vector<CutoutSpec> cutout;    // [prompt]: what its cut-out mark says (cutout_plan.hpp; nothing without one)
+    std::vector<uint8_t*> cutout_dst;  // [prompt]: where its RGBA goes, out_masks[] of the mark's entry (null without one)
     std::vector<std::vector<StrokeSpec>> strokes;      // [prompt]: its stroke marks (stroke_plan.hpp; none without one); its packed
                                                        // points are written once their clicks are derived (decode_batch_on)
     std::vector<std::vector<uint8_t const*>> stroke_map;       // [prompt][mark]: the map, out_masks[] of the mark's entry
@@ -74,19 +77,24 @@ constexpr int kPromptChunk = 8;          // prompts of one decode of a batch cal
 // out_masks: the call's per-entry pointers, which a prior mark's prior is read from; null: the device form, which has none
 BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, int const* points, int const* regions,
                                 uint8_t* const* out_masks) {
-    std::vector<char> has_handle(count), has_pointer(count);
+    std::vector<char> has_handle(count), has_pointer(count), same_as_head(count);
     SegmentationImpl const* any = nullptr;
-    for (int i = 0; i < count; ++i) {
+    for (int i = 0, head = -1; i < count; ++i) {
         has_handle[i] = segs[i] != nullptr;
         has_pointer[i] = out_masks && out_masks[i] != nullptr;
+        if (has_handle[i]) head = i;
+        same_as_head[i] = has_pointer[i] && head >= 0 && head != i && out_masks[i] == out_masks[head];
         if (!any) any = segs[i];
     }
     BatchPrompts b;
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        StrokePlannedPrompts with_strokes = plan_stroke_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
-                                                                /*device_form*/ out_masks == nullptr);
+        CutoutPlannedPrompts with_cutouts = plan_cutout_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+                                                                /*device_form*/ out_masks == nullptr, same_as_head);
+        b.cutout = std::move(with_cutouts.cutout);
+        for (CutoutSpec const& c : b.cutout) b.cutout_dst.push_back(c.any() ? out_masks[c.entry] : nullptr);
+        StrokePlannedPrompts& with_strokes = with_cutouts.inner;
         b.strokes = std::move(with_strokes.strokes);
         for (std::vector<StrokeSpec> const& marks : b.strokes) {
             b.stroke_map.emplace_back();
@@ -625,7 +633,8 @@ struct DeviceMasks {
 // order on one lane's stream, each taking the logits of the one before it as its mask input, and only the last one is
 // post-processed.  A prompt with a clean-up mark has its mask cleaned on the GPU behind the post-processing (the mask of the
 // last stage only; the logits fed back between stages are untouched).  A prompt with a matte mark has its mask -- the cleaned
-// one when it has both -- turned into a coverage on the GPU behind that, guided by the image the mark brought.
+// one when it has both -- turned into a coverage on the GPU behind that, guided by the image the mark brought.  A cut-out mark
+// behind the matte mark has that image's foreground colours estimated behind that, and delivered beside the coverage.
 template <typename Sink>
 void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
                                        int const* regions, Sink const& sink) {
@@ -685,8 +694,9 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 matte = MatteRequest{};
                 if (batch.matte[j].any()) {
                     MatteSpec const& m = batch.matte[j];
+                    // (its cut-out, if any: the destination may be the guide itself, whose bytes are taken here)
                     matte = MatteRequest{model.matte_guide(batch.matte_guide[j], rs.original.width, rs.original.height, m.channels), m.channels,
-                                         m.radius, m.eps};
+                                         m.radius, m.eps, CutoutRequest{batch.cutout_dst[j], batch.cutout[j].radius}};
                 }
                 if (!batch.strokes[j].empty()) {
                     // stroke marks: every map of the prompt uploaded and derived back to back, the call waits for the lane's

@@ -159,7 +159,10 @@ typedef struct dlimg_Api {
      * guide; the prompt's mask is then delivered as coverage 0 .. 255.
      * Stroke marks (clicks sampled from a scribble): a continuation entry whose four ints are {DLIMG_STROKE_MARK, clicks,
      * label, 0}, wherever a click entry may stand -- see DLIMG_STROKE_MARK below.  Its out_masks[i] is READ too: the stroke map,
-     * from which that many clicks of that label are derived on the GPU. */
+     * from which that many clicks of that label are derived on the GPU.
+     * Cut-out marks (a matte's foreground colours as RGBA): a continuation entry whose four ints are {DLIMG_CUTOUT_MARK,
+     * radius, 0, 0} DIRECTLY BEHIND THE MATTE MARK, the last entry of its prompt then -- see DLIMG_CUTOUT_MARK below.  It is
+     * the one continuation entry whose out_masks[i] is WRITTEN: height * width * 4 bytes. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -302,6 +305,37 @@ typedef struct dlimg_Api {
  * what OTHER prompts of the same call have received by then is unspecified.  The call waits for the GPU once per prompt with
  * stroke marks, however many it has.  A call without stroke marks is read as it always was. */
 #define DLIMG_STROKE_MARK 12
+/* regions[4 i] of a cut-out mark in get_segmentation_masks (slot 14): {DLIMG_CUTOUT_MARK, radius, 0, 0} DIRECTLY BEHIND THE
+ * MATTE MARK OF ITS PROMPT, and then the last entry of the prompt, cuts the object out: inside the soft band a pixel of the
+ * image is a mix of foreground and background colour, and multiplying it by the coverage carries the old background along as a
+ * fringe.  The mark estimates the FOREGROUND colour of every pixel (one pass of Forte's Blur-Fusion) from the matte mark's guide
+ * -- so that mark's channels is 3 or 4 -- and the coverage the prompt delivers.
+ * The mark is neither a click nor a stage; points[i] is not read and it does not count towards the 8 clicks.  out_masks[i] OF
+ * THE MARK IS WRITTEN: it receives height * width * 4 bytes, tightly packed.  Bytes 0 .. 2 of a pixel are the estimated
+ * foreground colour in the channel order of the guide's first three channels (RGBA in gives RGBA out, BGRA in gives BGRA out),
+ * byte 3 is the coverage.  out_masks[head] still receives the coverage, byte for byte what the same prompt delivers without
+ * the cut-out mark.  The pointer may be the guide itself when channels is 4: the image is then decontaminated in place, its
+ * fourth byte replaced by the coverage (the guide is taken before anything is delivered).  In memory from create_image the
+ * result is copied in place by the GPU's copy engine; otherwise it goes through pinned staging of its own size.  The prompt
+ * costs no further wait for the GPU: everything runs in stream order behind the matte.
+ * radius is 1 .. 32 pixels of the image; 0 means 16, a choice and not a measurement.
+ * The definition is integer arithmetic, so the bytes are the same wherever they are computed.  With a the delivered coverage,
+ * I_c channel c of the guide (c = 0, 1, 2), win(x, y) the (2 radius + 1)^2 square around a pixel clipped to the image, N its
+ * pixel count, fdiv floor division:
+ *   S_a, S_I, S_Ia = sums of a, I_c, I_c a over win(x, y)         S_b = 255 N - S_a       S_Ib = 255 S_I - S_Ia
+ *   Fh = fdiv(512 S_Ia + S_a, 2 S_a) if S_a > 0, else 256 I_c(x, y)
+ *   Bh = fdiv(512 S_Ib + S_b, 2 S_b) if S_b > 0, else 256 I_c(x, y)
+ *   num = 65025 Fh + a (65280 I_c - a Fh - (255 - a) Bh)          D = 65025 * 256
+ *   out_c = clamp(fdiv(2 num + D, 2 D), 0, 255)                   out_3 = a
+ * which is within one level of the float64 Blur-Fusion.  Where a == 255 the pixel keeps its colour exactly; a constant image
+ * stays constant; where no pixel of the window is covered the colour is the image's; a fully transparent pixel near the object
+ * carries the neighbouring foreground's colour, which is what straight-alpha compositing and later resampling want.
+ * Refused before anything is launched (the message says "mark" and names the entry): a cut-out mark that is not directly
+ * behind a matte mark, one that is not the last entry of its prompt, a second one on a prompt, a matte mark with channels == 1
+ * in front of it, a NULL pointer, a pointer equal to out_masks[head], radius outside 0 .. 32, non-zero trailing ints, a mark
+ * in front of any head, and dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to write to.  A grid
+ * prompt is refused through its matte mark.  A call without cut-out marks is read as it always was. */
+#define DLIMG_CUTOUT_MARK 13
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

@@ -263,6 +263,17 @@ struct Stroke {
     int clicks = 0;
 };
 
+// A cut-out: the foreground colours of the image under a Matte's coverage, as RGBA (one pass of Blur-Fusion on the GPU, in
+// integers; dlimgedit.h, DLIMG_CUTOUT_MARK), so that the object can be put on another background without a fringe of the old
+// one.  rgba: receives height * width * 4 bytes, tightly packed -- the estimated foreground colour in the order of the guide's
+// first three channels, then the coverage; it may be the Matte's guide itself when that has 4 channels (decontaminated in
+// place).  radius: 1 .. 32 pixels; 0: the library's default, 16.  Needs a Matte of 3 or 4 channels on the same prompt; travels
+// as a cut-out mark of table slot 14 directly behind the matte mark.  The mask the call returns is the coverage as ever.
+struct Cutout {
+    uint8_t* rgba = nullptr;
+    int radius = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -373,28 +384,34 @@ class Segmentation {
     // follow the derived one, and refine_after counts the clicks given here.  With DLIMG_LASSO_BOX there is no `region`.
     // matte: the mask is delivered as coverage 0 .. 255, its edge guided by the image (Matte), behind the clean-up.
     // strokes: scribbles whose sampled clicks follow the clicks given here (Stroke), in the order given; refine_after counts the
-    // clicks given here.  (The last argument, behind matte, so that calls written before it read as they did.)
+    // clicks given here.  (Behind matte, so that calls written before it read as they did.)
+    // cutout: the image's foreground colours under the matte's coverage go to cutout->rgba (Cutout); needs matte.  (The last
+    // argument, for the same reason.)
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
                        std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
                        std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt,
-                       std::optional<Matte> matte = std::nullopt, std::vector<Stroke> const& strokes = {}) const {
+                       std::optional<Matte> matte = std::nullopt, std::vector<Stroke> const& strokes = {},
+                       std::optional<Cutout> cutout = std::nullopt) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
                                             clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
                                             prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{},
                                             lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{},
                                             matte ? std::vector<std::optional<Matte>>{matte} : std::vector<std::optional<Matte>>{},
-                                            strokes.empty() ? std::vector<std::vector<Stroke>>{} : std::vector<std::vector<Stroke>>{strokes})[0]);
+                                            strokes.empty() ? std::vector<std::vector<Stroke>>{} : std::vector<std::vector<Stroke>>{strokes},
+                                            cutout ? std::vector<std::optional<Cutout>>{cutout} : std::vector<std::optional<Cutout>>{})[0]);
     }
 
     // Select by scribbling (addition of this build): the strokes alone are the prompt -- the clicks sampled from them in the
     // order given, the first FOREGROUND one first (so at least one stroke is a foreground stroke), and an optional box.  cleanup
-    // and matte as for compute_mask.  out_mask may be a stroke's map itself.  A stroke without a pixel >= 128 is reported by the
+    // matte and cutout as for compute_mask.  out_mask may be a stroke's map itself.  A stroke without a pixel >= 128 is reported by the
     // library ("the stroke mark's map is empty") and nothing is delivered.
     void scribble(std::vector<Stroke> const& strokes, uint8_t* out_mask, std::optional<Region> region = std::nullopt,
-                  std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+                  std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
+                  std::optional<Cutout> cutout = std::nullopt) const {
         if (!out_mask) throw Exception("scribble: the result has a place to go");
         check_strokes(strokes, "scribble");
         check_matte(matte, "scribble");
+        check_cutout(cutout, matte, "scribble");
         if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
             throw Exception("scribble: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         if (std::none_of(strokes.begin(), strokes.end(), [](Stroke const& s) { return s.label == 1; }))
@@ -411,12 +428,14 @@ class Segmentation {
         for (Stroke const& s : strokes) entry(Region(Point{DLIMG_STROKE_MARK, s.clicks}, Point{s.label, 0}), s.map);
         if (cleanup) entry(Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}), nullptr);
         if (matte) entry(Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}), matte->guide);
+        if (cutout) entry(Region(Point{DLIMG_CUTOUT_MARK, cutout->radius}, Point{0, 0}), cutout->rgba);     // (this one is written)
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), nullptr, &regs.data()->top_left.x, ptrs.data()));
     }
     Image scribble(std::vector<Stroke> const& strokes, std::optional<Region> region = std::nullopt,
-                   std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+                   std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
+                   std::optional<Cutout> cutout = std::nullopt) const {
         Image m(extent(), Channels::mask);
-        scribble(strokes, m.pixels(), region, cleanup, matte);
+        scribble(strokes, m.pixels(), region, cleanup, matte, cutout);
         return m;
     }
     static void check_strokes(std::vector<Stroke> const& strokes, char const* who) {
@@ -431,12 +450,14 @@ class Segmentation {
 
     // Snap a selection to the object (addition of this build): the lasso alone is the prompt -- its box, its most interior
     // point as a foreground click, and the selection itself as the mask input, whichever `what` names (Lasso) -- or the lasso
-    // and further clicks behind the derived one.  refine_after, cleanup and matte as for compute_mask.  out_mask may be
+    // and further clicks behind the derived one.  refine_after, cleanup, matte and cutout as for compute_mask.  out_mask may be
     // lasso.mask itself: a selection snapped in place.
     void snap(Lasso const& lasso, uint8_t* out_mask, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
-              std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+              std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
+              std::optional<Cutout> cutout = std::nullopt) const {
         if (!lasso.mask || !out_mask) throw Exception("snap: a lasso has a mask, and the result a place to go");
         check_matte(matte, "snap");
+        check_cutout(cutout, matte, "snap");
         if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
             throw Exception("snap: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         if (clicks.size() > 8) throw Exception("snap: a prompt takes at most 8 clicks");
@@ -466,19 +487,28 @@ class Segmentation {
             entry(Point{0, 0}, Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}));
             ptrs.back() = const_cast<uint8_t*>(matte->guide);      // the mark's out_masks pointer is the guide, which the call only reads
         }
+        if (cutout) {
+            entry(Point{0, 0}, Region(Point{DLIMG_CUTOUT_MARK, cutout->radius}, Point{0, 0}));
+            ptrs.back() = cutout->rgba;                            // the one mark whose out_masks pointer is written
+        }
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), clicks.empty() ? nullptr : &pts.data()->x,
                                                    &regs.data()->top_left.x, ptrs.data()));
     }
     Image snap(Lasso const& lasso, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
-               std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt) const {
+               std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
+               std::optional<Cutout> cutout = std::nullopt) const {
         Image m(extent(), Channels::mask);
-        snap(lasso, m.pixels(), clicks, refine_after, cleanup, matte);
+        snap(lasso, m.pixels(), clicks, refine_after, cleanup, matte, cutout);
         return m;
     }
     static void check_matte(std::optional<Matte> const& m, char const* who) {
         if (m && (!m->guide || m->radius < 1 || m->radius > 32 || m->eps < 0 || m->eps > 65025 ||
                   (m->channels != 1 && m->channels != 3 && m->channels != 4)))
             throw Exception(std::string(who) + ": a matte has a guide, a radius of 1 .. 32, an eps of 0 (the default) .. 65025 and 1, 3 or 4 channels");
+    }
+    static void check_cutout(std::optional<Cutout> const& c, std::optional<Matte> const& m, char const* who) {
+        if (c && (!c->rgba || c->radius < 0 || c->radius > 32 || !m || (m->channels != 3 && m->channels != 4)))
+            throw Exception(std::string(who) + ": a cut-out has a place for its RGBA, a radius of 0 (the default) .. 32, and a matte of 3 or 4 channels on its prompt");
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -490,7 +520,8 @@ class Segmentation {
     // optional box per prompt; refine_after: empty, or one list of marks per prompt (empty: none); clean: empty, or one
     // optional clean-up per prompt; prior: empty, or one optional prior per prompt; lasso: empty, or one optional lasso per
     // prompt (a prompt takes a prior or a lasso, not both); matte: empty, or one optional matte per prompt; strokes: empty, or
-    // one list of strokes per prompt (empty: none), whose sampled clicks follow the prompt's clicks.
+    // one list of strokes per prompt (empty: none), whose sampled clicks follow the prompt's clicks; cutout: empty, or one
+    // optional cut-out per prompt (which then has a matte).
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
@@ -499,11 +530,13 @@ class Segmentation {
                                                  std::vector<std::optional<Prior>> const& prior = {},
                                                  std::vector<std::optional<Lasso>> const& lasso = {},
                                                  std::vector<std::optional<Matte>> const& matte = {},
-                                                 std::vector<std::vector<Stroke>> const& strokes = {}) {
+                                                 std::vector<std::vector<Stroke>> const& strokes = {},
+                                                 std::vector<std::optional<Cutout>> const& cutout = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
             (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
             (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()) ||
-            (!matte.empty() && matte.size() != segs.size()) || (!strokes.empty() && strokes.size() != segs.size()))
+            (!matte.empty() && matte.size() != segs.size()) || (!strokes.empty() && strokes.size() != segs.size()) ||
+            (!cutout.empty() && cutout.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
         for (auto const& p : prior)
             if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
@@ -512,6 +545,8 @@ class Segmentation {
             if (l && (!l->mask || l->what < 0 || l->what > 7 || l->what == DLIMG_LASSO_MASK || l->strength_milli < 0 || l->strength_milli > 100000))
                 throw Exception("compute_mask_batch: a lasso has a mask, a `what` of 0 (all) .. 7 other than 4, and a strength_milli of 0 .. 100000");
         for (auto const& m : matte) check_matte(m, "compute_mask_batch");
+        for (size_t j = 0; j < cutout.size(); ++j)
+            check_cutout(cutout[j], matte.empty() ? std::optional<Matte>{} : matte[j], "compute_mask_batch");
         for (auto const& s : strokes)
             if (!s.empty()) check_strokes(s, "compute_mask_batch");
         for (auto const& c : clean)
@@ -586,6 +621,12 @@ class Segmentation {
                     pts.push_back(Point{0, 0});          // read and its out_masks pointer is the guide, which the call only reads
                     ptrs.push_back(const_cast<uint8_t*>(matte[j]->guide));
                     regs.push_back(Region(Point{DLIMG_MATTE_MARK, matte[j]->radius}, Point{matte[j]->eps, matte[j]->channels}));
+                }
+                if (!cutout.empty() && cutout[j]) {
+                    hs.push_back(nullptr);               // the cut-out mark, directly behind the matte mark: its point is not read
+                    pts.push_back(Point{0, 0});          // and its out_masks pointer is WRITTEN, the RGBA
+                    ptrs.push_back(cutout[j]->rgba);
+                    regs.push_back(Region(Point{DLIMG_CUTOUT_MARK, cutout[j]->radius}, Point{0, 0}));
                 }
             }
             if (hs.empty()) continue;
