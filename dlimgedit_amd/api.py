@@ -1285,6 +1285,9 @@ class ext:
         "dlimg_amd_test_hq_mask_path": ([_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _cf, _vp, _ci, _ip, _vp, _vp, _vp, _ip], _ci),
         "dlimg_amd_test_upscale_logits": ([_vp, _ci, _vp, _vp, _vp, _vp, _cf, _vp, _vp, _vp, _ci, _vp, _vp, _ip], _ci),
         "dlimg_amd_test_hq_features_finish": ([_vp, _vp, _vp, _vp, _vp, _ip], _ci),
+        "dlimg_amd_test_hq_branch": ([_vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp], _ci),
+        "dlimg_amd_test_layernorm_rows": ([_vp, _vp, _vp, _cf, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _ip, _ip], _ci),
+        "dlimg_amd_test_elementwise": ([_ci, _vp, _vp, _vp, C.c_longlong, C.c_longlong, _vp, _vp, _ip], _ci),
         "dlimg_amd_bench_attention": ([_ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
         "dlimg_amd_bench_prepost": ([_ci, _ci, _ci, C.POINTER(C.c_double), C.POINTER(C.c_double)], _ci),
         "dlimg_amd_bench_gemm": ([_ci, _ci, _ci, _ci, _ci, _ci, C.POINTER(C.c_double)], _ci),
@@ -1322,6 +1325,7 @@ class ext:
                "dlimg_amd_test_neck_conv1x1_ln", "dlimg_amd_test_neck_conv3x3_ln", "dlimg_amd_test_mask_cleanup",
                "dlimg_amd_test_grid_kernels", "dlimg_amd_test_prior_plane", "dlimg_amd_test_lasso_derive",
                "dlimg_amd_test_hq_mask_path", "dlimg_amd_test_upscale_logits", "dlimg_amd_test_hq_features_finish",
+               "dlimg_amd_test_hq_branch", "dlimg_amd_test_layernorm_rows", "dlimg_amd_test_elementwise",
                "dlimg_amd_bench_attention",
                "dlimg_amd_bench_prepost", "dlimg_amd_bench_gemm", "dlimg_amd_bench_gemm_streams",
                "dlimg_amd_bench_gemm_stamps", "dlimg_amd_test_gemm_tile_shape")
@@ -1846,6 +1850,82 @@ class ext:
         _check_hook(cls._h().dlimg_amd_test_hq_features_finish(vit.ctypes.data, emb.ctypes.data, b_vit.ctypes.data, b_emb.ctypes.data,
                                                                out.ctypes.data, C.byref(ok)))
         return out, bool(ok.value)
+
+    @classmethod
+    def test_hq_branch(cls, env: "Environment", branch: str, a, batch: Optional[int] = None):
+        """One branch of the SAM-HQ features as the product's encoder runs it (dlimg_amd_test_hq_branch: lane 0, the entry
+        SamModel::encode calls).  branch "vit" (K = the model's embed_dim, C = 256) or "emb" (K = 256, C = 64); a (B * 4096, K)
+        float16, B in 1 .. 2.  -> {"A" (B * 4096, 4 C) float32, "H" (B * 16384, C) float16, "Y" (B * 16384, 128) float32, and the
+        loaded operands "w1" (4 C, K) float16, "b1" (4 C,), "ln_w", "ln_b" (C,), "w2" (128, C) float16, "b2" (128,)}.
+        batch: the B the hook is given when it is not len(a) / 4096 (the refusals).  A refusal raises Error."""
+        f16, f32 = np.float16, np.float32
+        code = {"vit": 0, "emb": 1}.get(branch, branch)
+        a = None if a is None else np.ascontiguousarray(a, f16)
+        B = int(batch) if batch is not None else len(a) // 4096
+        K = cls.model_geometry(env)[0] if code == 0 else 256
+        Cc = 256 if code == 0 else 64
+        assert a is None or (a.ndim == 2 and a.shape[1] == K and len(a) >= min(max(B, 0), 2) * 4096)
+        n = min(max(B, 1), 2) * 4096
+        out = {"A": np.zeros((n, 4 * Cc), f32), "H": np.zeros((n * 4, Cc), f16), "Y": np.zeros((n * 4, 128), f32),
+               "w1": np.zeros((4 * Cc, K), f16), "b1": np.zeros(4 * Cc, f32), "ln_w": np.zeros(Cc, f32), "ln_b": np.zeros(Cc, f32),
+               "w2": np.zeros((128, Cc), f16), "b2": np.zeros(128, f32)}
+        _check_hook(cls._h().dlimg_amd_test_hq_branch(env.handle(), int(code), cls._ptr(a), B,
+                                                      *(out[k].ctypes.data for k in ("A", "H", "Y", "w1", "b1", "ln_w", "ln_b", "w2", "b2"))))
+        return out
+
+    @classmethod
+    def test_layernorm_rows(cls, x, w, b, eps: float, act: int = 0, want_f32: bool = True, want_f16: bool = False,
+                            in_place: bool = False, misalign_x: bool = False, nonfinite: Optional[int] = None,
+                            rows: Optional[int] = None, dim: Optional[int] = None):
+        """k::layernorm alone (dlimg_amd_test_layernorm_rows): ONE launcher call with guard bytes around every device buffer.
+        x (rows, dim) float32; want_f32 / want_f16 choose the results; in_place: the launch gets out_f32 = x; misalign_x: the
+        device x lies 4 bytes behind a 16-byte boundary; nonfinite (None: not asked for): the initial value of the report's int.
+        rows / dim: what the launcher is told when it is not x.shape (the refusals).
+        -> (float32 result or None, float16 result or None, the report's int or None, guard bytes intact).  A refusal raises Error."""
+        x, w, b = (np.ascontiguousarray(v, np.float32) for v in (x, w, b))
+        r = x.shape[0] if rows is None else int(rows)
+        d = x.shape[1] if dim is None else int(dim)
+        assert x.size >= r * d and w.size >= max(d, 1) and b.size >= max(d, 1)
+        o32 = np.zeros((r, d), np.float32) if want_f32 else None
+        o16 = np.zeros((r, d), np.float16) if want_f16 else None
+        flag = None if nonfinite is None else C.c_int(int(nonfinite))
+        ok = C.c_int(0)
+        try:
+            _check_hook(cls._h().dlimg_amd_test_layernorm_rows(x.ctypes.data, w.ctypes.data, b.ctypes.data, float(eps), r, d, int(act),
+                                                               int(bool(in_place)), int(bool(misalign_x)), cls._ptr(o32), cls._ptr(o16),
+                                                               None if flag is None else C.byref(flag), C.byref(ok)))
+        except Error as e:
+            e.nonfinite = None if flag is None else int(flag.value)      # a refusal returns the int as it was found
+            raise
+        return o32, o16, None if flag is None else int(flag.value), bool(ok.value)
+
+    @classmethod
+    def test_elementwise(cls, op: str, a, b=None, b_mod: int = 0, want_f32: bool = False, want_f16: bool = True,
+                         n: Optional[int] = None):
+        """The other row kernels of kernels/elementwise.hip alone (dlimg_amd_test_elementwise), guarded as test_layernorm_rows.
+        "cast_f16": a float32 (n,) -> float16.  "add_cast": a float32 (n,) + b float32 (b_mod,) or None, element i taking
+        b[i % b_mod] -> float32 and / or float16.  "im2col3x3": a float16 (B, 64, 64, C) -> float16 (B * 4096, 9 * C).
+        n / b_mod: what the launcher is told when it is not the arrays' sizes (the refusals).
+        -> (float32 result or None, float16 result or None, guard bytes intact)."""
+        code = {"cast_f16": 0, "add_cast": 1, "im2col3x3": 2}[op]
+        ok = C.c_int(0)
+        if code == 2:
+            a = np.ascontiguousarray(a, np.float16)
+            B, _, _, Cc = a.shape
+            assert a.shape[1:3] == (64, 64)
+            o16 = np.zeros((B * 4096, 9 * Cc), np.float16)
+            _check_hook(cls._h().dlimg_amd_test_elementwise(2, None, a.ctypes.data, None, Cc, B, None, o16.ctypes.data, C.byref(ok)))
+            return None, o16, bool(ok.value)
+        a = np.ascontiguousarray(a, np.float32).ravel()
+        count_ = a.size if n is None else int(n)
+        assert a.size >= count_
+        b = None if b is None else np.ascontiguousarray(b, np.float32).ravel()
+        assert b is None or b.size >= b_mod
+        o32 = np.zeros(count_, np.float32) if (want_f32 and code == 1) else None
+        o16 = np.zeros(count_, np.float16) if (want_f16 or code == 0) else None
+        _check_hook(cls._h().dlimg_amd_test_elementwise(code, a.ctypes.data, None, cls._ptr(b), int(b_mod), count_, cls._ptr(o32),
+                                                        cls._ptr(o16), C.byref(ok)))
+        return o32, o16, bool(ok.value)
 
     @classmethod
     def test_matte(cls, mask, guide, radius, eps, shortcut: bool = True, time_iters: int = 0):

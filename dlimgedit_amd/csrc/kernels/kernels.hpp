@@ -122,8 +122,9 @@ void neck_conv3x3_ln(const half_t* in, int B, const half_t* w, const half_t* zer
 
 // ---- row LayerNorm ---------------------------------------------------------------------------
 // y = (x-mean)/sqrt(var+eps)*w+b over rows of length D (<= 1280); optional GELU; f32 and/or f16 out.
-// x and out_f32 may alias.  nonfinite (optional, D a multiple of 256): an int in memory the kernel can write (pinned host
-// memory) that is set to 1 when a row holds an infinity or a NaN.
+// x and out_f32 may alias.  nonfinite (optional; D a multiple of 256 AND x, w, b, out_f32 16-byte, out_h 8-byte aligned, i.e.
+// the 16-byte kernel: refused otherwise): an int in memory the kernel can write (pinned host memory) that is set to 1 when a
+// row holds an infinity or a NaN; never cleared by the kernel.
 void layernorm(const float* x, const float* w, const float* b, float eps, int rows, int D, int act,
                float* out_f32, half_t* out_h, hipStream_t, int* nonfinite = nullptr);
 
@@ -153,7 +154,8 @@ void resize_preprocess_batch(const ResizeJob* jobs, int count, const float* deco
                              hipStream_t);
 
 // ---- elementwise -----------------------------------------------------------------------------
-// out_h[i] = f16(a[i] + (b ? b[i % b_mod] : 0)); out_f32 likewise (either may be null); n % 4 == 0
+// out_h[i] = f16(a[i] + (b ? b[i % b_mod] : 0)); out_f32 likewise (either may be null); n % 4 == 0 and, with b, b_mod % 4 == 0
+// and b_mod > 0 (refused otherwise); every pointer 16-byte aligned (out_h: 8)
 void add_cast(const float* a, const float* b, size_t b_mod, size_t n, float* out_f32, half_t* out_h, hipStream_t);
 // 3x3 im2col over a [B,64,64,C] f16 map (zero pad 1): out [B*4096, 9*C], column = (ky*3+kx)*C + c
 void im2col3x3(const half_t* in, int B, int C, half_t* out, hipStream_t);

@@ -495,7 +495,7 @@ void SamModel::encode(int batch, float* const* emb_dst) {
                     k::add_cast(x_.get(), nullptr, 0, (size_t)M * D, nullptr, xn_.get(), stream_);
                 });
             }
-            hq_gemm_pair(xn_.get(), D, W.hq_vit1_, W.hq_vit_ln_, W.hq_vit2_, M, hq_vit_.get());
+            hq_branch(HqBranch::vit, xn_.get(), M, hq_vit_.get());
         }
         ++layer_index;
     }
@@ -561,7 +561,7 @@ void SamModel::encode(int batch, float* const* emb_dst) {
     if (W.has_hq()) {
         // the embedding branch of the HQ features, then per image: both branches and their biases, in raster order, behind
         // the embedding in the handle's buffer (or in the lane's workspace when the pass has no handle)
-        hq_gemm_pair(emb_h_.get(), kEmbedDim, W.hq_emb1_, W.hq_emb_ln_, W.hq_emb2_, M, hq_embf_.get());
+        hq_branch(HqBranch::emb, emb_h_.get(), M, hq_embf_.get());
         clock_.timed(ST_ENC_OTHER, (double)batch * kHqFeatureFloats * 12, [&] {
             for (int i = 0; i < batch; ++i) {
                 float* dst = (emb_dst && emb_dst[i]) ? emb_dst[i] + kEmbeddingFloats : hq_feat_.get() + (size_t)i * kHqFeatureFloats;
@@ -584,7 +584,18 @@ void SamModel::encode(int batch, float* const* emb_dst) {
 // positions with a LayerNorm2d + GELU between them, which is a ROW LayerNorm once the first result [M][4 * C] is read as
 // [4 M][C].  a: f16 [M][K]; out: fp32 [4 M][128], row = token * 4 + first sub-pixel, column = second sub-pixel * 32 + channel,
 // without the second convolution's bias (hq_features_finish adds it).
-void SamModel::hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out) {
+SamModel::HqBranchTensors SamModel::hq_tensors(HqBranch which) const {
+    SamWeights const& W = *weights_;
+    if (which == HqBranch::vit) return {W.hq_vit1_, W.hq_vit_ln_, W.hq_vit2_};
+    return {W.hq_emb1_, W.hq_emb_ln_, W.hq_emb2_};
+}
+
+void SamModel::hq_branch(HqBranch which, half_t const* a, int M, float* out) {
+    const HqBranchTensors t = hq_tensors(which);
+    LinearH const& conv1 = t.conv1;
+    NormW const& ln = t.ln;
+    LinearH const& conv2 = t.conv2;
+    const int K = conv1.in;                      // the encoder's width (ViT branch) or the embedding's 256 channels
     const int C = conv1.out / 4;                 // channels between the two convolutions: 256 (ViT branch) or 64 (embedding branch)
     k::GemmArgs g;
     g.A = a; g.lda = K; g.W = conv1.w.get(); g.ldw = K; g.bias = conv1.b.get();
@@ -597,6 +608,20 @@ void SamModel::hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW 
     g.A = hq_h_.get(); g.lda = C; g.W = conv2.w.get(); g.ldw = C;
     g.out_f32 = out; g.ldc32 = conv2.out; g.M = 4 * M; g.N = conv2.out; g.K = C;
     gemm(g);
+}
+
+// Diagnostic: one branch alone on a caller's device input, through the entry encode() calls.
+SamModel::HqBranchView SamModel::run_hq_branch(HqBranch which, half_t const* a, int batch) {
+    SamWeights const& W = *weights_;
+    DLIMG_ASSERT(W.has_hq() && a != nullptr && batch >= 1 && batch <= 2);
+    reserve_encoder(batch);
+    alone_ = batch == 1 && shared_gpu_ && board_ && board_->others_idle(lane_index_);     // what encode() tells the GEMM planner
+    float* out = which == HqBranch::vit ? hq_vit_.get() : hq_embf_.get();       // the workspace encode() gives the branch
+    hq_branch(which, a, batch * kTokens, out);
+    HIP_CHECK(hipGetLastError());
+    const HqBranchTensors t = hq_tensors(which);
+    return HqBranchView{t.conv1.in, t.conv1.out / 4, hq_a_.get(), hq_h_.get(), out, t.conv1.w.get(), t.conv1.b.get(),
+                        t.ln.w.get(), t.ln.b.get(), t.conv2.w.get(), t.conv2.b.get()};
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -135,6 +135,8 @@ constexpr size_t kHqFeatureFloats = (size_t)kLowRes * kLowRes * 32;
 constexpr size_t handle_floats(bool hq) { return kEmbeddingFloats + (hq ? kHqFeatureFloats : 0); }
 constexpr int kHqMaxPoints = 9;      // a SAM-HQ prompt: the HQ token takes the 15th token row
 
+enum class HqBranch { vit, emb };    // the two branches of the SAM-HQ features: early ViT block, final embedding
+
 // One execution lane.  What is the lane's own here: the encoder, the decoder, image intake (staging ring, resize tables,
 // staged resizes) and the pass flags with DeferredPass.  The rest are components with contracts of their own, which the
 // methods below only forward to: StageClock (stage_clock.hpp; under mutex()), CompletionEvents (completion_events.hpp;
@@ -268,6 +270,18 @@ class SamModel {
     std::vector<std::pair<std::string, size_t>> encoder_operands_layout(int layer) const;
     void encoder_operands(float* out, int layer) const;
 
+    // Diagnostic: one branch of the SAM-HQ features alone, as encode() runs it (the same private entry, which picks the
+    // branch's tensors): a is a DEVICE input f16 [batch * 4096][K], K = the encoder's width (vit) or 256 (emb), batch 1..2.
+    // Enqueued on the lane's stream under mutex(); after synchronize() the view's pointers are readable: A fp32
+    // [batch * 4096][4 C] (hq_a_), H f16 [batch * 16384][C] (hq_h_), Y fp32 [batch * 16384][128] (the branch's workspace), and
+    // the loaded operands w1 f16 [4 C][K], b1 [4 C], ln_w / ln_b [C], w2 f16 [128][C], b2 [128].
+    struct HqBranchView {
+        int K, C;
+        float const* A; half_t const* H; float const* Y;
+        half_t const* w1; float const* b1; float const* ln_w; float const* ln_b; half_t const* w2; float const* b2;
+    };
+    HqBranchView run_hq_branch(HqBranch which, half_t const* a, int batch);
+
     // Masks to the caller, in steps so that the wait happens outside mutex() (MaskTransport, mask_transport_exec.hpp):
     // acquire_mask_slot (no mutex needed; callers hold the slot as a MaskSlotLease, below), enqueue_masks with the first
     // n_iou IoU predictions of the last decode() (under mutex()), finish_masks (no mutex), release_mask_slot.
@@ -332,7 +346,9 @@ class SamModel {
     void reserve_decoder(int count);
     void decode_chunk(float const* const* emb, float const* coords, float const* labels, int count, int first, int points,
                       k::MaskSource const* mask_input);
-    void hq_gemm_pair(half_t const* a, int K, LinearH const& conv1, NormW const& ln, LinearH const& conv2, int M, float* out);
+    struct HqBranchTensors { LinearH const& conv1; NormW const& ln; LinearH const& conv2; };
+    HqBranchTensors hq_tensors(HqBranch which) const;                         // the ONE place a branch's tensors are chosen
+    void hq_branch(HqBranch which, half_t const* a, int M, float* out);
     void gemm(k::GemmArgs const& a, Stage shape = ST_COUNT);     // shape: ST_GEMM_PATCH / _PROJ / _FC2 for the stage clocks
     template <typename F> void neck_launch(double flops, F&& launch);     // launch(start, stop): one of k::neck_conv*_ln
     struct DeviceTap { std::string name; half_t const* h; float const* f; size_t n; };      // one of h / f; n elements

@@ -191,6 +191,29 @@ DLIMG_API int dlimg_amd_test_upscale_logits(uint16_t const* keys_h, int P, uint1
  * sub-pixel * 32 + channel); b_vit / b_emb [32]; out [256][256][32]. */
 DLIMG_API int dlimg_amd_test_hq_features_finish(float const* vit, float const* emb, float const* b_vit, float const* b_emb, float* out,
                                                 int* guards_ok);
+/* One branch of the SAM-HQ features alone, as the product's encoder runs it: lane 0 of env's first replica, under the lane's
+ * mutex, through the entry SamModel::encode calls (which picks the branch's tensors).  branch 0: the early-ViT branch, K = the
+ * model's embed_dim, C = 256; branch 1: the embedding branch, K = 256, C = 64.  a: f16 [B * 4096][K], B = batch in 1 .. 2.
+ * Results: out_A fp32 [B * 4096][4 C] (transposed convolution as a GEMM, bias included), out_H f16 [B * 16384][C] (LayerNorm +
+ * GELU of out_A read as [B * 16384][C]), out_Y fp32 [B * 16384][128] (second GEMM, without its bias).  The branch's loaded
+ * operands: w1 f16 [4 C][K] and b1 [4 C], ln_w / ln_b [C], w2 f16 [128][C] and b2 [128]; any of the nine outputs may be NULL.
+ * Refused by name before anything is launched: a model without dec.hq.* tensors, a branch other than 0 / 1, a batch outside
+ * 1 .. 2, a null environment or input. */
+DLIMG_API int dlimg_amd_test_hq_branch(dlimg_Environment env, int branch, uint16_t const* a, int batch, float* out_A, uint16_t* out_H,
+                                       float* out_Y, uint16_t* w1, float* b1, float* ln_w, float* ln_b, uint16_t* w2, float* b2);
+/* k::layernorm alone, one launcher call on the null stream; x [rows][dim], w / b [dim] HOST memory, every device buffer with 256
+ * guard bytes of 0xA5 on either side (*guards_ok: untouched after the launch).  out_f32 / out_f16: either or both.  in_place != 0:
+ * the launch gets out_f32 = x (needs out_f32).  misalign_x != 0: the device x starts 4 bytes behind a 16-byte boundary.
+ * nonfinite (optional): in and out, the value of an int in host-visible memory the launch is given as its non-finite report.
+ * A launcher's refusal arrives as the call's error; *nonfinite is then returned as it was found. */
+DLIMG_API int dlimg_amd_test_layernorm_rows(float const* x, float const* w, float const* b, float eps, int rows, int dim, int act,
+                                            int in_place, int misalign_x, float* out_f32, uint16_t* out_f16, int* nonfinite,
+                                            int* guards_ok);
+/* The other row kernels of kernels/elementwise.hip alone, guarded as above.  op 0: k::cast_f16, a fp32 [n] -> out_f16 [n].
+ * op 1: k::add_cast, a fp32 [n] + b fp32 [b_mod] (NULL: nothing added; element i takes b[i % b_mod]) -> out_f32 / out_f16 [n],
+ * either or both.  op 2: k::im2col3x3, in_h f16 [n = B][64][64][C = b_mod] -> out_f16 [B * 4096][9][C]. */
+DLIMG_API int dlimg_amd_test_elementwise(int op, float const* a, uint16_t const* in_h, float const* b, long long b_mod, long long n,
+                                         float* out_f32, uint16_t* out_f16, int* guards_ok);
 
 /* ---- kernels alone, timed on device-resident data --------------------------------------------- */
 /* Times the two pixel kernels of the path alone on `batch` (1..16) device-resident 1024x1024 RGBA images / mask requests in

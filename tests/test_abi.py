@@ -71,7 +71,9 @@ def test_only_declared_dlimg_symbols_are_exported(api):
     # dlimg_amd_test_lasso_derive (tests/test_gpu_lasso_kernel.py)
     # ... and the three kernel-alone hooks of csrc/hq_test_hooks.cpp: dlimg_amd_test_hq_mask_path, dlimg_amd_test_upscale_logits and
     # dlimg_amd_test_hq_features_finish (tests/test_gpu_hq_kernels.py)
-    assert len(api.ext.HOOK_EXPORTS) == 33 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
+    # ... and dlimg_amd_test_hq_branch (tests/test_gpu_hq_features.py), dlimg_amd_test_layernorm_rows and dlimg_amd_test_elementwise
+    # (tests/test_gpu_row_kernels.py), in csrc/hq_test_hooks.cpp too
+    assert len(api.ext.HOOK_EXPORTS) == 36 and all("_test_" in n or "_bench_" in n for n in api.ext.HOOK_EXPORTS)
     # every hook has its ctypes signature in the one table ext._h() applies, and the library has every name of the table
     assert set(api.ext._HOOK_SIGS) == set(api.ext.HOOK_EXPORTS)
     hooks_lib = api.ext._h()
