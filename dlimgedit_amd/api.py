@@ -183,6 +183,9 @@ def matte_hooks_library() -> C.CDLL:
         _matte_hooks_lib.dlimg_amd_test_cutout.argtypes = [_vpp, _vpp, _vpp, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int,
                                                            C.POINTER(C.c_float)]
         _matte_hooks_lib.dlimg_amd_test_cutout.restype = C.c_int
+        _matte_hooks_lib.dlimg_amd_test_edge.argtypes = [_vpp, _ip, _ip, _ip, _ip, _ip, C.c_int, C.c_int, _ip, _ip, C.c_int,
+                                                         C.POINTER(C.c_float)]
+        _matte_hooks_lib.dlimg_amd_test_edge.restype = C.c_int
     return _matte_hooks_lib
 
 
@@ -353,6 +356,10 @@ STROKE_DEFAULT_CLICKS = 3    # clicks of a stroke mark that says 0
 CUTOUT_MARK = 13             # regions[4 i] of a cut-out mark (dlimgedit.h: DLIMG_CUTOUT_MARK; csrc/cutout_plan.hpp: kCutoutMark)
 CUTOUT_MAX_RADIUS = 32
 CUTOUT_DEFAULT_RADIUS = 16   # radius of a cut-out mark that says 0
+EDGE_MARK = 14               # regions[4 i] of an edge mark (dlimgedit.h: DLIMG_EDGE_MARK; csrc/edge_plan.hpp: kEdgeMark)
+EDGE_MAX_OFFSET = 64         # offset of an edge mark: -64 .. 64 pixels
+EDGE_MAX_FEATHER = 32
+EDGE_MAX_BORDER = 32
 
 
 @dataclass
@@ -391,7 +398,10 @@ class ClickEntries:
     click of every prompt is its head's.  Such a prompt is decoded behind the others like a prompt with marks.
     A cut-out mark is a continuation entry (CUTOUT_MARK, radius, 0, 0) directly behind the matte mark, the last entry of its
     prompt then, whose out_masks pointer is WRITTEN: cutouts[j] is (radius, the (h, w, 4) uint8 array that receives prompt j's
-    foreground colours and coverage), None without one.  It changes nothing else."""
+    foreground colours and coverage), None without one.  It changes nothing else.
+    An edge mark is a continuation entry (EDGE_MARK, offset, feather, border) behind the clicks and the clean-up mark of its prompt
+    and in front of its matte mark, whose point and pointer are not read: the prompt's mask is delivered grown, shrunk, feathered
+    or bordered.  It changes neither token_rows nor stage_clicks nor launches."""
     heads: list
     points: list
     regions: list
@@ -636,6 +646,33 @@ def _checked_cutout(cutout, matte: list, n: int) -> list:
     return out
 
 
+def _checked_edge(edge, n: int) -> list:
+    """`edge` of a call of n prompts -> per prompt None or (offset, feather, border): edge is None or one entry per prompt, None,
+    an int offset or (offset, feather, border) with offset -64 .. 64, feather 0 .. 32, border 0 .. 32, not all three 0."""
+    if edge is None:
+        return [None] * n
+    if isinstance(edge, (int, np.integer)):
+        raise Error("edge: None, or one entry (None, an offset or (offset, feather, border)) per prompt")
+    edge = list(edge)
+    if len(edge) != n:
+        raise Error("edge: None, or one entry (None, an offset or (offset, feather, border)) per prompt")
+    out = []
+    for q in edge:
+        if q is None:
+            out.append(None)
+            continue
+        q = (q, 0, 0) if isinstance(q, (int, np.integer)) else q
+        if not isinstance(q, (tuple, list)) or len(q) != 3 or not all(isinstance(v, (int, np.integer)) for v in q):
+            raise Error("edge: an edge is an int offset or (offset, feather, border)")
+        offset, feather, border = (int(v) for v in q)
+        if not -EDGE_MAX_OFFSET <= offset <= EDGE_MAX_OFFSET or not 0 <= feather <= EDGE_MAX_FEATHER or not 0 <= border <= EDGE_MAX_BORDER:
+            raise Error(f"edge: offset is -{EDGE_MAX_OFFSET} .. {EDGE_MAX_OFFSET}, feather 0 .. {EDGE_MAX_FEATHER}, border 0 .. {EDGE_MAX_BORDER}")
+        if (offset, feather, border) == (0, 0, 0):
+            raise Error("edge: offset, feather and border all 0 is the identity: pass None")
+        out.append((offset, feather, border))
+    return out
+
+
 def _with_cutouts(outs: list, cutouts: list) -> list:
     """The results of a batch call: the mask of a prompt, (coverage, rgba) of one with a cut-out."""
     return [o if q is None else (o, q[1]) for o, q in zip(outs, cutouts)]
@@ -709,7 +746,8 @@ def _entry_pointers(segs, heads, regs, outs_by_head: dict, priors: list, lassos:
 
 
 def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] = None, prior: Optional[list] = None,
-                    lasso: Optional[list] = None, matte: Optional[list] = None, cutout: Optional[list] = None):
+                    lasso: Optional[list] = None, matte: Optional[list] = None, cutout: Optional[list] = None,
+                    edge: Optional[list] = None):
     """The `points` / `regions` form of a batch call with clean-up, grid or prior marks as entry lists: entry i of the caller's,
     then its marks (the prior mark first: it stands directly behind its head).  -> (index into segs or None per entry, [(x, y)]
     or None, [(4 ints)]).  A point prompt gets the empty region (no box); a grid prompt is its head with the empty region and
@@ -728,6 +766,8 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
                 raise Error("a grid prompt takes no lasso")
             if matte is not None and matte[i] is not None:
                 raise Error("a grid prompt takes no matte: a label map is not a coverage")
+            if edge is not None and edge[i] is not None:
+                raise Error("a grid prompt takes no edge mark: a label map has no edge to move")
             regs.append(EMPTY_REGION)
             heads.append(None)
             if pts is not None:
@@ -751,6 +791,11 @@ def _marked_entries(n: int, points, regions, clean: list, grid: Optional[list] =
             if pts is not None:
                 pts.append((0, 0))
             regs.append((CLEAN_MARK, clean[i][0], clean[i][1], 0))
+        if edge is not None and edge[i] is not None:          # behind the clean-up mark, in front of the matte mark
+            heads.append(None)
+            if pts is not None:
+                pts.append((0, 0))
+            regs.append((EDGE_MARK,) + tuple(edge[i]))
         if matte is not None and matte[i] is not None:        # behind everything else of its prompt
             heads.append(None)
             if pts is not None:
@@ -774,7 +819,7 @@ def _marked_arrays(segs, heads, pts, regs):
 
 def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=None, grid=None, prior=None,
                   prior_strength=0, lasso=None, lasso_what=0, lasso_strength=0, matte=None, strokes=None,
-                  cutout=None) -> ClickEntries:
+                  cutout=None, edge=None) -> ClickEntries:
     """Entry lists for prompts of several clicks: clicks[j] the Points of prompt j (1 .. 8, the first one foreground),
     labels[j] their labels (None: all foreground), regions[j] its box or None.  refine_after: None, "each" (for every
     prompt), or per prompt None / "each" / click counts k -- "a refinement mark after the first k clicks": the prompt is then
@@ -802,6 +847,9 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     cutout: None, or per prompt None / a radius / (radius, out) -- a cut-out mark directly behind the prompt's matte mark (which
     it needs, with an image of 3 or 4 channels): the image's foreground colours under the matte's coverage, as RGBA (see
     compute_mask_clicks).  Entry lists without cut-outs are what they were.
+    edge: None, or per prompt None / an int offset / (offset, feather, border) -- an edge mark behind the prompt's clean-up mark
+    and in front of its matte mark: the mask grown, shrunk, feathered or bordered (see compute_mask_clicks).  Entry lists without
+    edge marks are what they were.
     Pure host code."""
     n = len(clicks)
     strokes = _checked_strokes(strokes, n)
@@ -817,6 +865,7 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
     any_matte = any(q is not None for q in matte)
     cutout = _checked_cutout(cutout, matte, n)
     any_cutout = any(q is not None for q in cutout)
+    edge = _checked_edge(edge, n)
     labels = [None] * n if labels is None else list(labels)
     regions = [None] * n if regions is None else list(regions)
     refine_after = [refine_after] * n if refine_after is None or isinstance(refine_after, str) else list(refine_after)
@@ -839,6 +888,8 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             raise Error("a grid prompt takes no matte: a label map is not a coverage")
         if grid[j] is not None and strokes[j]:
             raise Error("a grid prompt takes no strokes")
+        if grid[j] is not None and edge[j] is not None:
+            raise Error("a grid prompt takes no edge mark: a label map has no edge to move")
         if any_stroke:
             out.strokes.append([q[0] for q in strokes[j]])
         if grid[j] is not None:
@@ -913,6 +964,10 @@ def click_entries(clicks, labels=None, regions=None, refine_after=None, clean=No
             out.heads.append(None)
             out.points.append((0, 0))
             out.regions.append((CLEAN_MARK, clean[j][0], clean[j][1], 0))
+        if edge[j] is not None:              # behind the clean-up mark, in front of the matte mark
+            out.heads.append(None)
+            out.points.append((0, 0))
+            out.regions.append((EDGE_MARK,) + edge[j])
         if matte[j] is not None:             # behind everything else of its prompt
             out.heads.append(None)
             out.points.append((0, 0))
@@ -1021,7 +1076,7 @@ class Segmentation:
                             region: Optional[Region] = None, out: Optional[np.ndarray] = None, refine_after=None,
                             clean=None, prior: Optional[np.ndarray] = None, prior_strength: int = 0,
                             lasso: Optional[np.ndarray] = None, lasso_what: int = 0, lasso_strength: int = 0,
-                            matte=None, strokes=None, cutout=None):
+                            matte=None, strokes=None, cutout=None, edge=None):
         """Click-to-refine: one mask from 1 .. 8 clicks, labels[k] 1 (foreground, the first one always) or 0 (background), and
         an optional box.  With two clicks or more, or a box, the mask is the decoder's output 0.
         refine_after: click counts k, or "each" -- the clicks are replayed in stages as SAM's interactive predictor would take
@@ -1049,8 +1104,14 @@ class Segmentation:
         the call returns (coverage, rgba): rgba an (h, w, 4) uint8 array (`out`, a C-contiguous one of the caller's, which may be
         the matte's 4-channel image itself: decontaminated in place) whose first three bytes are the FOREGROUND colour of the
         pixel in the image's channel order -- one pass of Blur-Fusion over that radius on the GPU, in integers, which takes the
-        old background out of the soft edge -- and whose fourth byte is the coverage (dlimgedit.h, DLIMG_CUTOUT_MARK)."""
+        old background out of the soft edge -- and whose fourth byte is the coverage (dlimgedit.h, DLIMG_CUTOUT_MARK).
+        edge: an int offset, or (offset, feather, border) -- the mask (cleaned, with `clean`) is grown (offset > 0) or shrunk
+        (offset < 0) by that many pixels, -64 .. 64, with a disc; feathered by a linear ramp 2 * feather pixels wide, 0 .. 32; or
+        turned into a band of `border` pixels, 0 .. 32, on each side of the moved edge -- by an exact Euclidean distance on the
+        GPU, in integers (dlimgedit.h, DLIMG_EDGE_MARK).  A mask that touches the image's border is not shrunk from it.  With
+        `matte`, the matte filters what the edge mark delivered: shrink in front of it against a halo."""
         return Segmentation.compute_mask_batch([self], clicks=[clicks], labels=[labels], regions=[region],
+                                               edge=None if edge is None else [edge],
                                                cutout=None if cutout is None else [cutout],
                                                strokes=None if strokes is None else [list(strokes)],
                                                out=None if out is None else [out],
@@ -1062,7 +1123,7 @@ class Segmentation:
 
     def snap_selection(self, mask: np.ndarray, what: int = 0, strength: int = 0, clicks: Optional[Sequence[Point]] = None,
                        labels: Optional[Sequence[int]] = None, refine_after=None, clean=None,
-                       out: Optional[np.ndarray] = None, matte=None, cutout=None):
+                       out: Optional[np.ndarray] = None, matte=None, cutout=None, edge=None):
         """Snap a selection to the object: mask, an (h, w) uint8 selection of this image (a dragged lasso, a painted blob; 0 ..
         255 read as coverage), is the prompt -- its box (LASSO_BOX), its most interior point as a foreground click
         (LASSO_CLICK) and the selection itself as SAM's mask input (LASSO_MASK, at `strength` thousandths, 0: the default
@@ -1071,34 +1132,35 @@ class Segmentation:
         derived one (the first of them foreground); refine_after counts these; clean as for compute_mask_clicks.  `out` may be
         `mask` itself: a selection snapped in place.  An empty selection (no low-res cell above half coverage) raises Error.
         matte: (image, radius, eps) as for compute_mask_clicks -- the snapped selection comes back soft-edged.  cutout (with
-        matte): as for compute_mask_clicks -- (coverage, rgba) comes back."""
+        matte): as for compute_mask_clicks -- (coverage, rgba) comes back.  edge: as for compute_mask_clicks."""
         if clicks:
             return self.compute_mask_clicks(clicks, labels, None, out, refine_after, clean, lasso=mask, lasso_what=what,
-                                            lasso_strength=strength, matte=matte, cutout=cutout)
+                                            lasso_strength=strength, matte=matte, cutout=cutout, edge=edge)
         if labels or refine_after is not None:
             raise Error("snap_selection: labels and refine_after go with `clicks`")
         return Segmentation.compute_mask_batch([self], out=None if out is None else [out], clean=None if clean is None else [tuple(clean)],
                                                lasso=[mask], lasso_what=what, lasso_strength=strength,
                                                matte=None if matte is None else [tuple(matte)],
-                                               cutout=None if cutout is None else [cutout])[0]
+                                               cutout=None if cutout is None else [cutout],
+                                               edge=None if edge is None else [edge])[0]
 
     def scribble(self, fg: np.ndarray, bg: Optional[np.ndarray] = None, clicks: int = 0, region: Optional[Region] = None,
-                 out: Optional[np.ndarray] = None, clean=None, matte=None, cutout=None):
+                 out: Optional[np.ndarray] = None, clean=None, matte=None, cutout=None, edge=None):
         """Select by scribbling: fg, an (h, w) uint8 map of a stroke drawn over the object (a pixel belongs to it from 128 on),
         and optionally bg, a stroke over what the selection must leave out, are the prompt -- `clicks` foreground clicks (1 .. 8,
         0: the default 3) spread along fg and as many background clicks along bg, sampled on the GPU from the 256 x 256 low-res
         grid: the cell nearest the stroke's centroid, then farthest-point samples (dlimgedit.h, DLIMG_STROKE_MARK).  region: a
-        box to go with them; clean, matte, cutout and out as for compute_mask_clicks.  An empty stroke (no pixel from 128 on) raises
+        box to go with them; clean, matte, cutout, edge and out as for compute_mask_clicks.  An empty stroke (no pixel from 128 on) raises
         Error."""
         marks = [(fg, 1, clicks)] + ([] if bg is None else [(bg, 0, clicks)])
-        return self.compute_mask_clicks(None, None, region, out, None, clean, matte=matte, strokes=marks, cutout=cutout)
+        return self.compute_mask_clicks(None, None, region, out, None, clean, matte=matte, strokes=marks, cutout=cutout, edge=edge)
 
     @staticmethod
     def compute_mask_batch(segs: Sequence["Segmentation"], points: Optional[Sequence[Point]] = None,
                            regions: Optional[Sequence[Region]] = None, out: Optional[Sequence[np.ndarray]] = None,
                            clicks: Optional[Sequence[Sequence[Point]]] = None, labels=None, refine_after=None,
                            clean=None, grid=None, prior=None, prior_strength=0, lasso=None, lasso_what=0,
-                           lasso_strength=0, matte=None, strokes=None, cutout=None) -> list:
+                           lasso_strength=0, matte=None, strokes=None, cutout=None, edge=None) -> list:
         """One single-mask query per entry of `segs`, decoded as one batch (table slot 14): a point each, a region each, or
         -- both given -- the box regions[i] refined by the foreground point points[i] in one prompt (SAM's combined prompt:
         point, top-left, bottom-right with labels 1, 2, 3; the mask is the decoder's output 0).
@@ -1122,7 +1184,9 @@ class Segmentation:
         strokes (with `clicks`, whose entries may then be None): None, or per prompt None / a list of (map, label, clicks) --
         stroke marks, see compute_mask_clicks and scribble.
         cutout (either form): None, or per prompt None / a radius / (radius, out) -- cut-out marks, see compute_mask_clicks: the
-        result of such a prompt is (coverage, rgba) in place of the mask."""
+        result of such a prompt is (coverage, rgba) in place of the mask.
+        edge (either form): None, or per prompt None / an int offset / (offset, feather, border) -- edge marks, see
+        compute_mask_clicks; a box-only call may carry them too."""
         if strokes is not None and clicks is None:
             if points is not None:
                 raise Error("compute_mask_batch: strokes go with `clicks` (whose entries may be None), not with `points`")
@@ -1138,7 +1202,7 @@ class Segmentation:
             assert len(outs) == len(segs) and all(o.dtype == np.uint8 and o.flags.c_contiguous for o in outs)
             cutouts = _checked_cutout(cutout, _checked_matte(matte, len(segs)), len(segs))
             entries = click_entries(clicks, labels, regions, refine_after, clean, grid, prior, prior_strength, lasso, lasso_what,
-                                    lasso_strength, matte, strokes, cutouts)
+                                    lasso_strength, matte, strokes, cutouts, edge)
             out_of = {i: outs[j] for j, i in enumerate(entries.prompt_heads)}
             priors = _checked_prior(prior, prior_strength, len(segs))
             lassos = _checked_lasso(lasso, lasso_what, lasso_strength, len(segs))
@@ -1158,11 +1222,12 @@ class Segmentation:
         lassos = _checked_lasso(lasso, lasso_what, lasso_strength, n)
         mattes = _checked_matte(matte, n)
         cutouts = _checked_cutout(cutout, mattes, n)
+        edges = _checked_edge(edge, n)
         if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in priors) \
-                or any(q is not None for q in lassos) or any(q is not None for q in mattes):
+                or any(q is not None for q in lassos) or any(q is not None for q in mattes) or any(q is not None for q in edges):
             if points is None and regions is None and any(g is None and q is None for g, q in zip(grids, lassos)):
                 raise Error("compute_mask_batch: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos, mattes, cutouts)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, priors, lassos, mattes, cutouts, edges)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             ptrs = (C.c_void_p * m)(*_entry_pointers(segs, heads, regs, {e: outs[h] for e, h in enumerate(heads) if h is not None}, priors,
                                                      lassos, mattes, None, cutouts))
@@ -1499,11 +1564,11 @@ class ext:
 
     @classmethod
     def compute_mask_batch_device(cls, segs, dev_out: int, points=None, regions=None, root_device: int = 0, clicks=None,
-                                  labels=None, refine_after=None, clean=None, grid=None) -> list:
+                                  labels=None, refine_after=None, clean=None, grid=None, edge=None) -> list:
         """Device-output form of Segmentation.compute_mask_batch (points, regions or both, or clicks / labels / regions, as
         there): masks land tightly packed at `dev_out` (a device pointer on HIP device `root_device`), wherever their
-        embeddings live; returns the byte offset of every mask.  refine_after, clean, grid: as there (a grid prompt's
-        label map is delivered as a mask is)."""
+        embeddings live; returns the byte offset of every mask.  refine_after, clean, grid, edge: as there (a grid prompt's
+        label map is delivered as a mask is; an edge mark needs no pointer, so this form serves it)."""
         if refine_after is not None and clicks is None:
             raise Error("compute_mask_batch_device: refine_after goes with `clicks`")
         if clicks is not None:
@@ -1511,7 +1576,7 @@ class ext:
                 raise Error("compute_mask_batch_device: `points` or `clicks`, not both")
             if len(clicks) != len(segs):
                 raise Error("compute_mask_batch_device: one list of clicks per segmentation")
-            entries = click_entries(clicks, labels, regions, refine_after, clean, grid)
+            entries = click_entries(clicks, labels, regions, refine_after, clean, grid, edge=edge)
             calls = _entry_calls(entries)
             if len(calls) > 1:      # one-click prompts with and without a box: a call each, so that the masks stay in order
                 calls = [([i], entries.regions[i] != EMPTY_REGION) for i in range(len(entries.heads))]
@@ -1527,10 +1592,11 @@ class ext:
         n = len(segs)
         marks = _checked_clean(clean, n)
         grids = _checked_grid(grid, n)
-        if any(m is not None for m in marks) or any(g is not None for g in grids):
+        edges = _checked_edge(edge, n)
+        if any(m is not None for m in marks) or any(g is not None for g in grids) or any(q is not None for q in edges):
             if points is None and regions is None and any(g is None for g in grids):
                 raise Error("compute_mask_batch_device: neither points nor regions given")
-            heads, pts, regs = _marked_entries(n, points, regions, marks, grids)
+            heads, pts, regs = _marked_entries(n, points, regions, marks, grids, edge=edges)
             m, handles, p, r = _marked_arrays(segs, heads, pts, regs)
             offsets = (C.c_size_t * m)()
             _check(cls._l().dlimg_amd_get_segmentation_masks_device(handles, m, p, r, root_device, dev_out, offsets))
@@ -1991,6 +2057,35 @@ class ext:
         same = all((a == b).all() for a, b in zip(covs, given_a)) and all((a == b).all() for a, b in zip(guides, given_g))
         out = (outs, bool(ok.value) and same, int(launches.value)) if many else (outs[0], bool(ok.value) and same)
         return out if time_iters <= 0 else out + (float(ms.value),)
+
+    @classmethod
+    def test_edge(cls, masks, params, shortcut: bool = True, time_iters: int = 0):
+        """The edge kernels alone (dlimg_amd_test_edge, lib/libdlimgedit_matte_hooks.so): mask (h, w) uint8 and params (offset,
+        feather, border) through ONE k::mask_edge call on the default device, with guard bytes around the mask and the
+        workspace.  -> (result uint8 [h, w], guard bytes intact).  Lists of equal length for both arguments: that many jobs in
+        the one call, -> (list of results, guards intact, launches).  A mask None reaches the launcher as a null mask, of the
+        extent params then carries as (offset, feather, border, w, h).  shortcut False: no block is filled for being of one
+        polarity (same bytes).  time_iters > 0: two further elements, the milliseconds of one call (the mean of time_iters
+        repetitions between two events, each on the mask as given: a device-to-device copy of it goes back first) and the
+        milliseconds of those copies alone.  A refusal of the launcher raises Error."""
+        many = isinstance(masks, (list, tuple))
+        given = [None if m is None else np.array(m, np.uint8, order="C") for m in (masks if many else [masks])]     # copies: the hook writes them
+        pars = [tuple(int(v) for v in p) for p in (params if many else [params])]
+        n = len(given)
+        assert n == len(pars) and all(m is None or m.ndim == 2 for m in given)
+        assert all(len(p) == (3 if m is not None else 5) for m, p in zip(given, pars))
+        ints = lambda v: (C.c_int * n)(*v)
+        mp = (C.c_void_p * n)(*[None if m is None else m.ctypes.data for m in given])
+        ok, launches, ms = C.c_int(0), C.c_int(0), (C.c_float * 2)(0.0, 0.0)
+        lib = matte_hooks_library()
+        if lib.dlimg_amd_test_edge(mp, ints([p[3] if m is None else m.shape[1] for m, p in zip(given, pars)]),
+                                   ints([p[4] if m is None else m.shape[0] for m, p in zip(given, pars)]), ints([p[0] for p in pars]),
+                                   ints([p[1] for p in pars]), ints([p[2] for p in pars]), n, int(bool(shortcut)), C.byref(ok),
+                                   C.byref(launches), int(time_iters), ms) != 0:
+            msg = lib.dlimg_init().contents.last_error()
+            raise Error(msg.decode("utf-8", "replace") if msg else "Unknown error")
+        out = (given, bool(ok.value), int(launches.value)) if many else (given[0], bool(ok.value))
+        return out if time_iters <= 0 else out + (float(ms[0]), float(ms[1]))
 
     @classmethod
     def test_stroke_derive(cls, stroke_map: np.ndarray, pre_w: int, pre_h: int, clicks: int = STROKE_DEFAULT_CLICKS, time_iters: int = 0):

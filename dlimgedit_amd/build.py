@@ -9,11 +9,13 @@ Three libraries come out of the same sources:
   lib/libdlimgedit_test.so    the product's OBJECTS plus the hook sources (HOOK_SOURCES, csrc/*test_hooks.cpp): additionally
                               exports the dlimg_amd_test_* / dlimg_amd_bench_* hooks (include/dlimgedit/dlimgedit_amd_test.h)
                               the parity tests and the kernels-alone timing loops call; built by default next to the product
-  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp, csrc/stroke_test_hooks.cpp and
-                              csrc/cutout_test_hooks.cpp (SIDE_HOOK_SOURCES): exports dlimg_init, dlimg_amd_test_matte, the matte
-                              kernels alone (tests/test_gpu_matte_kernel.py), dlimg_amd_test_stroke_derive, the stroke derivation
-                              alone (tests/test_gpu_stroke_kernel.py), and dlimg_amd_test_cutout, the cut-out kernels alone
-                              (tests/test_gpu_cutout_kernel.py).  The test library's list of hooks is held to its length by
+  lib/libdlimgedit_matte_hooks.so  the product's OBJECTS plus csrc/matte_test_hooks.cpp, csrc/stroke_test_hooks.cpp,
+                              csrc/cutout_test_hooks.cpp and csrc/edge_test_hooks.cpp (SIDE_HOOK_SOURCES): exports dlimg_init,
+                              dlimg_amd_test_matte, the matte kernels alone (tests/test_gpu_matte_kernel.py),
+                              dlimg_amd_test_stroke_derive, the stroke derivation alone (tests/test_gpu_stroke_kernel.py),
+                              dlimg_amd_test_cutout, the cut-out kernels alone (tests/test_gpu_cutout_kernel.py), and
+                              dlimg_amd_test_edge, the edge kernels alone (tests/test_gpu_edge_kernel.py).
+                              The test library's list of hooks is held to its length by
                               tests/test_abi.py, so these hooks have a library of their own
   lib/libdlimgedit_tuning.so  `--tuning`: everything compiled with -DDLIMG_TUNING -- additionally the ablated kernel variants
                               and in-kernel cycle stamps the scripts under tools/ use (DLIMGEDIT_*_ABLATE, GemmArgs::stamps);
@@ -46,7 +48,7 @@ EXPORTS_TEST_MAP = CSRC / "exports_test.map"
 HOOK_SOURCES = ["test_hooks.cpp", "neck_test_hooks.cpp", "cleanup_test_hooks.cpp", "grid_test_hooks.cpp", "prior_test_hooks.cpp",
                 "lasso_test_hooks.cpp", "hq_test_hooks.cpp"]
 # its own library (and the tuning library), with a version script of its own
-SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp", "cutout_test_hooks.cpp"]
+SIDE_HOOK_SOURCES = ["matte_test_hooks.cpp", "stroke_test_hooks.cpp", "cutout_test_hooks.cpp", "edge_test_hooks.cpp"]
 MATTE_HOOKS_MAP = CSRC / "matte_hooks_exports.map"
 
 SOURCES = [
@@ -65,6 +67,7 @@ SOURCES = [
     "kernels/mask_matte.hip",
     "kernels/mask_stroke.hip",
     "kernels/mask_cutout.hip",
+    "kernels/mask_edge.hip",
     "kernels/resize.hip",
     "kernels/objects.hip",
     "resize_tables.cpp",
@@ -95,6 +98,7 @@ EXTRA_FLAGS = {
     "kernels/mask_matte.hip": ["-ffp-contract=off"],       # integer throughout; as its neighbours all the same (tests/matte_ref.py)
     "kernels/mask_stroke.hip": ["-ffp-contract=off"],      # integer throughout; as its neighbours all the same (tests/stroke_ref.py)
     "kernels/mask_cutout.hip": ["-ffp-contract=off"],      # integer throughout; as its neighbours all the same (tests/cutout_ref.py)
+    "kernels/mask_edge.hip": ["-ffp-contract=off"],        # integer but for a square root's first guess (tests/edge_ref.py)
     "kernels/resize.hip": ["-ffp-contract=off"],
     "kernels/objects.hip": ["-ffp-contract=off"],
     "resize_tables.cpp": ["-ffp-contract=off"],

@@ -1,4 +1,4 @@
-// What the kernels that take box sums over a clipped (2r+1)^2 window share (mask_matte.hip, mask_cutout.hip): a workgroup of
+// What the kernels that take box sums over a clipped (2r+1)^2 window share (mask_matte.hip, mask_cutout.hip; mask_edge.hip takes the cells alone): a workgroup of
 // BLOCK threads takes a strip of BLOCK - 2r columns by a band of rows, thread t owning column x0 - r + t; column sums slide
 // down the band in registers and block_scan turns a row of them into prefixes, so that a window sum is prefix[x + r] -
 // prefix[x - r - 1].  The smallest and largest byte of every CELL x CELL cell of a plane (cell_extremes) let a block learn from
@@ -65,10 +65,10 @@ DLIMG_DEVICE void cell_extremes(const uint8_t* plane, int w, int h, int cells_x,
     if (t == 0) cells[cell] = s_lo | (s_hi << 8);
 }
 
-// Whether the plane is one value over the pixels [xa, xb] x [ya, yb] (clipped to the image), by the cells that touch them; the
-// value in *value.  Every thread of the block calls it and gets the same answer.  Job: w, h, cells, cells_x.
+// The smallest and the largest byte of the plane over the pixels [xa, xb] x [ya, yb] (clipped to the image), by the cells that
+// touch them.  Every thread of the block calls it and gets the same answer.  Job: w, h, cells, cells_x.
 template <typename Job>
-DLIMG_DEVICE bool uniform_over(Job const& job, int xa, int xb, int ya, int yb, int* value) {
+DLIMG_DEVICE void extremes_over(Job const& job, int xa, int xb, int ya, int yb, int* smallest, int* largest) {
     __shared__ int u_lo, u_hi;
     const int t = (int)threadIdx.x;
     if (t == 0) {
@@ -93,8 +93,16 @@ DLIMG_DEVICE bool uniform_over(Job const& job, int xa, int xb, int ya, int yb, i
         atomicMax(&u_hi, hi);
     }
     __syncthreads();
-    *value = u_lo;
-    return u_lo == u_hi;
+    *smallest = u_lo;
+    *largest = u_hi;
+}
+
+// Whether the plane is one value there, by the same cells; the value in *value.
+template <typename Job>
+DLIMG_DEVICE bool uniform_over(Job const& job, int xa, int xb, int ya, int yb, int* value) {
+    int hi;
+    extremes_over(job, xa, xb, ya, yb, value, &hi);
+    return *value == hi;
 }
 
 }  // namespace boxwin

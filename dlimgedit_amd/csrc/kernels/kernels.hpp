@@ -471,5 +471,28 @@ size_t mask_cutout_workspace_bytes(const CutoutJob* jobs, int count);
 int mask_cutout_launches(const CutoutJob* jobs, int count);          // kernel launches mask_cutout makes for these jobs
 void mask_cutout(const CutoutJob* jobs_host, int count, void* workspace, hipStream_t, bool shortcut = true);
 
+// ---- edge marks (K24, kernels/mask_edge.hip) --------------------------------------------------
+// Grow, shrink, feather and border a mask, in place: an exact Euclidean distance to the mask's edge, an offset, a map to bytes,
+// in integers (tests/edge_ref.py restates it in numpy).  mask M [H][W] u8 tightly packed; a pixel is foreground when its byte is
+// >= 128.  Pixels outside the image do not exist: they are neither foreground nor background, so a mask that touches the image's
+// edge is not eroded from it.  d2 of a pixel: the exact squared distance to the nearest pixel of the other polarity, infinite
+// where there is none.  isqrt rounds down, fdiv is floor division.
+//     q = isqrt(65536 d2)                 S = q - 128 for a foreground pixel, -(q - 128) for a background one
+//     T = S + 256 offset                  border > 0:  T <- 256 border - |T|
+//     out = 255 if T > 0 else 0                                          (feather == 0)
+//     out = clamp(fdiv(255 (T + 256 f) + 256 f, 512 f), 0, 255)           (feather == f > 0)
+// offset -64 .. 64 (positive grows), feather 0 .. 32, border 0 .. 32, not all three 0.  With R = |offset| + feather + border + 1
+// every d2 >= R^2, the infinite one too, gives the byte of d2 == R^2: distances are exact below R only.  Jobs of one call may
+// differ in size.  Refused before anything is launched: a null mask, an extent that is not positive, whose w * h does not fit
+// an int or which is so thin that one mask needs 2^24 workgroups or more, parameters outside these ranges, all three 0.
+// Stream-ordered, no host synchronisation, no global atomics: three launches per 16 jobs (two with shortcut = false).
+// workspace: mask_edge_workspace_bytes(jobs, count) bytes of device memory (2 per pixel, 4 per 64 x 64 cell), contents irrelevant
+// before and after.  shortcut = false: the blocks whose mask is of one polarity over their halo of R pixels -- whose output is
+// one byte -- are computed like any other (measurements and tests; same bytes).
+struct EdgeJob { uint8_t* mask; int w, h, offset, feather, border; };   // mask: device, packed rows, in place
+size_t mask_edge_workspace_bytes(const EdgeJob* jobs, int count);
+int mask_edge_launches(const EdgeJob* jobs, int count);              // kernel launches mask_edge makes for these jobs
+void mask_edge(const EdgeJob* jobs_host, int count, void* workspace, hipStream_t, bool shortcut = true);
+
 }  // namespace k
 }  // namespace dlimg

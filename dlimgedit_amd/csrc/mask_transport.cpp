@@ -16,6 +16,9 @@ constexpr double kCleanBytesPerPixelAndPass = 2 * 1 + 2 * 4 + 4 + 4 * 4 + 1;    
 constexpr double kMatteBytesPerPixel = 2 * 1 + 1 + 2 * 2 * 4;
 // k::mask_cutout, no block uniform: the coverage read twice (cells, sums), the RGBA written; the guide's channels on top
 constexpr double kCutoutBytesPerPixel = 2 * 1 + 4;
+// k::mask_edge at the largest reach, no block uniform: the mask read by the cells and, with the halo rows above and below a band,
+// six times by the column pass; two bytes of distance written, read twice over with the halo columns; the mask written
+constexpr double kEdgeBytesPerPixel = 1 + 6 + 2 + 4 + 1;
 
 // Direct xGMI copies between two GPUs need peer access switched on once per direction (without it the runtime stages
 // the copy through host memory: still correct, slower).  Failures are not errors: the copy falls back by itself.
@@ -44,6 +47,12 @@ void enable_peer_access(int from_device, int to_device) {
 bool any_cleanup(CleanSpec const* clean, int count) {
     for (int i = 0; clean && i < count; ++i)
         if (clean[i].any()) return true;
+    return false;
+}
+
+bool any_edge(EdgeRequest const* edge, int count) {
+    for (int i = 0; edge && i < count; ++i)
+        if (edge[i].any()) return true;
     return false;
 }
 
@@ -101,9 +110,9 @@ hipEvent_t MaskTransport::piece_event(MaskSlot& slot, int i) {
 
 // The plan of the slot, step by step, on the lane's stream; slot.done behind the last of them.
 void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
-                        GridPaint const* paint, MatteRequest const* matte) {
+                        GridPaint const* paint, MatteRequest const* matte, EdgeRequest const* edge) {
     MaskTransportPlan const& p = slot.plan;
-    DLIMG_ASSERT(!paint || (count == 1 && !clean && !matte));
+    DLIMG_ASSERT(!paint || (count == 1 && !clean && !matte && !edge));
     // the slot is ours, and its previous user waited for the slot's event before letting go of it
     slot.dev.reserve(p.reserve_device);
     slot.pin.reserve(p.reserve_pinned);
@@ -137,6 +146,7 @@ void MaskTransport::run(MaskSlot& slot, k::PostJob const* jobs, int count, float
             for (int i = s.first; i < s.first + s.count; ++i) bytes += kLogitBytes + (double)slot.input.sizes[i];
             clock_.timed(ST_POST, bytes, [&] { k::postprocess_masks(&slot.kernel_jobs[s.first], s.count, stream_); });
             if (clean) run_cleanup(slot, s, clean);
+            if (edge) run_edge(slot, s, edge);
             if (matte) run_matte(slot, s, matte);
         } else if (s.kind == MaskStep::event) {
             HIP_CHECK(hipEventRecord(piece_event(slot, s.first), stream_));
@@ -171,6 +181,28 @@ void MaskTransport::run_cleanup(MaskSlot& slot, MaskStep const& s, CleanSpec con
     slot.clean_workspace.reserve(k::mask_cleanup_workspace_bytes(slot.clean_jobs.data(), n_clean));
     clock_.timed(ST_POST, clean_bytes, [&] { k::mask_cleanup(slot.clean_jobs.data(), n_clean, slot.clean_workspace.get(), stream_); },
                  clock_.profiling() ? k::mask_cleanup_launches(slot.clean_jobs.data(), n_clean) : 1);
+}
+
+// The edge marks of the masks of launch step `s`, behind its post-processing launch and its clean-up and in front of its mattes:
+// in place where the launch wrote them, device memory in every mode a request with edge marks is planned in (never the direct
+// mode), as for clean-up.
+void MaskTransport::run_edge(MaskSlot& slot, MaskStep const& s, EdgeRequest const* edge) {
+    slot.edge_jobs.clear();
+    double bytes = 0;
+    for (int i = s.first; i < s.first + s.count; ++i) {
+        if (!edge[i].any()) continue;
+        DLIMG_ASSERT(slot.plan.mode != MaskMode::direct);
+        k::PostJob const& j = slot.kernel_jobs[i];
+        slot.edge_jobs.push_back(k::EdgeJob{j.dst, j.out_w, j.out_h, edge[i].offset, edge[i].feather, edge[i].border});
+        bytes += kEdgeBytesPerPixel * (double)slot.input.sizes[i];
+    }
+    if (slot.edge_jobs.empty()) return;
+    const int n = (int)slot.edge_jobs.size();
+    roctx::Range range("dlimg.mask_edge");
+    slot.edge_workspace.reserve(k::mask_edge_workspace_bytes(slot.edge_jobs.data(), n));
+    clock_.timed(ST_POST, bytes, [&] { k::mask_edge(slot.edge_jobs.data(), n, slot.edge_workspace.get(), stream_); },
+                 clock_.profiling() ? k::mask_edge_launches(slot.edge_jobs.data(), n) : 1);
+    HIP_CHECK(hipGetLastError());        // a launch that was not taken is reported here, not by the copy behind it
 }
 
 // The mattes of the masks of launch step `s`, behind its post-processing launch and its clean-up: in place where the launch
@@ -220,7 +252,7 @@ void MaskTransport::run_cutout(MaskSlot& slot, k::PostJob const& j, MatteRequest
 }
 
 void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean,
-                            GridPaint const* paint, MatteRequest const* matte) {
+                            GridPaint const* paint, MatteRequest const* matte, EdgeRequest const* edge) {
     if (count <= 0) return;
     // DLIMGEDIT_DIRECT_MASKS=0: measurement aid (always the copy path)
     static const bool direct_allowed = [] { const char* e = std::getenv("DLIMGEDIT_DIRECT_MASKS"); return !e || std::atoi(e) != 0; }();
@@ -229,7 +261,8 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
     in.iou_count = iou_count;
     if (!any_cleanup(clean, count)) clean = nullptr;
     if (!any_matte(matte, count)) matte = nullptr;
-    in.direct_allowed = direct_allowed && !clean && !matte;      // a mask to clean or to matte goes through the slot's device buffer
+    if (!any_edge(edge, count)) edge = nullptr;
+    in.direct_allowed = direct_allowed && !clean && !matte && !edge;     // a mask to clean, to edge or to matte goes through the slot's device buffer
     in.others_idle = mask_mode_asks_idle(count, in.direct_allowed) && (!board_ || board_->others_idle(lane_index_));
     // a destination in pinned image memory of the library (the Image the reference's wrapper allocates for the result
     // through create_image).  Direct mode looks at every destination, staged mode only asks whether all of them are pinned:
@@ -241,7 +274,7 @@ void MaskTransport::enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, f
         if (!in.dst_pinned[i] && !every) break;
     }
     plan_mask_transport(in, slot.plan);
-    run(slot, jobs, count, iou, device_, clean, paint, matte);
+    run(slot, jobs, count, iou, device_, clean, paint, matte, edge);
     if (board_) board_->mark(lane_index_, stream_);
 }
 
@@ -274,7 +307,7 @@ void MaskTransport::finish(MaskSlot& slot, k::PostJob const* jobs, int count, fl
 }
 
 void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean,
-                                   GridPaint const* paint) {
+                                   GridPaint const* paint, EdgeRequest const* edge) {
     if (count <= 0) return;
     // test hook: take the staging + peer-copy path even when the destination is this lane's own GPU (a one-GPU box
     // has no second device to copy to; the path is the same code, the copy degenerates to device-to-device)
@@ -282,7 +315,7 @@ void MaskTransport::enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int c
     const bool force_peer = fp && std::atoi(fp) != 0;
     fill_sizes(slot.input.sizes, jobs, count);
     plan_mask_transport_device(slot.input.sizes, dst_device == device_ && !force_peer, slot.plan);
-    run(slot, jobs, count, nullptr, dst_device, any_cleanup(clean, count) ? clean : nullptr, paint);
+    run(slot, jobs, count, nullptr, dst_device, any_cleanup(clean, count) ? clean : nullptr, paint, nullptr, any_edge(edge, count) ? edge : nullptr);
 }
 
 void MaskTransport::wait(MaskSlot& slot) { HIP_CHECK(hipEventSynchronize(slot.done)); }

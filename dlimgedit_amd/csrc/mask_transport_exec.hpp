@@ -11,6 +11,12 @@
 //                                            mode: k::mask_cleanup runs right behind the post-processing launch, in place
 //                                            where that launch wrote -- the slot's device buffer, or the destination itself
 //                                            when that is memory of the lane's own GPU -- before any copy or event
+//   edge (enqueue, enqueue_device)           optional, [count]: the edge mark of mask i (edge_plan.hpp; kernels.hpp K24; all three
+//                                            values 0: none).  Treated as clean-up is: never the direct mode; k::mask_edge runs
+//                                            behind the post-processing launch and behind k::mask_cleanup when both are asked
+//                                            for, in place where the launch wrote -- the slot's device buffer, or the
+//                                            destination itself when that is memory of the lane's own GPU -- before the matte
+//                                            and before any copy or event; its workspace is pooled with the slot
 //   matte (enqueue)                          optional, [count]: the matte of mask i (matte_plan.hpp; kernels.hpp K21; a null
 //                                            guide: none).  Treated as clean-up is: never the direct mode; k::mask_matte runs
 //                                            behind the post-processing launch and behind k::mask_cleanup when both are asked
@@ -47,6 +53,12 @@ struct GridPaint {
     k::GridKept kept{};
 };
 
+// What an edge mark asks of one mask of a request: the mark's ints (all 0: the mask is delivered as it is).
+struct EdgeRequest {
+    int offset = 0, feather = 0, border = 0;
+    bool any() const { return offset != 0 || feather != 0 || border != 0; }
+};
+
 // What a cut-out mark asks of a mask with a matte: where the RGBA goes, and the mark's radius.
 struct CutoutRequest {
     uint8_t* dst = nullptr;                 // HOST memory, [out_h][out_w][4]; null: no cut-out
@@ -72,6 +84,8 @@ struct MaskSlot {
     std::vector<k::PostJob> kernel_jobs;    // the caller's jobs with the destinations the plan gives the kernel
     std::vector<k::CleanJob> clean_jobs;    // the masks of the request that are cleaned, where the kernel wrote them
     DeviceBuffer<uint8_t> clean_workspace;  // labels and areas of k::mask_cleanup, pooled with the slot like `dev`
+    std::vector<k::EdgeJob> edge_jobs;      // the masks of the request whose edge is moved, where the kernel wrote them
+    DeviceBuffer<uint8_t> edge_workspace;   // the distances and the cells of k::mask_edge, pooled with the slot like `dev`
     std::vector<k::MatteJob> matte_jobs;    // the masks of the request that get a soft edge, where the kernel wrote them
     DeviceBuffer<uint8_t> matte_workspace;  // the A and B planes and the cells of k::mask_matte, pooled with the slot like `dev`
     DeviceBuffer<uint8_t> cutout_dev;       // the RGBA of the request's cut-out, 4 bytes per pixel, and the cells of k::mask_cutout:
@@ -93,17 +107,18 @@ class MaskTransport {
     MaskSlot& acquire();
     void release(MaskSlot& s);
     void enqueue(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int iou_count, CleanSpec const* clean = nullptr,
-                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr);
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr, EdgeRequest const* edge = nullptr);
     void finish(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count);
     void enqueue_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
-                        GridPaint const* paint = nullptr);
+                        GridPaint const* paint = nullptr, EdgeRequest const* edge = nullptr);
     void wait(MaskSlot& slot);
 
   private:
     hipEvent_t piece_event(MaskSlot& slot, int i);
     void run(MaskSlot& slot, k::PostJob const* jobs, int count, float const* iou, int dst_device, CleanSpec const* clean,
-             GridPaint const* paint, MatteRequest const* matte = nullptr);
+             GridPaint const* paint, MatteRequest const* matte = nullptr, EdgeRequest const* edge = nullptr);
     void run_cleanup(MaskSlot& slot, MaskStep const& step, CleanSpec const* clean);
+    void run_edge(MaskSlot& slot, MaskStep const& step, EdgeRequest const* edge);
     void run_matte(MaskSlot& slot, MaskStep const& step, MatteRequest const* matte);
     void run_cutout(MaskSlot& slot, k::PostJob const& job, MatteRequest const& matte);
 

@@ -291,13 +291,13 @@ class SamModel {
     MaskSlot& acquire_mask_slot() { return masks_.acquire(); }
     void release_mask_slot(MaskSlot& s) { masks_.release(s); }
     void enqueue_masks(MaskSlot& slot, k::PostJob const* jobs, int count, int iou_count, CleanSpec const* clean = nullptr,
-                       GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) {
-        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean, paint, matte);
+                       GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr, EdgeRequest const* edge = nullptr) {
+        masks_.enqueue(slot, jobs, count, iou_.get(), iou_count, clean, paint, matte, edge);
     }
     void finish_masks(MaskSlot& slot, k::PostJob const* jobs, int count, float* iou_out, int iou_count) { masks_.finish(slot, jobs, count, iou_out, iou_count); }
     void enqueue_masks_device(MaskSlot& slot, k::PostJob const* jobs, int count, int dst_device, CleanSpec const* clean = nullptr,
-                              GridPaint const* paint = nullptr) {
-        masks_.enqueue_device(slot, jobs, count, dst_device, clean, paint);
+                              GridPaint const* paint = nullptr, EdgeRequest const* edge = nullptr) {
+        masks_.enqueue_device(slot, jobs, count, dst_device, clean, paint, edge);
     }
     void wait_masks(MaskSlot& slot) { masks_.wait(slot); }
     // Blocking convenience form of the three calls above (mutex() held throughout).

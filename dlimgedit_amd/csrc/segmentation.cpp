@@ -1,6 +1,6 @@
 #include "segmentation.hpp"
 
-#include "cutout_plan.hpp"
+#include "edge_plan.hpp"
 #include "grid_plan.hpp"
 #include "lasso_plan.hpp"
 #include "matte_plan.hpp"
@@ -55,6 +55,8 @@ struct BatchPrompts {
     bool any_matte = false;
     std::vector<CutoutSpec> cutout;    // [prompt]: what its cut-out mark says (cutout_plan.hpp; nothing without one)
     std::vector<uint8_t*> cutout_dst;  // [prompt]: where its RGBA goes, out_masks[] of the mark's entry (null without one)
+    std::vector<EdgeSpec> edge;        // [prompt]: what its edge mark says (edge_plan.hpp; nothing without one)
+    bool any_edge = false;
     std::vector<std::vector<StrokeSpec>> strokes;      // [prompt]: its stroke marks (stroke_plan.hpp; none without one); its packed
                                                        // points are written once their clicks are derived (decode_batch_on)
     std::vector<std::vector<uint8_t const*>> stroke_map;       // [prompt][mark]: the map, out_masks[] of the mark's entry
@@ -90,8 +92,11 @@ BatchPrompts read_batch_prompts(SegmentationImpl const* const* segs, int count, 
     {
         // a mark needs the mask branch of the model; the environment's replicas share one model file
         const bool mask_branch = any && any->environment().lane(any->replica(), 0).has_mask_branch();
-        CutoutPlannedPrompts with_cutouts = plan_cutout_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
-                                                                /*device_form*/ out_masks == nullptr, same_as_head);
+        EdgePlannedPrompts with_edges = plan_edge_prompts(has_handle, points != nullptr, regions, mask_branch, has_pointer,
+                                                          /*device_form*/ out_masks == nullptr, same_as_head);
+        b.edge = std::move(with_edges.edge);
+        b.any_edge = with_edges.any_edge;
+        CutoutPlannedPrompts& with_cutouts = with_edges.inner;
         b.cutout = std::move(with_cutouts.cutout);
         for (CutoutSpec const& c : b.cutout) b.cutout_dst.push_back(c.any() ? out_masks[c.entry] : nullptr);
         StrokePlannedPrompts& with_strokes = with_cutouts.inner;
@@ -604,8 +609,8 @@ struct HostMasks {
     uint8_t* const* out_masks;
     uint8_t* dst(int head) const { return out_masks[head]; }
     void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
-                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) const {
-        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean, paint, matte);
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr, EdgeRequest const* edge = nullptr) const {
+        model.enqueue_masks(slot, jobs.data(), (int)jobs.size(), 0, clean, paint, matte, edge);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs) const {
         model.finish_masks(slot, jobs.data(), (int)jobs.size(), nullptr, 0);
@@ -619,9 +624,9 @@ struct DeviceMasks {
     int root_device;
     uint8_t* dst(int head) const { return dev_out + offsets[head]; }
     void enqueue(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const& jobs, CleanSpec const* clean,
-                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr) const {
+                 GridPaint const* paint = nullptr, MatteRequest const* matte = nullptr, EdgeRequest const* edge = nullptr) const {
         DLIMG_ASSERT(!matte);                    // (the planner refuses a matte mark in the device form)
-        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean, paint);
+        model.enqueue_masks_device(slot, jobs.data(), (int)jobs.size(), root_device, clean, paint, edge);
     }
     void finish(SamModel& model, SamModel::MaskSlot& slot, std::vector<k::PostJob> const&) const { model.wait_masks(slot); }
 };
@@ -634,7 +639,9 @@ struct DeviceMasks {
 // post-processed.  A prompt with a clean-up mark has its mask cleaned on the GPU behind the post-processing (the mask of the
 // last stage only; the logits fed back between stages are untouched).  A prompt with a matte mark has its mask -- the cleaned
 // one when it has both -- turned into a coverage on the GPU behind that, guided by the image the mark brought.  A cut-out mark
-// behind the matte mark has that image's foreground colours estimated behind that, and delivered beside the coverage.
+// behind the matte mark has that image's foreground colours estimated behind that, and delivered beside the coverage.  A prompt
+// with an edge mark has its mask -- the cleaned one -- grown, shrunk, feathered or bordered behind the clean-up and in front of
+// the matte, which then filters what the edge mark delivered.
 template <typename Sink>
 void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* const* segs, BatchPrompts const& batch, int const* points,
                                        int const* regions, Sink const& sink) {
@@ -648,6 +655,7 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
     std::vector<Chunk> chunks;
     std::vector<CleanSpec> clean;              // of the chunk being enqueued, [job]
     MatteRequest matte;                        // of the chunk being enqueued: a prompt with a matte mark is a chunk of its own
+    std::vector<EdgeRequest> edge;             // of the chunk being enqueued, [job]
     auto finish = [&](Chunk& c) {
         if (!c.lease.held()) return;
         const MaskSlotLease lease = std::move(c.lease);      // the slot goes back whether the wait throws or not
@@ -767,8 +775,16 @@ void SegmentationImpl::decode_batch_on(int replica, SegmentationImpl const* cons
                 clean.resize(n);
                 for (int j = 0; j < n; ++j) clean[j] = batch.clean[part.prompts[j]];
             }
+            if (batch.any_edge) {
+                edge.resize(n);
+                for (int j = 0; j < n; ++j) {
+                    EdgeSpec const& e = batch.edge[part.prompts[j]];
+                    edge[j] = EdgeRequest{e.offset, e.feather, e.border};
+                }
+            }
             // (a prompt with a matte mark is a chunk of its own: n == 1)
-            sink.enqueue(model, cur.lease.slot(), cur.jobs, batch.any_clean ? clean.data() : nullptr, nullptr, matte.any() ? &matte : nullptr);
+            sink.enqueue(model, cur.lease.slot(), cur.jobs, batch.any_clean ? clean.data() : nullptr, nullptr, matte.any() ? &matte : nullptr,
+                         batch.any_edge ? edge.data() : nullptr);
         }
         for (auto& c : chunks) finish(c);
     } catch (...) {

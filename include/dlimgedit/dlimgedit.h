@@ -162,7 +162,10 @@ typedef struct dlimg_Api {
      * from which that many clicks of that label are derived on the GPU.
      * Cut-out marks (a matte's foreground colours as RGBA): a continuation entry whose four ints are {DLIMG_CUTOUT_MARK,
      * radius, 0, 0} DIRECTLY BEHIND THE MATTE MARK, the last entry of its prompt then -- see DLIMG_CUTOUT_MARK below.  It is
-     * the one continuation entry whose out_masks[i] is WRITTEN: height * width * 4 bytes. */
+     * the one continuation entry whose out_masks[i] is WRITTEN: height * width * 4 bytes.
+     * Edge marks (grow, shrink, feather, border): a continuation entry whose four ints are {DLIMG_EDGE_MARK, offset, feather,
+     * border}, behind the clicks and the clean-up mark of its prompt and in front of its matte mark -- see DLIMG_EDGE_MARK
+     * below.  Its out_masks[i] is not read. */
     dlimg_Result (*get_segmentation_masks)(dlimg_Segmentation const* segs, int count, int const* points,
                                            int const* regions, uint8_t** out_masks);
 } dlimg_Api;
@@ -336,6 +339,33 @@ typedef struct dlimg_Api {
  * in front of any head, and dlimg_amd_get_segmentation_masks_device, which has no per-entry pointer to write to.  A grid
  * prompt is refused through its matte mark.  A call without cut-out marks is read as it always was. */
 #define DLIMG_CUTOUT_MARK 13
+/* regions[4 i] of an edge mark in get_segmentation_masks (slot 14): {DLIMG_EDGE_MARK, offset, feather, border} grows, shrinks,
+ * feathers or borders the mask its prompt delivers -- the four of an editor's Select > Modify menu -- on the GPU, in front of
+ * the copy.  The mark is neither a click nor a stage; points[i] and out_masks[i] of the mark are not read and it does not count
+ * towards the 8 clicks.  A prompt has one at most.  It stands behind every click, stroke mark and refinement mark of its prompt
+ * and behind the clean-up mark when there is one; in front of the matte mark (and with it the cut-out mark) when there is one,
+ * and is otherwise the last entry of its prompt.  The stages run in that order: clean-up, edge, matte, cut-out; the matte
+ * filters what the edge mark delivered.
+ * offset is -64 .. 64 pixels (positive grows, negative shrinks), feather 0 .. 32, border 0 .. 32; not all three 0.
+ * The definition is integer arithmetic, so the bytes are the same wherever they are computed.  A pixel of the mask is
+ * foreground when its byte is >= 128.  Pixels outside the image do not exist: they are neither foreground nor background, so
+ * a mask that touches the image's edge is not eroded from it.  d2 of a pixel is the exact squared Euclidean distance to the
+ * nearest pixel of the other kind, infinite where the image has none.  With isqrt rounding down and fdiv floor division:
+ *   q = isqrt(65536 d2)                   the distance in 1/256 pixel
+ *   S = q - 128 for a foreground pixel, -(q - 128) for a background pixel        (the edge runs half-way between pixel centres)
+ *   T = S + 256 offset;                   border > 0:  T <- 256 border - |T|     (a band of `border` pixels either side)
+ *   out = 255 if T > 0 else 0                                                    (feather == 0)
+ *   out = clamp(fdiv(255 (T + 256 f) + 256 f, 512 f), 0, 255)                    (feather == f > 0: a ramp 2 f pixels wide)
+ * With R = |offset| + feather + border + 1 every d2 >= R^2, the infinite one included, gives the byte of d2 == R^2.  With
+ * feather == border == 0 this is binary dilation or erosion by the disc {(dx, dy): isqrt(65536 (dx^2 + dy^2)) < 256 |offset| +
+ * 128}: 3 x 3 for 1, the 21-pixel disc for 2; no distance sits on a tie, so the two are exact duals.
+ * The prompt costs no further wait for the GPU: the kernels run in stream order behind the post-processing, in place where the
+ * mask is delivered into memory of the producing GPU, else in staging.
+ * Refused before anything is launched (the message says "mark" and names the entry): values outside these ranges, all three
+ * 0 (the identity), a second edge mark on a prompt, a mark in front of any head, a mark in front of a click, stroke,
+ * refinement or clean-up mark or behind a matte mark, and an edge mark on a grid prompt (a label map has no edge to move).  A
+ * call without edge marks is read as it always was. */
+#define DLIMG_EDGE_MARK 14
 
 /* The only exported symbol of the drop-in ABI.  Returns a process-lifetime table; idempotent. */
 DLIMG_API dlimg_Api const* dlimg_init(void);

@@ -274,6 +274,17 @@ struct Cutout {
     int radius = 0;
 };
 
+// An edge mark: the mask a prompt delivers grown (offset > 0) or shrunk (offset < 0) by that many pixels with a disc, feathered by
+// a linear ramp 2 * feather pixels wide, or turned into a band of `border` pixels on each side of the moved edge -- an editor's
+// Select > Modify, by an exact Euclidean distance on the GPU, in integers (dlimgedit.h, DLIMG_EDGE_MARK).  offset -64 .. 64,
+// feather 0 .. 32, border 0 .. 32, not all three 0.  A mask that touches the image's border is not shrunk from it.  Travels as an
+// edge mark of table slot 14 behind the clean-up mark and in front of the matte mark, which then filters what this delivered.
+struct Edge {
+    int offset = 0;
+    int feather = 0;
+    int border = 0;
+};
+
 // One click of a click-to-refine prompt: on the object (foreground) or where the mask should not be (background).
 struct Click {
     Point point;
@@ -385,33 +396,37 @@ class Segmentation {
     // matte: the mask is delivered as coverage 0 .. 255, its edge guided by the image (Matte), behind the clean-up.
     // strokes: scribbles whose sampled clicks follow the clicks given here (Stroke), in the order given; refine_after counts the
     // clicks given here.  (Behind matte, so that calls written before it read as they did.)
-    // cutout: the image's foreground colours under the matte's coverage go to cutout->rgba (Cutout); needs matte.  (The last
+    // cutout: the image's foreground colours under the matte's coverage go to cutout->rgba (Cutout); needs matte.  (Behind
+    // strokes, for the same reason.)
+    // edge: the mask is grown, shrunk, feathered or bordered (Edge), behind the clean-up and in front of the matte.  (The last
     // argument, for the same reason.)
     Image compute_mask(std::vector<Click> const& clicks, std::optional<Region> region = std::nullopt,
                        std::vector<int> const& refine_after = {}, std::optional<MaskCleanup> clean = std::nullopt,
                        std::optional<Prior> prior = std::nullopt, std::optional<Lasso> lasso = std::nullopt,
                        std::optional<Matte> matte = std::nullopt, std::vector<Stroke> const& strokes = {},
-                       std::optional<Cutout> cutout = std::nullopt) const {
+                       std::optional<Cutout> cutout = std::nullopt, std::optional<Edge> edge = std::nullopt) const {
         return std::move(compute_mask_batch({this}, std::vector<std::vector<Click>>{clicks}, {region}, {refine_after},
                                             clean ? std::vector<std::optional<MaskCleanup>>{clean} : std::vector<std::optional<MaskCleanup>>{},
                                             prior ? std::vector<std::optional<Prior>>{prior} : std::vector<std::optional<Prior>>{},
                                             lasso ? std::vector<std::optional<Lasso>>{lasso} : std::vector<std::optional<Lasso>>{},
                                             matte ? std::vector<std::optional<Matte>>{matte} : std::vector<std::optional<Matte>>{},
                                             strokes.empty() ? std::vector<std::vector<Stroke>>{} : std::vector<std::vector<Stroke>>{strokes},
-                                            cutout ? std::vector<std::optional<Cutout>>{cutout} : std::vector<std::optional<Cutout>>{})[0]);
+                                            cutout ? std::vector<std::optional<Cutout>>{cutout} : std::vector<std::optional<Cutout>>{},
+                                            edge ? std::vector<std::optional<Edge>>{edge} : std::vector<std::optional<Edge>>{})[0]);
     }
 
     // Select by scribbling (addition of this build): the strokes alone are the prompt -- the clicks sampled from them in the
     // order given, the first FOREGROUND one first (so at least one stroke is a foreground stroke), and an optional box.  cleanup
-    // matte and cutout as for compute_mask.  out_mask may be a stroke's map itself.  A stroke without a pixel >= 128 is reported by the
+    // matte, cutout and edge as for compute_mask.  out_mask may be a stroke's map itself.  A stroke without a pixel >= 128 is reported by the
     // library ("the stroke mark's map is empty") and nothing is delivered.
     void scribble(std::vector<Stroke> const& strokes, uint8_t* out_mask, std::optional<Region> region = std::nullopt,
                   std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
-                  std::optional<Cutout> cutout = std::nullopt) const {
+                  std::optional<Cutout> cutout = std::nullopt, std::optional<Edge> edge = std::nullopt) const {
         if (!out_mask) throw Exception("scribble: the result has a place to go");
         check_strokes(strokes, "scribble");
         check_matte(matte, "scribble");
         check_cutout(cutout, matte, "scribble");
+        check_edge(edge, "scribble");
         if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
             throw Exception("scribble: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         if (std::none_of(strokes.begin(), strokes.end(), [](Stroke const& s) { return s.label == 1; }))
@@ -427,15 +442,16 @@ class Segmentation {
         };
         for (Stroke const& s : strokes) entry(Region(Point{DLIMG_STROKE_MARK, s.clicks}, Point{s.label, 0}), s.map);
         if (cleanup) entry(Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}), nullptr);
+        if (edge) entry(Region(Point{DLIMG_EDGE_MARK, edge->offset}, Point{edge->feather, edge->border}), nullptr);
         if (matte) entry(Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}), matte->guide);
         if (cutout) entry(Region(Point{DLIMG_CUTOUT_MARK, cutout->radius}, Point{0, 0}), cutout->rgba);     // (this one is written)
         detail::check(api().get_segmentation_masks(hs.data(), int(hs.size()), nullptr, &regs.data()->top_left.x, ptrs.data()));
     }
     Image scribble(std::vector<Stroke> const& strokes, std::optional<Region> region = std::nullopt,
                    std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
-                   std::optional<Cutout> cutout = std::nullopt) const {
+                   std::optional<Cutout> cutout = std::nullopt, std::optional<Edge> edge = std::nullopt) const {
         Image m(extent(), Channels::mask);
-        scribble(strokes, m.pixels(), region, cleanup, matte, cutout);
+        scribble(strokes, m.pixels(), region, cleanup, matte, cutout, edge);
         return m;
     }
     static void check_strokes(std::vector<Stroke> const& strokes, char const* who) {
@@ -450,14 +466,15 @@ class Segmentation {
 
     // Snap a selection to the object (addition of this build): the lasso alone is the prompt -- its box, its most interior
     // point as a foreground click, and the selection itself as the mask input, whichever `what` names (Lasso) -- or the lasso
-    // and further clicks behind the derived one.  refine_after, cleanup, matte and cutout as for compute_mask.  out_mask may be
+    // and further clicks behind the derived one.  refine_after, cleanup, matte, cutout and edge as for compute_mask.  out_mask may be
     // lasso.mask itself: a selection snapped in place.
     void snap(Lasso const& lasso, uint8_t* out_mask, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
               std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
-              std::optional<Cutout> cutout = std::nullopt) const {
+              std::optional<Cutout> cutout = std::nullopt, std::optional<Edge> edge = std::nullopt) const {
         if (!lasso.mask || !out_mask) throw Exception("snap: a lasso has a mask, and the result a place to go");
         check_matte(matte, "snap");
         check_cutout(cutout, matte, "snap");
+        check_edge(edge, "snap");
         if (cleanup && (cleanup->max_hole < 0 || cleanup->max_island < 0 || (cleanup->max_hole == 0 && cleanup->max_island == 0)))
             throw Exception("snap: a clean-up mark has max_hole >= 0 and max_island >= 0, not both 0");
         if (clicks.size() > 8) throw Exception("snap: a prompt takes at most 8 clicks");
@@ -483,6 +500,7 @@ class Segmentation {
         }
         if (!clicks.empty() && !clicks[0].foreground) throw Exception("snap: the first click given is a foreground click");
         if (cleanup) entry(Point{0, 0}, Region(Point{DLIMG_CLEAN_MARK, cleanup->max_hole}, Point{cleanup->max_island, 0}));
+        if (edge) entry(Point{0, 0}, Region(Point{DLIMG_EDGE_MARK, edge->offset}, Point{edge->feather, edge->border}));
         if (matte) {
             entry(Point{0, 0}, Region(Point{DLIMG_MATTE_MARK, matte->radius}, Point{matte->eps, matte->channels}));
             ptrs.back() = const_cast<uint8_t*>(matte->guide);      // the mark's out_masks pointer is the guide, which the call only reads
@@ -496,9 +514,9 @@ class Segmentation {
     }
     Image snap(Lasso const& lasso, std::vector<Click> const& clicks = {}, std::vector<int> const& refine_after = {},
                std::optional<MaskCleanup> cleanup = std::nullopt, std::optional<Matte> matte = std::nullopt,
-               std::optional<Cutout> cutout = std::nullopt) const {
+               std::optional<Cutout> cutout = std::nullopt, std::optional<Edge> edge = std::nullopt) const {
         Image m(extent(), Channels::mask);
-        snap(lasso, m.pixels(), clicks, refine_after, cleanup, matte, cutout);
+        snap(lasso, m.pixels(), clicks, refine_after, cleanup, matte, cutout, edge);
         return m;
     }
     static void check_matte(std::optional<Matte> const& m, char const* who) {
@@ -509,6 +527,11 @@ class Segmentation {
     static void check_cutout(std::optional<Cutout> const& c, std::optional<Matte> const& m, char const* who) {
         if (c && (!c->rgba || c->radius < 0 || c->radius > 32 || !m || (m->channels != 3 && m->channels != 4)))
             throw Exception(std::string(who) + ": a cut-out has a place for its RGBA, a radius of 0 (the default) .. 32, and a matte of 3 or 4 channels on its prompt");
+    }
+    static void check_edge(std::optional<Edge> const& e, char const* who) {
+        if (e && (e->offset < -64 || e->offset > 64 || e->feather < 0 || e->feather > 32 || e->border < 0 || e->border > 32 ||
+                  (e->offset == 0 && e->feather == 0 && e->border == 0)))
+            throw Exception(std::string(who) + ": an edge has an offset of -64 .. 64, a feather of 0 .. 32 and a border of 0 .. 32, not all three 0");
     }
     static std::vector<int> refine_each(size_t clicks) {
         std::vector<int> after;
@@ -521,7 +544,7 @@ class Segmentation {
     // optional clean-up per prompt; prior: empty, or one optional prior per prompt; lasso: empty, or one optional lasso per
     // prompt (a prompt takes a prior or a lasso, not both); matte: empty, or one optional matte per prompt; strokes: empty, or
     // one list of strokes per prompt (empty: none), whose sampled clicks follow the prompt's clicks; cutout: empty, or one
-    // optional cut-out per prompt (which then has a matte).
+    // optional cut-out per prompt (which then has a matte); edge: empty, or one optional edge per prompt.
     static std::vector<Image> compute_mask_batch(std::vector<Segmentation const*> const& segs,
                                                  std::vector<std::vector<Click>> const& clicks,
                                                  std::vector<std::optional<Region>> const& regions = {},
@@ -531,12 +554,13 @@ class Segmentation {
                                                  std::vector<std::optional<Lasso>> const& lasso = {},
                                                  std::vector<std::optional<Matte>> const& matte = {},
                                                  std::vector<std::vector<Stroke>> const& strokes = {},
-                                                 std::vector<std::optional<Cutout>> const& cutout = {}) {
+                                                 std::vector<std::optional<Cutout>> const& cutout = {},
+                                                 std::vector<std::optional<Edge>> const& edge = {}) {
         if (clicks.size() != segs.size() || (!regions.empty() && regions.size() != segs.size()) ||
             (!refine_after.empty() && refine_after.size() != segs.size()) || (!clean.empty() && clean.size() != segs.size()) ||
             (!prior.empty() && prior.size() != segs.size()) || (!lasso.empty() && lasso.size() != segs.size()) ||
             (!matte.empty() && matte.size() != segs.size()) || (!strokes.empty() && strokes.size() != segs.size()) ||
-            (!cutout.empty() && cutout.size() != segs.size()))
+            (!cutout.empty() && cutout.size() != segs.size()) || (!edge.empty() && edge.size() != segs.size()))
             throw Exception("compute_mask_batch: one list of clicks, at most one region and at most one list of marks per segmentation");
         for (auto const& p : prior)
             if (p && (!p->mask || p->strength_milli < 0 || p->strength_milli > 100000))
@@ -547,6 +571,7 @@ class Segmentation {
         for (auto const& m : matte) check_matte(m, "compute_mask_batch");
         for (size_t j = 0; j < cutout.size(); ++j)
             check_cutout(cutout[j], matte.empty() ? std::optional<Matte>{} : matte[j], "compute_mask_batch");
+        for (auto const& e : edge) check_edge(e, "compute_mask_batch");
         for (auto const& s : strokes)
             if (!s.empty()) check_strokes(s, "compute_mask_batch");
         for (auto const& c : clean)
@@ -563,7 +588,8 @@ class Segmentation {
             if (!clicks[j][0].foreground) throw Exception("compute_mask_batch: the first click of a prompt is a foreground click");
             refined = refined || clicks[j].size() > 1 || (!clean.empty() && clean[j].has_value()) ||
                       (!prior.empty() && prior[j].has_value()) || (!lasso.empty() && lasso[j].has_value()) ||
-                      (!matte.empty() && matte[j].has_value()) || (!strokes.empty() && !strokes[j].empty());   // any continuation entry
+                      (!matte.empty() && matte[j].has_value()) || (!strokes.empty() && !strokes[j].empty()) ||
+                      (!edge.empty() && edge[j].has_value());                                                  // any continuation entry
             out.emplace_back(segs[j]->extent(), Channels::mask);
         }
         // The entry lists of table slot 14: the head entry of a prompt carries the handle, the first click and the box (an
@@ -615,6 +641,12 @@ class Segmentation {
                     pts.push_back(Point{0, 0});
                     ptrs.push_back(nullptr);
                     regs.push_back(Region(Point{DLIMG_CLEAN_MARK, clean[j]->max_hole}, Point{clean[j]->max_island, 0}));
+                }
+                if (!edge.empty() && edge[j]) {
+                    hs.push_back(nullptr);               // the edge mark, behind the clean-up mark and in front of the matte mark:
+                    pts.push_back(Point{0, 0});          // neither its point nor its pointer is read
+                    ptrs.push_back(nullptr);
+                    regs.push_back(Region(Point{DLIMG_EDGE_MARK, edge[j]->offset}, Point{edge[j]->feather, edge[j]->border}));
                 }
                 if (!matte.empty() && matte[j]) {
                     hs.push_back(nullptr);               // the matte mark, behind everything else of its prompt: its point is not

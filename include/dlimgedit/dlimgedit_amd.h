@@ -104,7 +104,9 @@ DLIMG_API int dlimg_amd_segmentation_device(dlimg_Segmentation seg, int* out_rep
  * prompt with the previous stage's logits as mask input, as there; clean-up marks, {DLIMG_CLEAN_MARK, max_hole,
  * max_island, 0}, mean what they mean there: the prompt's one mask is cleaned on the GPU that produced it -- in place at its
  * destination when that is memory of the same GPU, else in the lane's staging buffer before the peer copy -- and the mark's
- * out_offsets repeats its head's; a grid mark, {DLIMG_GRID_MARK, side, iou_permille, stability_permille} behind a head with an
+ * out_offsets repeats its head's; edge marks, {DLIMG_EDGE_MARK, offset, feather, border}, likewise: they need no pointer, the
+ * mask is grown, shrunk, feathered or bordered on the GPU that produced it, in place or in staging by the same rule, and the
+ * mark's out_offsets repeats its head's; a grid mark, {DLIMG_GRID_MARK, side, iou_permille, stability_permille} behind a head with an
  * empty region, delivers that prompt's label map where its mask would go, painted in place when the root is the producing
  * GPU, else in the lane's staging buffer before the peer copy, and its out_offsets repeats its head's too).  Mask i is produced on the GPU that holds
  * segs[i]'s embedding and is delivered into the memory of HIP device `root_device` at dev_out + offset_i, where
